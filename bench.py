@@ -37,6 +37,20 @@ against the 157.3 TFLOP/s fp32 vector peak (no MFMA applies to a recurrence).
 `cpu_baseline` times the reference's own AVX-512/AVX kernels (oracle/_ref, OpenMP dynamic,1
 like IntelPairHmm.cc:151-154) on a bounded sample of the same workload on the host cores this
 process may use (cgroup quota respected; `cores` = threads actually used).
+
+A plain run does only what the headline needs: set up, warm up, time the K steps and print the
+line (`roofline` and `kernels_ms` from the timed steps' own HIP events where those are kernels
+running alone, else null).  Everything that takes runs of its own -- the single-call probe and
+the issue ceilings (`single_call`, `fallback_pass`, `config.fallback_fraction`, the N>1 kernel
+times), `cpu_baseline`, the sub-records (`two_callers`, `host_path`, `small_batch`, `jni_path`,
+`pdhmm`, `sw`, `long_reads*`, `no_fallback`) and the N>1 `in_library` probe -- runs with `--full`:
+
+    python bench.py --gpus 1 --steps 10 --warmup 3 --full
+
+`--dump-outputs DIR` writes what the last timed step computed, the log10 likelihoods rank 0
+holds (all ranks' pairs, read-major), as DIR/log10_likelihoods.npy (float64; a fixed seeded
+sample of them when the batch has more than DUMP_MAX_VALUES pairs).  The inputs come from a
+fixed seed, so two builds run with the same arguments can be compared value for value.
 """
 import argparse
 import json
@@ -52,6 +66,18 @@ sys.path.insert(0, ROOT)
 
 FLOP_PER_CELL = 12.0          # 8 mul + 4 add, avx-pairhmm-template.h:213-222
 PEAK_FP32_VECTOR_TFLOPS = 157.3  # MI355X_MICROARCH.md: 256 CU x 256 flop/clk x 2.4 GHz
+DUMP_MAX_VALUES = 4 * 1024 * 1024  # --dump-outputs: 32 MB of float64 at most
+DUMP_SAMPLE_SEED = 20250418
+
+
+def dump_outputs(out_dir, values):
+    """--dump-outputs: the last timed step's log10 likelihoods (a torch tensor on rank 0) as float64 .npy."""
+    v = values.detach().cpu().numpy().astype(np.float64, copy=False).ravel()
+    if v.size > DUMP_MAX_VALUES:
+        idx = np.sort(np.random.RandomState(DUMP_SAMPLE_SEED).choice(v.size, DUMP_MAX_VALUES, replace=False))
+        v = v[idx]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "log10_likelihoods.npy"), v)
 
 
 def cpu_baseline(batch, budget_s=6.0):
@@ -587,8 +613,15 @@ def main():
     ap.add_argument("--double", action="store_true", help="useDoublePrecision (BASELINE config 3)")
     ap.add_argument("--fma-mode", type=int, default=1, choices=[0, 1], help="1 (default): the arithmetic of GKL's AVX-512 object (gcc-contracted FMAs); "
                                                                            "0: of its AVX object (unfused: 12 operations per cell), what GKL computes on a host without AVX-512")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the single_call / small_batch / host_path / no_fallback sub-records")
+    ap.add_argument("--full", action="store_true", help="also measure everything beyond the headline: the single-call probe and issue "
+                                                        "ceilings, cpu_baseline, the sub-records, the N>1 in-library probe (off: the "
+                                                        "timed steps and the line only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's log10 likelihoods to "
+                                                                         "DIR/log10_likelihoods.npy (float64)")
+    ap.add_argument("--max-processes", type=int, default=16, help="--full: the largest process count of small_batch.processes "
+                                                                  "(4, 8, 16 processes; a larger count is cut to this)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip cpu_baseline")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip the single_call / small_batch / host_path / no_fallback sub-records")
     ap.add_argument("--weak", action="store_true", help="N>1: every rank owns its own --reads reads (weak scaling) instead of a "
                                                         "read range of the one batch")
     ap.add_argument("--config4", action="store_true", help="BASELINE config 4: ONE 8000 x 125 batch (1 M pairs), sharded")
@@ -607,6 +640,10 @@ def main():
     ap.add_argument("--small-proc-device", type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument("--small-proc-seconds", type=float, default=1.5, help=argparse.SUPPRESS)
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.max_processes < 1:
+        ap.error("--max-processes must be at least 1")
     if a.jni_worker:
         # child-process mode: computeLikelihoodsNative through the mock JVM in a process of its own -- what a JVM is to the
         # device: the library's streams are the only ones the process has (in the process that measured everything else,
@@ -634,9 +671,9 @@ def main():
     # the processes FIRST costs the headline 1-4 % (sixteen processes' worth of host activity just before the timed loop).  So
     # the N = 1 run with its extras is two steps: everything that needs this process on the GPU runs in a child (this same
     # command, GKL_BENCH_INNER=1), and when that child is gone the parent -- which never opened the device -- measures the processes
-    # and prints the child's line with that record added.
-    if (int(os.environ.get("WORLD_SIZE", "1")) == 1 and a.gpus == 1 and not a.no_extras and not a.double and not a.overlap and a.fma_mode == 1
-            and os.environ.get("GKL_BENCH_INNER") != "1" and os.environ.get("GKL_BENCH_PROCESSES", "1") != "0"):
+    # and prints the child's line with that record added.  (--full only: a plain run measures in this process.)
+    if (a.full and int(os.environ.get("WORLD_SIZE", "1")) == 1 and a.gpus == 1 and not a.no_extras and not a.double and not a.overlap
+            and a.fma_mode == 1 and os.environ.get("GKL_BENCH_INNER") != "1" and os.environ.get("GKL_BENCH_PROCESSES", "1") != "0"):
         p = subprocess.run([sys.executable, os.path.abspath(__file__)] + sys.argv[1:], env=dict(os.environ, GKL_BENCH_INNER="1"),
                            stdout=subprocess.PIPE, text=True)
         line = next((ln for ln in reversed(p.stdout.splitlines()) if ln.startswith("{")), None)
@@ -661,7 +698,8 @@ def main():
         except Exception as e:
             res["jni_path"] = {"error": repr(e)}
         try:
-            rec = process_records(0 if os.environ.get("GKL_BENCH_SAME_DEVICE") == "1" else int(os.environ.get("LOCAL_RANK", "0")), a.workload)
+            rec = process_records(0 if os.environ.get("GKL_BENCH_SAME_DEVICE") == "1" else int(os.environ.get("LOCAL_RANK", "0")), a.workload,
+                                  counts=tuple(sorted({min(n, a.max_processes) for n in (4, 8, 16)})))
         except Exception as e:
             rec = {"error": repr(e)}
         res.setdefault("small_batch", {})["processes"] = rec
@@ -669,7 +707,7 @@ def main():
             # ... and the same deployment for PDHMM: P processes, each one caller looping fixture-sized regions
             try:
                 pr = process_records(0 if os.environ.get("GKL_BENCH_SAME_DEVICE") == "1" else int(os.environ.get("LOCAL_RANK", "0")), "pdhmm",
-                                     counts=(4, 8), duration_s=1.0)
+                                     counts=tuple(sorted({min(n, a.max_processes) for n in (4, 8)})), duration_s=1.0)
                 pr["note"] = ("P processes, each ONE caller with its own PDHMM context looping the fixture's 276 x 48 region through "
                               "gklhip_pdhmm_compute_cross (= computeLikelihoodsNative after marshalling), all started together")
             except Exception as e:
@@ -781,11 +819,12 @@ def main():
             gather.submit(k)
 
     def drain():
-        gather.finish()
+        full = gather.finish()    # the last step's result, every rank's pairs, on rank 0 (None elsewhere)
         torch.cuda.synchronize(dev)
         if world > 1:
             dist.barrier()
             torch.cuda.synchronize(dev)
+        return full
 
     for _ in range(a.warmup):
         step()
@@ -793,8 +832,10 @@ def main():
     t0 = time.perf_counter()
     for _ in range(a.steps):
         step()
-    drain()
+    last_out = drain()
     elapsed = time.perf_counter() - t0
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, last_out)
     my_elapsed = elapsed          # this rank's own clock around the same K steps (the line's time is the max over ranks)
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=comm_dev)
@@ -834,41 +875,49 @@ def main():
                          "fixed_cost_ms": round(v[4] - v[5] - v[6], 3), "gcups": round(v[1] / v[4] / 1e6, 1) if v[4] > 0 else None})
     if rank == 0:
         st = ctxs[0].stats()
-        with native.PairHmmContext(use_double=a.double, device=dev_index, record_events=1, fma_mode=a.fma_mode) as probe:
-            pout = torch.empty(batch.n_pairs, dtype=torch.float64, device=dev)
-            for _ in range(2):
-                probe.compute_device(dbatch, pout)
-            torch.cuda.synchronize(dev)
-            # latency of ONE call: nothing to overlap with (synchronised before and after)
-            def one_call():
-                probe.compute_device(dbatch, pout)
+        # --full: a probe context after the timed region (runs of its own); a plain run leaves these None
+        pst = single_ms = cells_fp64 = mix64_cells_per_s = mix_cells_per_s = mix_clock_ghz = None
+        if a.full:
+            with native.PairHmmContext(use_double=a.double, device=dev_index, record_events=1, fma_mode=a.fma_mode) as probe:
+                pout = torch.empty(batch.n_pairs, dtype=torch.float64, device=dev)
+                for _ in range(2):
+                    probe.compute_device(dbatch, pout)
                 torch.cuda.synchronize(dev)
-            single_ms = _median_ms(one_call, 5, 1)
-            pst = probe.stats()
-            st["n_fallback"] = pst["n_fallback"]   # needs a synchronising call: outside the timed region
-            # cells of the pairs the policy sent to the fp64 pass (flags of the probe call, read back outside the timed region)
-            try:
-                _, _, used = probe.raw(batch.n_pairs)
-                flagged = used.reshape(batch.n_reads, batch.n_haps).astype(np.int64)
-                cells_fp64 = int(batch.read_lens.astype(np.int64) @ flagged @ batch.hap_lens.astype(np.int64))
-                mix64_cells_per_s = None if a.double else probe.issue_ceiling(use_double=True, ms_budget=30.0)[0]
-            except Exception:
-                cells_fp64, mix64_cells_per_s = None, None
-            # the chip's issue ceiling for the recurrence's bare instruction mix (4 mul + 4 fma per cell, bank-clean
-            # operands, four wavefronts per SIMD) and the clock it sustains there: 50 ms, outside the timed region
-            try:
-                mix_cells_per_s, mix_clock_ghz = probe.issue_ceiling(use_double=a.double, ms_budget=50.0)
-            except Exception:
-                mix_cells_per_s, mix_clock_ghz = None, None
+                # latency of ONE call: nothing to overlap with (synchronised before and after)
+                def one_call():
+                    probe.compute_device(dbatch, pout)
+                    torch.cuda.synchronize(dev)
+                single_ms = _median_ms(one_call, 5, 1)
+                pst = probe.stats()
+                st["n_fallback"] = pst["n_fallback"]   # needs a synchronising call: outside the timed region
+                # cells of the pairs the policy sent to the fp64 pass (flags of the probe call, read back outside the timed region)
+                try:
+                    _, _, used = probe.raw(batch.n_pairs)
+                    flagged = used.reshape(batch.n_reads, batch.n_haps).astype(np.int64)
+                    cells_fp64 = int(batch.read_lens.astype(np.int64) @ flagged @ batch.hap_lens.astype(np.int64))
+                    mix64_cells_per_s = None if a.double else probe.issue_ceiling(use_double=True, ms_budget=30.0)[0]
+                except Exception:
+                    cells_fp64, mix64_cells_per_s = None, None
+                # the chip's issue ceiling for the recurrence's bare instruction mix (4 mul + 4 fma per cell, bank-clean
+                # operands, four wavefronts per SIMD) and the clock it sustains there: 50 ms, outside the timed region
+                try:
+                    mix_cells_per_s, mix_clock_ghz = probe.issue_ceiling(use_double=a.double, ms_budget=50.0)
+                except Exception:
+                    mix_cells_per_s, mix_clock_ghz = None, None
         k_ms = float(np.mean(ms_main))
         fb_ms = float(np.mean(ms_fb))
         dev_ms = float(np.mean(ms_dev))
         kernel_times_from = "HIP events of the timed steps"
+        kernels_alone = True
         if n_ctx > 1:
             # consecutive steps share the chip: a kernel's event-to-event time in the timed region includes the other
             # stream's kernels.  The durations of kernels running ALONE come from the probe call above.
-            k_ms, fb_ms, dev_ms = pst["ms_fwd_main"], pst["ms_fwd_fallback"], pst["ms_total_device"]
-            kernel_times_from = "the single-call probe after the timed region (in it consecutive steps overlap on two streams)"
+            if pst is not None:
+                k_ms, fb_ms, dev_ms = pst["ms_fwd_main"], pst["ms_fwd_fallback"], pst["ms_total_device"]
+                kernel_times_from = "the single-call probe after the timed region (in it consecutive steps overlap on two streams)"
+            else:
+                kernels_alone = False   # no roofline from these; --full times the kernels alone
+                kernel_times_from = "HIP events of the timed steps, where consecutive steps overlap on two streams (each includes the other's kernels)"
         step_ms = elapsed / a.steps * 1e3
         achieved = FLOP_PER_CELL * batch.cells / (k_ms * 1e-3) / 1e12
         traffic_profile = None
@@ -894,7 +943,7 @@ def main():
                                    f"100-500 bp), {'fp64 all pairs' if a.double else 'fp32 + fp64 fallback policy'}, "
                                    f"inputs and log10 outputs resident in HBM",
                        "pairs_per_gpu": batch.n_pairs, "cells_per_gpu": batch.cells,   # rank 0's share
-                       "fallback_fraction": round(st["n_fallback"] / batch.n_pairs, 4),
+                       "fallback_fraction": round(st["n_fallback"] / batch.n_pairs, 4) if st["n_fallback"] >= 0 else None,   # (-1: unknown, --full)
                        "parallelism": (f"one batch cut into {world} read ranges balanced by cells, one per rank; gather to rank 0 over RCCL, "
                                        f"overlapped with the next step" if strong else
                                        f"every rank its own reads x{world}; gather to rank 0" if world > 1 else "single GPU"),
@@ -924,7 +973,7 @@ def main():
                                  "peak (SIMD-32: one wave64 FMA per 2 cycles); it has no contraction, so it runs on the vector ALUs "
                                  "and issues no MFMA. The recurrence needs 4 mul + 4 fma per cell (1.5 flop per instruction: 0.75 "
                                  "of peak at best) and a SIMD issues one such op per ~2.3 cycles, not 2: issue_ceiling_tflops is "
-                                 "that bound, measured in this run (DESIGN.md section 3)"},
+                                 "that bound, measured in this run with --full (DESIGN.md section 3)"},
             # the second kernel of a step, priced the same way: the packed fp64 recomputation of the flagged pairs
             "fallback_pass": None if (a.double or not cells_fp64 or fb_ms <= 0) else {
                 "kernel": "pairhmm_fwd_jobs_kernel<double, 10>", "cells": cells_fp64, "kernel_ms": round(fb_ms, 3),
@@ -953,11 +1002,13 @@ def main():
             "single_call": {"ms_per_call": round(single_ms, 3), "gcups": round(batch.cells / single_ms / 1e6, 1),
                             "kernels_ms": {"fwd_main": round(pst["ms_fwd_main"], 3), "fwd_fp64_fallback": round(pst["ms_fwd_fallback"], 3)},
                             "fixed_cost_ms": round(single_ms - pst["ms_fwd_main"] - pst["ms_fwd_fallback"], 3),
-                            "note": "one device-resident call, synchronised before and after (host planning included)"},
+                            "note": "one device-resident call, synchronised before and after (host planning included)"} if single_ms is not None else None,
             "plan": {"chunks": st["n_chunks"], "hap_groups": st["n_hap_groups"], "rows_per_lane": st["rows_per_lane"],
                      "lane_fill": round(st["lane_fill"], 4)},
         }
-        if world == 1 and not a.no_extras and not a.double and n_ctx == 1 and a.fma_mode == 1:
+        if not kernels_alone:
+            res["roofline"] = None
+        if a.full and world == 1 and not a.no_extras and not a.double and n_ctx == 1 and a.fma_mode == 1:
             try:
                 # two callers on one GPU (what the JNI shim's slots give concurrent GATK threads, and what every rank of
                 # an N>1 run does): two contexts on two streams alternate between consecutive steps
@@ -1105,7 +1156,7 @@ def main():
                                       "fallback_fraction": round(rst["n_fallback"] / reg.n_pairs, 5)}
             except Exception as e:  # never lose the headline line to a sub-record
                 res["extras_error"] = repr(e)
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             try:
                 res["cpu_baseline"] = cpu_baseline(batch)
             except Exception as e:  # never lose the GPU line to a baseline problem
@@ -1115,7 +1166,7 @@ def main():
         dist.barrier()
         dist.destroy_process_group()
     if rank == 0:
-        if world > 1 and not a.no_extras:
+        if a.full and world > 1 and not a.no_extras:
             # The same batch through the LIBRARY's own multi-device path (one process, GKL_HIP_DEVICES-style context,
             # RCCL gather inside the C ABI) -- what a JVM gets.  After the process group is gone (the other ranks have
             # left their GPUs), in a child process with a time limit: a problem there must not cost the line.

@@ -6,11 +6,13 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REQUIRED = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
             "vs_baseline", "dtype", "data", "config", "roofline", "kernels_ms", "fixed_cost_ms", "single_call")
+PROCS_TOP = 15   # small_batch.processes' largest count under pytest (bench.py --full alone: 16)
 
 
 def _line(out):
@@ -21,8 +23,10 @@ def _line(out):
 
 @pytest.mark.gpu
 def test_bench_line_single_gpu():
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--reads", "600", "--haps", "24", "--steps", "3", "--warmup", "1"],
-                       capture_output=True, text=True, timeout=900, cwd=ROOT)
+    # --max-processes 15: this pytest process holds the GPU too; with 15 workers the run keeps to the 16 processes with the device
+    # open that bench.py --full on its own uses
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--reads", "600", "--haps", "24", "--steps", "3", "--warmup", "1",
+                        "--full", "--max-processes", str(PROCS_TOP)], capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-2000:]
     d = _line(p.stdout)
     for k in REQUIRED + ("cpu_baseline", "host_path", "small_batch", "no_fallback", "two_callers"):
@@ -91,7 +95,7 @@ def test_bench_line_single_gpu():
     # the deployment GATK produces: P processes x one caller on the one GPU
     pr = d["small_batch"]["processes"]
     assert "error" not in pr, pr
-    for n in (4, 8, 16):
+    for n in (4, 8, PROCS_TOP):
         assert pr[f"processes_{n}"]["aggregate_gcups"] > 0 and 0 < pr[f"processes_{n}"]["p50_ms"] <= pr[f"processes_{n}"]["p99_ms"]
         assert "first_call_after_idle_ms" in pr[f"processes_{n}"] and "calls_over_5ms" in pr[f"processes_{n}"]
     er = d["small_batch"]["eighth_device_resident"]
@@ -99,11 +103,63 @@ def test_bench_line_single_gpu():
 
 
 @pytest.mark.gpu
+def test_plain_bench_times_the_steps_alone_and_dumps_the_last_steps_outputs(tmp_path, oracle):
+    """Without --full the line is the headline alone (no probe, no sub-record, no child process); --dump-outputs writes the
+    last timed step's log10 likelihoods: the same bits in two runs, and the oracle's values within the device log10's tolerance."""
+    dumps = []
+    for i in range(2):
+        out = tmp_path / f"run{i}"
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--reads", "600", "--haps", "24", "--steps", "5", "--warmup", "2",
+                            "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert p.returncode == 0, p.stderr[-2000:]
+        d = _line(p.stdout)
+        assert d["metric"] == "pairhmm_gcups" and d["unit"] == "GCUPS" and d["higher_is_better"] is True and d["dtype"] == "f32"
+        assert d["n_gpus"] == 1 and d["steps"] == 5 and d["warmup"] == 2 and d["value"] > 0 and d["ms_per_step"] > 0
+        # value and ms_per_step describe the same timed steps
+        assert abs(d["value"] - d["config"]["cells_per_gpu"] / d["ms_per_step"] / 1e6) < 0.02 * d["value"]
+        for k in ("cpu_baseline", "host_path", "small_batch", "two_callers", "jni_path", "pdhmm", "sw", "no_fallback", "long_reads",
+                  "long_reads_5k", "in_library", "extras_error"):
+            assert k not in d, k
+        assert d["single_call"] is None and d["fallback_pass"] is None and d["roofline"]["issue_ceiling_tflops"] is None
+        assert d["kernels_ms"]["from"].startswith("HIP events") and 0 < d["roofline"]["frac"] < 1
+        assert os.listdir(out) == ["log10_likelihoods.npy"]
+        v = np.load(out / "log10_likelihoods.npy")
+        assert v.dtype == np.float64 and v.shape == (600 * 24,)
+        dumps.append(v)
+    assert dumps[0].tobytes() == dumps[1].tobytes()
+    from gkl_amd.synth import DEFAULT_SEED, make_batch
+    exp = oracle.batch(make_batch("hc", 600, 24, seed=DEFAULT_SEED), use_double=True, n_threads=4)
+    assert np.max(np.abs(dumps[0] - exp) / np.abs(exp)) < 1e-5
+
+
+def test_bench_options_cpu():
+    """--full and --dump-outputs exist; --steps below 1 is refused before anything is set up."""
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120, cwd=ROOT)
+    assert p.returncode == 0 and "--full" in p.stdout and "--dump-outputs" in p.stdout, p.stderr[-1000:]
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=120, cwd=ROOT)
+    assert p.returncode == 2 and "--steps" in p.stderr and not p.stdout
+
+
+def test_dump_outputs_takes_the_same_sample_of_a_large_output_every_time_cpu(tmp_path, monkeypatch):
+    import torch
+    import bench
+    monkeypatch.setattr(bench, "DUMP_MAX_VALUES", 1000)
+    v = torch.arange(5000, dtype=torch.float64)
+    bench.dump_outputs(str(tmp_path / "a"), v)
+    bench.dump_outputs(str(tmp_path / "b"), v)
+    a, b = np.load(tmp_path / "a" / "log10_likelihoods.npy"), np.load(tmp_path / "b" / "log10_likelihoods.npy")
+    assert a.dtype == np.float64 and a.size == 1000 and a.tobytes() == b.tobytes()
+    assert np.all(np.diff(a) > 0) and a[-1] < 5000          # distinct positions, in their original order
+    bench.dump_outputs(str(tmp_path / "c"), v[:800])         # small enough: every value, as it is
+    assert np.load(tmp_path / "c" / "log10_likelihoods.npy").tobytes() == v[:800].numpy().tobytes()
+
+
+@pytest.mark.gpu
 def test_bench_line_two_ranks_on_one_gpu():
     env = dict(os.environ, GKL_BENCH_SAME_DEVICE="1", GKL_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                         "--master-port", "29533", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--reads", "600", "--haps", "24",
-                        "--steps", "4", "--warmup", "2"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
+                        "--steps", "4", "--warmup", "2", "--full"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert p.returncode == 0, p.stderr[-2000:]
     d = _line(p.stdout)
     for k in REQUIRED:
@@ -165,7 +221,7 @@ def test_bench_starts_its_own_ranks_without_a_launcher():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     env.update(GKL_BENCH_SAME_DEVICE="1", GKL_BENCH_BACKEND="gloo")
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--reads", "600", "--haps", "24", "--steps", "4",
-                        "--warmup", "2", "--no-extras"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
+                        "--warmup", "2", "--full", "--no-extras"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert p.returncode == 0, p.stderr[-2000:]
     d = _line(p.stdout)
     for k in REQUIRED:
