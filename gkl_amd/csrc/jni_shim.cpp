@@ -27,6 +27,10 @@
 //     IllegalArgumentException instead of crashing the JVM;
 //   * HIP failures raise java/lang/RuntimeException, allocation failures
 //     java/lang/OutOfMemoryError (the reference's two classes, JavaData.h:130,140,150).
+// Client mode -- GKL_HIP_SERVER=PATH where the library loads: JNI_OnLoad asks the server on
+// PATH instead of probing a device, every slot's context is a client context of that server (gklhip_init reads the same
+// variable), the marshalling arenas are plain memory, and a big call is marshalled whole and sent as ONE request (no
+// pipelining: the mode is for region-sized calls).  The process then makes no HIP call at all.
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -46,6 +50,7 @@
 
 #include "../../include/gkl_hip_pairhmm.h"
 #include "../../include/gkl_pairhmm_jni.h"
+#define GKL_JNI_SERVER_PROBE 1   // (JNI_OnLoad: client mode pings the server)
 #include "jni_onload.h"
 
 #ifdef GKL_USE_SYSTEM_JNI
@@ -82,6 +87,10 @@ constexpr const char* kRTE = "java/lang/RuntimeException";
 // device -- is given back (like the context's own buffers, pairhmm_api.hip: trim_due) -- one 1.28 M-pair call must not keep
 // ~100 MB pinned per slot for the life of the JVM.  clear() runs at the start of a call, when nothing of the slot's previous
 // call is in flight any more.
+const bool g_client_mode = [] { const char* v = getenv("GKL_HIP_SERVER"); return v && *v; }();   // (read at load)
+void* arena_alloc(size_t bytes) { return g_client_mode ? malloc(bytes ? bytes : 1) : gklhip_host_alloc(bytes); }
+void arena_free(void* p) { if (g_client_mode) free(p); else gklhip_host_free(p); }
+
 struct PinnedBytes {
   uint8_t* p = nullptr;
   size_t cap = 0, len = 0;
@@ -89,12 +98,12 @@ struct PinnedBytes {
   PinnedBytes() = default;
   PinnedBytes(const PinnedBytes&) = delete;
   PinnedBytes& operator=(const PinnedBytes&) = delete;
-  ~PinnedBytes() { gklhip_host_free(p); }
+  ~PinnedBytes() { arena_free(p); }
   void clear() {
     if (since_grow < 64) since_grow++;
     if (cap > ((size_t)32 << 20) && len < cap / 4) {
       if (small_uses < 16) small_uses++;
-      if (small_uses >= 16 && since_grow >= 64) { gklhip_host_free(p); p = nullptr; cap = 0; small_uses = 0; }
+      if (small_uses >= 16 && since_grow >= 64) { arena_free(p); p = nullptr; cap = 0; small_uses = 0; }
     } else {
       small_uses = 0;
     }
@@ -103,10 +112,10 @@ struct PinnedBytes {
   uint8_t* grow(size_t add) {  // returns where the new bytes go
     if (len + add > cap) {
       const size_t want = std::max<size_t>(2 * cap, std::max<size_t>(len + add, 1 << 16));
-      uint8_t* q = static_cast<uint8_t*>(gklhip_host_alloc(want));
+      uint8_t* q = static_cast<uint8_t*>(arena_alloc(want));
       if (!q) throw std::bad_alloc();
       if (len) memcpy(q, p, len);
-      gklhip_host_free(p);
+      arena_free(p);
       p = q;
       cap = want;
       since_grow = 0;
@@ -703,7 +712,7 @@ JNIEXPORT void JNICALL Java_com_intel_gkl_pairhmm_IntelPairHmm_computeLikelihood
     };
     const char* pv = getenv("GKL_HIP_JNI_PIPELINE_PAIRS");   // (read per call: tests switch it)
     const int64_t pipeline_from = pv && *pv ? atoll(pv) : 160000LL;   // (a 4000 x 50 call: 3.5 -> 3.2 ms pipelined; below ~150k pairs one range is all there is)
-    bool pipelined = !(n_pairs < pipeline_from || n_reads < 64 || pipeline_from <= 0);
+    bool pipelined = !(n_pairs < pipeline_from || n_reads < 64 || pipeline_from <= 0 || g_client_mode);
     if (pipelined && !sl->pipe) {
       // first big call of this slot: second engine (same configuration as the slot's first, whatever initNative has
       // been told since) and the compute threads.  If they cannot be had -- device memory, thread limit -- the call

@@ -35,6 +35,7 @@
 #include "pairhmm_tables.h"
 #include "pairhmm_aux_kernels.h"
 #include "pairhmm_host_finalize.h"
+#include "pairhmm_remote.h"
 
 #include "pairhmm_ctx.h"
 #include "pairhmm_device_pass.h"
@@ -147,6 +148,7 @@ static int init_devices_impl(const gklhip_config* cfg, const int32_t* devices, i
 int gklhip_release_idle(gklhip_ctx* c, int32_t* streams_released) {
   if (streams_released) *streams_released = 0;
   if (!c) return fail(GKLHIP_ERR_INVALID_ARG, "context is NULL");
+  if (c->remote) return GKLHIP_OK;   // (the server's context keeps what it holds)
   std::unique_lock<std::mutex> lock(c->mu, std::try_to_lock);
   if (!lock.owns_lock()) return GKLHIP_OK;   // a call is running: nothing is idle
   int n = 0;
@@ -183,8 +185,32 @@ int gklhip_release_idle(gklhip_ctx* c, int32_t* streams_released) {
   return GKLHIP_OK;
 }
 
+// A client context: a socket to the PairHMM server and an arena (pairhmm_remote.cpp); no HIP call on this path.
+static int connect_impl(const char* socket_path, const gklhip_config* cfg, gklhip_ctx** out_ctx) {
+  if (!out_ctx) return fail(GKLHIP_ERR_INVALID_ARG, "out_ctx is NULL");
+  *out_ctx = nullptr;
+  if (!cfg) return fail(GKLHIP_ERR_INVALID_ARG, "config is NULL");
+  if (cfg->abi_version != GKLHIP_ABI_VERSION)
+    return fail(GKLHIP_ERR_INVALID_ARG, "config ABI version %d, library %d", cfg->abi_version, GKLHIP_ABI_VERSION);
+  std::unique_ptr<gklhip_ctx> c(new gklhip_ctx());
+  c->cfg = *cfg;
+  memset(&c->stats, 0, sizeof c->stats);
+  std::string err;
+  const int rc = gklhip_remote::connect(socket_path, cfg, &c->remote, &err);
+  if (rc != GKLHIP_OK) return fail(rc, "%s", err.c_str());
+  *out_ctx = c.release();
+  return GKLHIP_OK;
+}
+
+// GKL_HIP_SERVER=PATH: every gklhip_init of the process is a client context of the server on PATH
+static const char* server_socket_from_env() {
+  const char* v = getenv("GKL_HIP_SERVER");
+  return v && *v ? v : nullptr;
+}
+
 int gklhip_fault_inject(const char* spec);
 static int init_impl(const gklhip_config* cfg, gklhip_ctx** out_ctx) {
+  if (const char* path = server_socket_from_env()) return connect_impl(path, cfg, out_ctx);
   static std::once_flag fault_env;
   std::call_once(fault_env, [] { if (const char* v = getenv("GKLHIP_FAULT_INJECT")) (void)gklhip_fault_inject(v); });
   // GKL_HIP_DEVICES=0,1,...: shard every call over these devices (used when the config does not pin one)
@@ -202,7 +228,35 @@ int gklhip_done(gklhip_ctx* c) {
   return GKLHIP_OK;
 }
 
-int gklhip_num_devices(gklhip_ctx* c) { return c ? (int)c->dev.size() : 0; }
+int gklhip_num_devices(gklhip_ctx* c) { return !c ? 0 : c->remote ? gklhip_remote::num_devices(c->remote) : (int)c->dev.size(); }
+
+int gklhip_is_remote(gklhip_ctx* c) { return c && c->remote ? 1 : 0; }
+
+int gklhip_connect(const char* socket_path, const gklhip_config* cfg, gklhip_ctx** out_ctx) {
+  return guarded([&] { return connect_impl(socket_path, cfg, out_ctx); });
+}
+
+int gklhip_server_stats(const char* socket_path, gklhip_server_info* out) {
+  return guarded([&] {
+    if (!out) return fail(GKLHIP_ERR_INVALID_ARG, "NULL argument");
+    std::string err;
+    const int rc = gklhip_remote::server_stats(socket_path, out, &err);
+    return rc == GKLHIP_OK ? rc : fail(rc, "%s", err.c_str());
+  });
+}
+
+int gklhip_host_register(void* p, size_t bytes) {
+  if (!p || !bytes) return fail(GKLHIP_ERR_INVALID_ARG, "NULL or empty range");
+  const hipError_t e = hipHostRegister(p, bytes, hipHostRegisterDefault);
+  if (e != hipSuccess) { (void)hipGetLastError(); return fail(GKLHIP_ERR_HIP, "hipHostRegister: %s", hipGetErrorString(e)); }
+  return GKLHIP_OK;
+}
+
+int gklhip_host_unregister(void* p) {
+  if (!p) return GKLHIP_OK;
+  HIP_TRY(hipHostUnregister(p));
+  return GKLHIP_OK;
+}
 
 int gklhip_gather_backend(gklhip_ctx* c) {
   if (!c || c->dev.size() < 2) return 0;
@@ -230,6 +284,7 @@ int gklhip_partition_reads(int32_t n_reads, const int64_t* read_off, int32_t n_p
 
 static int compute_device_impl(gklhip_ctx* c, const gklhip_batch* dev_batch, double* out_dev, void* hip_stream) {
   if (!c) return fail(GKLHIP_ERR_INVALID_ARG, "context is NULL (initNative not called)");
+  if (c->remote) return fail(GKLHIP_ERR_UNSUPPORTED, "gklhip_compute_device: device-resident batches cannot go to the PairHMM server (client context)");
   int rc = validate(dev_batch);
   if (rc) return rc;
   if (!out_dev && (int64_t)dev_batch->n_reads * dev_batch->n_haps > 0)
@@ -288,6 +343,8 @@ static int compute_device_impl(gklhip_ctx* c, const gklhip_batch* dev_batch, dou
 static std::atomic<int64_t> g_fault_from{0}, g_fault_count{0}, g_fault_calls{0};
 int gklhip_fault_inject(const char* spec) {
   long from = 0, count = 0;
+  if (spec && *spec && server_socket_from_env())
+    return fail(GKLHIP_ERR_UNSUPPORTED, "gklhip_fault_inject: this process computes through the PairHMM server (GKL_HIP_SERVER)");
   if (spec && *spec) {
     if (strncmp(spec, "compute:", 8) != 0) return fail(GKLHIP_ERR_INVALID_ARG, "fault spec: compute:N or compute:NxK");
     char* end = nullptr;
@@ -312,6 +369,12 @@ static int compute_impl(gklhip_ctx* c, const gklhip_batch* hb, double* out_host)
   const int64_t n_pairs = (int64_t)hb->n_reads * hb->n_haps;
   if (n_pairs == 0) return GKLHIP_OK;
   if (!out_host) return fail(GKLHIP_ERR_INVALID_ARG, "output array is NULL");
+  if (c->remote) {
+    std::lock_guard<std::mutex> lock(c->mu);
+    std::string err;
+    rc = gklhip_remote::compute(c->remote, hb, out_host, &c->stats, &err);
+    return rc == GKLHIP_OK ? rc : fail(rc, "%s", err.c_str());
+  }
   if (fault_due()) {
     for (int64_t i = 0; i < n_pairs; i++) out_host[i] = std::numeric_limits<double>::quiet_NaN();
     return fail(GKLHIP_ERR_HIP, "injected fault (GKLHIP_FAULT_INJECT)");
@@ -341,7 +404,15 @@ static int compute_impl(gklhip_ctx* c, const gklhip_batch* hb, double* out_host)
   return multi_compute_host(c, c->dev, hb, out_host);
 }
 
+// A client process (GKL_HIP_SERVER set; decided once per process) makes no HIP call: its "page-locked" buffers are plain
+// memory -- the server copies from the client's arena anyway.
+static bool client_process() {
+  static const bool v = server_socket_from_env() != nullptr;
+  return v;
+}
+
 void* gklhip_host_alloc(size_t bytes) {
+  if (client_process()) return malloc(bytes ? bytes : 1);
   void* p = nullptr;
   if (hipHostMalloc(&p, bytes ? bytes : 1, hipHostMallocDefault | hipHostMallocPortable) != hipSuccess) {
     (void)hipGetLastError();
@@ -351,11 +422,13 @@ void* gklhip_host_alloc(size_t bytes) {
 }
 
 void gklhip_host_free(void* p) {
+  if (client_process()) { free(p); return; }
   if (p) (void)hipHostFree(p);
 }
 
 static int get_step_times_impl(gklhip_ctx* ctx, int32_t steps_back, float* ms_main, float* ms_fallback, float* ms_total) {
   if (!ctx) return fail(GKLHIP_ERR_INVALID_ARG, "context is NULL");
+  if (ctx->remote) return fail(GKLHIP_ERR_UNSUPPORTED, "gklhip_get_step_times: not available on a client context of the PairHMM server");
   std::lock_guard<std::mutex> lock(ctx->mu);
   DevCtx* c = ctx->dev[0];  // (several devices: device 0's shard)
   if (c->cfg.record_events != 2) return fail(GKLHIP_ERR_INVALID_ARG, "context was not created with record_events = 2");
@@ -382,6 +455,7 @@ int gklhip_get_stats(gklhip_ctx* c, gklhip_stats* out) {
 
 static int get_raw_impl(gklhip_ctx* ctx, float* raw32, double* raw64, uint8_t* used64) {
   if (!ctx) return fail(GKLHIP_ERR_INVALID_ARG, "context is NULL");
+  if (ctx->remote) return fail(GKLHIP_ERR_UNSUPPORTED, "gklhip_get_raw: the raw sums stay on the PairHMM server (client context)");
   std::lock_guard<std::mutex> lock(ctx->mu);
   int64_t n_fallback = 0;
   bool any = false;

@@ -30,6 +30,7 @@ int gklhip_small_call_counts(int device, int64_t out[3], int reset) {
 // clock the chip sustains under this load (it clocks to its power budget).
 int gklhip_measure_issue_ceiling(gklhip_ctx* ctx, int use_double, double ms_budget, double* cells_per_s, double* clock_ghz) {
   if (!ctx || !cells_per_s) return fail(GKLHIP_ERR_INVALID_ARG, "NULL argument");
+  if (ctx->remote) return fail(GKLHIP_ERR_UNSUPPORTED, "gklhip_measure_issue_ceiling: not available on a client context of the PairHMM server");
   std::lock_guard<std::mutex> lock(ctx->mu);
   DevCtx* c = ctx->dev[0];
   HIP_TRY(hipSetDevice(c->device));

@@ -147,7 +147,10 @@ struct gklhip_ctx {
   int last_set = 0;
   gklhip_stats stats;
   int32_t last_reads = 0, last_haps = 0;
+  // A client context (gklhip_connect): every call goes to the PairHMM server; nothing above is used, and no HIP call is made.
+  gklhip_remote::Client* remote = nullptr;
   ~gklhip_ctx() {
+    if (remote) { gklhip_remote::close(remote); return; }
     workers.clear();  // joins the threads
     for (size_t d = 0; d < comms.size(); d++)
       if (comms[d]) { (void)hipSetDevice(dev[d]->device); (void)g_rccl.CommDestroy(comms[d]); }

@@ -48,6 +48,26 @@ class Stats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+SERVER_MAX_DEVICES = 16
+
+
+class ServerInfo(C.Structure):
+    """gklhip_server_info: the PairHMM server's counters (gklhip_server_stats)."""
+    _fields_ = [("protocol", C.c_int32), ("pid", C.c_int32), ("calls_served", C.c_int64), ("calls_failed", C.c_int64),
+                ("calls_active", C.c_int32), ("live_connections", C.c_int32), ("connections_total", C.c_int64),
+                ("arenas_registered", C.c_int64), ("arenas_copied", C.c_int64), ("requests_refused", C.c_int64),
+                ("n_devices", C.c_int32), ("reserved", C.c_int32), ("device", C.c_int32 * SERVER_MAX_DEVICES),
+                ("connections", C.c_int32 * SERVER_MAX_DEVICES), ("small_calls", (C.c_int64 * 3) * SERVER_MAX_DEVICES)]
+
+    def as_dict(self):
+        d = {n: getattr(self, n) for n, _ in self._fields_[:10]}
+        k = self.n_devices
+        d["devices"] = list(self.device[:k])
+        d["connections_per_device"] = list(self.connections[:k])
+        d["small_call_counts"] = [tuple(int(x) for x in self.small_calls[i]) for i in range(k)]
+        return d
+
+
 _lib = None
 
 
@@ -112,6 +132,12 @@ def load_library(path: Optional[str] = None):
     lib.gklhip_get_table_f32.restype = C.c_int64
     lib.gklhip_get_table_f64.argtypes = [C.c_int, C.c_void_p, C.c_int64]
     lib.gklhip_get_table_f64.restype = C.c_int64
+    lib.gklhip_connect.argtypes = [C.c_char_p, C.POINTER(Config), C.POINTER(C.c_void_p)]
+    lib.gklhip_connect.restype = C.c_int
+    lib.gklhip_is_remote.argtypes = [C.c_void_p]
+    lib.gklhip_is_remote.restype = C.c_int
+    lib.gklhip_server_stats.argtypes = [C.c_char_p, C.POINTER(ServerInfo)]
+    lib.gklhip_server_stats.restype = C.c_int
     if lib.gklhip_abi_version() != ABI_VERSION:
         raise RuntimeException("libgklhip_pairhmm.so ABI mismatch")
     if path is None:
@@ -220,6 +246,17 @@ def small_call_counts(device: int = 0, reset: bool = False):
     return int(out[0]), int(out[1]), int(out[2])
 
 
+def server_stats(socket_path: str) -> dict:
+    """Counters of the PairHMM server on `socket_path` (gklhip_server_stats): calls served, live connections,
+    connections and small-call counts per device, arenas registered in place versus copied.  Makes no HIP call."""
+    lib = load_library()
+    info = ServerInfo()
+    st = lib.gklhip_server_stats(os.fsencode(socket_path), C.byref(info))
+    if st != OK:
+        _raise(lib, st)
+    return info.as_dict()
+
+
 def rccl_selftest(device: int = 0) -> None:
     lib = load_library()
     st = lib.gklhip_rccl_selftest(device)
@@ -229,16 +266,22 @@ def rccl_selftest(device: int = 0) -> None:
 
 class PairHmmContext:
     """One gklhip context (= one initNative).  `devices` = a list of device ordinals: every call is sharded over
-    them inside the library (a device may appear twice)."""
+    them inside the library (a device may appear twice).  `server` = the socket of a PairHMM server
+    (gkl_amd.server): a client context whose calls that server computes (gklhip_connect; this process makes no HIP
+    call for it).  GKL_HIP_SERVER in the environment makes every context without `devices` a client context."""
 
     def __init__(self, use_double: bool = False, max_threads: int = 0, device: int = -1,
                  fma_mode: int = 1, finalize: int = -1, record_events: bool = False,
-                 rows_per_lane: int = 0, lib_path: Optional[str] = None, devices=None):
+                 rows_per_lane: int = 0, lib_path: Optional[str] = None, devices=None, server: Optional[str] = None):
         self.lib = load_library(lib_path)
         cfg = Config(ABI_VERSION, device, int(use_double), int(max_threads), int(fma_mode),
                      int(finalize), int(record_events), int(rows_per_lane))
         h = C.c_void_p()
-        if devices:
+        if server is not None:
+            if devices:
+                raise IllegalArgumentException("a client context of a server takes no device list")
+            st = self.lib.gklhip_connect(os.fsencode(server), C.byref(cfg), C.byref(h))
+        elif devices:
             arr = (C.c_int32 * len(devices))(*devices)
             st = self.lib.gklhip_init_devices(C.byref(cfg), arr, len(devices), C.byref(h))
         else:
@@ -251,6 +294,11 @@ class PairHmmContext:
     @property
     def n_devices(self) -> int:
         return self.lib.gklhip_num_devices(self.handle)
+
+    @property
+    def is_remote(self) -> bool:
+        """True for a client context of a PairHMM server."""
+        return bool(self.lib.gklhip_is_remote(self.handle))
 
     @property
     def gather_backend(self) -> str:

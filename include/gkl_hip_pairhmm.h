@@ -153,7 +153,8 @@ int gklhip_compute(gklhip_ctx* ctx, const gklhip_batch* host_batch, double* out_
 
 /* Page-locked host memory for a binder's marshalling buffers (replaces the per-array
  * Get<T>ArrayElements pins of JavaData.h:135-154 with one flat, DMA-able staging area that is
- * reused across calls).  NULL on failure.  Not tied to a context. */
+ * reused across calls).  NULL on failure.  Not tied to a context.  In a process with GKL_HIP_SERVER set (client mode,
+ * decided at the first call) this is plain memory: such a process makes no HIP call. */
 void* gklhip_host_alloc(size_t bytes);
 void gklhip_host_free(void* p);
 
@@ -212,6 +213,47 @@ int gklhip_release_idle(gklhip_ctx* ctx, int32_t* streams_released);
  * fail with GKLHIP_ERR_HIP before any work (output array poisoned with NaN); NULL or "" disarms.  The first gklhip_init of
  * a process arms it from the environment variable GKLHIP_FAULT_INJECT. */
 int gklhip_fault_inject(const char* spec);
+
+/* ---- Client mode: one server process per node owns the GPU (gkl_amd/lib/gklhip_server) ----
+ * gklhip_connect: a context whose calls are computed by the server listening on the Unix-domain socket `socket_path`.
+ * The server makes a context of its own from `cfg` (use_double, max_threads, fma_mode, finalize; device only when it
+ * was started without --devices) and runs every call through its gklhip_compute, so the calls of many client
+ * processes meet in one process's small-call combiner.  A client process makes no HIP call: batches travel through a
+ * shared-memory arena (memfd) the server maps.  gklhip_init with GKL_HIP_SERVER=PATH in the environment is
+ * gklhip_connect(PATH, cfg, out_ctx).  On a remote context gklhip_compute, gklhip_get_stats, gklhip_release_idle (no-op)
+ * and gklhip_done work; gklhip_compute_device, gklhip_get_raw, gklhip_get_step_times and gklhip_measure_issue_ceiling
+ * return GKLHIP_ERR_UNSUPPORTED, and so does gklhip_fault_inject in a process with GKL_HIP_SERVER set.  A server that
+ * has gone away fails the call with GKLHIP_ERR_HIP and a message that names the socket. */
+#define GKLHIP_SERVER_PROTOCOL 1
+#define GKLHIP_SERVER_MAX_DEVICES 16
+typedef struct {
+  int32_t protocol;          /* GKLHIP_SERVER_PROTOCOL of the server */
+  int32_t pid;               /* the server's process id */
+  int64_t calls_served;      /* gklhip_compute calls answered (any status) */
+  int64_t calls_failed;      /* ... of them with a status other than GKLHIP_OK */
+  int32_t calls_active;      /* calls inside gklhip_compute right now */
+  int32_t live_connections;  /* compute connections open right now */
+  int64_t connections_total; /* compute connections accepted since the start */
+  int64_t arenas_registered; /* arenas mapped and page-locked in place (hipHostRegister): H2D is DMA from the client's pages */
+  int64_t arenas_copied;     /* arenas whose calls are copied into the server's own pinned staging (registration failed) */
+  int64_t requests_refused;  /* malformed requests, refused hellos and peers of another uid */
+  int32_t n_devices;         /* entries used below: the --devices list, or the devices the connections asked for */
+  int32_t reserved;
+  int32_t device[GKLHIP_SERVER_MAX_DEVICES];          /* device ordinal of each entry */
+  int32_t connections[GKLHIP_SERVER_MAX_DEVICES];     /* live compute connections on each entry */
+  int64_t small_calls[GKLHIP_SERVER_MAX_DEVICES][3];  /* gklhip_small_call_counts of each entry's device */
+} gklhip_server_info;
+
+int gklhip_connect(const char* socket_path, const gklhip_config* cfg, gklhip_ctx** out_ctx);
+/* 1 for a context made by gklhip_connect (or gklhip_init under GKL_HIP_SERVER), 0 otherwise. */
+int gklhip_is_remote(gklhip_ctx* ctx);
+/* Asks the server on `socket_path` for its counters (also the JNI library's load-time probe in client mode). */
+int gklhip_server_stats(const char* socket_path, gklhip_server_info* out);
+
+/* Page-locks existing host memory (hipHostRegister) so that gklhip_compute's copies from it are DMA; the server does
+ * this to the arena it maps.  gklhip_host_unregister undoes it. */
+int gklhip_host_register(void* p, size_t bytes);
+int gklhip_host_unregister(void* p);
 
 const char* gklhip_strerror(int status);
 /* Thread-local detail message of the last failing call on this thread. */
