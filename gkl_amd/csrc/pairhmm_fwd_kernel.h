@@ -240,6 +240,7 @@ struct WaveJob {
   // registers
   T M[RPL], X[RPL], Y[RPL];
   T pMM[RPL], pGAPM[RPL], pMX[RPL], pXX[RPL], pMY[RPL];
+  T nMM, nGAPM, nMX, nXX;  // pMM, pGAPM, pMX, pXX of slot 0 of the lane BELOW (two-value hand-off of the asm programs)
   T dM, dX, dY;       // row above at the previous column (diagonal inputs)
   T rM, rX, rY;       // row above at this lane's NEXT column, fetched at the end of the previous step
   T sM, sX;           // running sums of the lane's bottom row
@@ -321,6 +322,13 @@ struct WaveJob {
         code[s] = -1;
       }
     }
+    // Two-value hand-off (tools/gen_fwd_asm.py: handoff): this lane computes, for the lane below, what that lane's row 0
+    // needs from this lane's bottom row -- with THAT row's coefficients.  Lane 63 has no lane below and keeps its own;
+    // a lane below that starts another read or is idle masks what it receives (lmask = 0), so any finite values serve.
+    nMM = __shfl_down(pMM[0], 1, kLanes);
+    nGAPM = __shfl_down(pGAPM[0], 1, kLanes);
+    nMX = __shfl_down(pMX[0], 1, kLanes);
+    nXX = __shfl_down(pXX[0], 1, kLanes);
     own_codes = 0;
 #pragma unroll
     for (int s = 0; s < RPL; s++) own_codes |= (uint32_t)((code[s] >= 0 && code[s] < 4) ? code[s] : 0) << (2 * s);
@@ -361,6 +369,12 @@ struct WaveJob {
     rX = recv_above(X[RPL - 1], lmask);
     rY = recv_above(Y[RPL - 1], lmask);
   }
+
+  // The three-value state (r, d) in the two-value form of the asm programs' hand-off: what row 0 computes from it in
+  // `advance` -- its X of the coming column, its M-inner of that column (from d) and of the one after (from r).
+  __device__ __forceinline__ T handoff_x0() const { return mul_add2<FMA>(rX, pXX[0], rM, pMX[0]); }
+  __device__ __forceinline__ T handoff_inner_d() const { return m_inner<FMA>(dM, dX, dY, pMM[0], pGAPM[0]); }
+  __device__ __forceinline__ T handoff_inner_r() const { return m_inner<FMA>(rM, rX, rY, pMM[0], pGAPM[0]); }
 
   __device__ __forceinline__ void load_priors(uint32_t code, int lane, T* pr) const {
     // 24-bit multiply: kRowBytes is 3072 in fp64 and a plain v_mul_lo_u32 issues at quarter rate

@@ -34,6 +34,15 @@ so the first one decides) has one separator in flight at a time and its output c
 branch of the first kind, a dependent load per storing step in the second.
 Preconditions (checked by the caller, WaveJob::run): fp64: no haplotype of the job contains an 'N' (four prior planes), no
 packed output.
+
+The hand-off between lanes (docs/NOTES.md 63).  In the three-value form a lane fetches the bottom row M, X, Y of the lane
+above at the end of every step (`dpp_recv`), keeps it one step as the row above (r) and one more as the diagonal (d), and
+its row 0 computes X(0) and the inner sum of M(0) from it.  The whole-job FMA programs f32r8 and f64r10 (`Cfg.two`; not
+their wide variants) use the two-value form: the lane above performs those five operations with the lower row's
+coefficients and sends the two results (`handoff`) -- one DPP less per fp32 step, two per fp64 step, no arithmetic added,
+the same bits.  The same programs keep no running sum of M: the bottom row's Y of a read's last lane carries it.
+Everything else -- wide, narrow and unfused programs, the fast blocks of the round-3 arrangement, the C++ steps -- keeps
+the three values and the sum.
 """
 import sys
 
@@ -112,6 +121,26 @@ class Cfg:
             assert self.PR(0) % 4 == 0 and self.last < 256
             self.codes, self.planes, self.plane_stride, self.code_shift = 4, R // 2, 1024, None   # code * kRowBytes via KREG
             self.vec_bytes = 16
+
+        # Two-value hand-off (the whole-job FMA programs f32r8 and f64r10, not their wide variants): a lane sends the lane
+        # below that lane's next X(0) and the M-inner of its row 0 instead of its own bottom row M, X, Y (see `handoff`).
+        # The registers are those the three-value form no longer needs, so one map serves both forms:
+        #   NX   X(0) of the lane, two registers alternating with the step parity (the fixed X(0) and the first of RS)
+        #   NI   M-inner of row 0, likewise
+        #   NPMM, NGAPM, NPMX, NPXX   pMM, pGAPM, pMX, pXX of slot 0 of the lane BELOW (where PMM(0), GAPM(0), PMX(0) were:
+        #        odd registers in the fp32 map, like the coefficients they replace; NPXX odd too)
+        #   SNX, SNI   the two values on their way down (fp32: an even X or Y, an odd coefficient and these in every fmac)
+        self.two = fma and name in ("f32r8", "f64r10")
+        (a0, a1, a2), (b0, b1, b2) = self.RS
+        self.NX = [self.X(0), a0]
+        self.NI = [a2, b0]
+        self.NPMM, self.NGAPM, self.NPMX, self.NPXX = self.PMM(0), self.GAPM(0), self.PMX(0), a1
+        self.SNX, self.SNI = b2, b1
+        # The same programs keep no running sum of M: the bottom row's Y of a read's LAST lane feeds nothing the result needs
+        # (itself and a masked lane), so it carries the sum -- pMY = pYY = 1 there (see `recurrence`).  PYYB: pYY of the
+        # bottom slot, no longer the slot's pXX in such a lane (fp32: an odd register, the wide variant's flag value; fp64:
+        # where the sum was).
+        self.PYYB = self.SM if f64 else self.FV
 
     # operand text
     def v(self, n):
@@ -198,44 +227,59 @@ def recurrence_unfused(c, yo, yn, d, r, general):
     return o
 
 
-def recurrence(c, yo, yn, d, r, general):
+def recurrence(c, yo, yn, d, r, general, h2=None):
     """M-inner + Y bottom-up, prior multiply, X column top-down, running sum of M.  yo/yn: Y source / destination register
-    functions (the same one: in place through v_fma with a product temporary)."""
+    functions (the same one: in place through v_fma with a product temporary).
+    h2 = (x0, x0_old, ni), the two-value hand-off: row 0's X of this column and its M-inner arrived from the lane above
+    (registers x0 and ni; x0_old holds the previous column's X of row 0), so row 0 is its prior multiply and its Y alone.
+    And no running sum of M: the bottom row's Y takes PYYB for its pYY, and the driver sets it and the row's pMY to 1 in a
+    read's last lane -- Y' = fma(Y, 1, M * 1) = round(Y + M), the sum's own chain of rounded adds in the same column order,
+    one column late (the separator step adds the last column before the store reads it).  That Y feeds itself and the lane
+    below, which starts another read or is idle and masks what it receives."""
     if not c.fma:
         return recurrence_unfused(c, yo, yn, d, r, general)
     R, o = c.R, []
-    dM, dX, dY = d
-    rM, rX, rY = r
+    dM, dX, dY = d if h2 is None else (None, None, None)
+    rM, rX, rY = r if h2 is None else (None, None, None)
+    x0, x0_old, ni = h2 if h2 is not None else (c.X(0), c.X(0), c.X(0))
+    pyy = lambda s: c.PYYB if (h2 is not None and s == R - 1) else c.PXX(s)
     inplace = yo is yn
     for s in range(R - 1, -1, -1):
-        md, xd, yd = (c.M(s - 1), c.X(s - 1), yo(s - 1)) if s > 0 else (dM, dX, dY)
+        md, xd, yd = (c.M(s - 1), c.X(s - 1) if s > 1 else x0_old, yo(s - 1)) if s > 0 else (dM, dX, dY)
         t = c.YB(s) if inplace else yn(s)
-        o.append(f"{fp(c, 'mul')} {c.v(c.X(s))}, {c.v(md)}, {c.v(c.PMM(s))}")
+        inner = s > 0 or h2 is None
+        if inner:
+            o.append(f"{fp(c, 'mul')} {c.v(c.X(s))}, {c.v(md)}, {c.v(c.PMM(s))}")
         o.append(f"{fp(c, 'mul')} {c.v(t)}, {c.v(c.M(s))}, {c.v(c.PMY(s))}")
-        o.append(f"{fp(c, 'fmac')} {c.v(c.X(s))}, {c.v(xd)}, {c.v(c.GAPM(s))}")
+        if inner:
+            o.append(f"{fp(c, 'fmac')} {c.v(c.X(s))}, {c.v(xd)}, {c.v(c.GAPM(s))}")
         if inplace:
-            o.append(f"{fp(c, 'fma')} {c.v(yn(s))}, {c.v(yo(s))}, {c.v(c.PXX(s))}, {c.v(t)}")   # = fmac into the product: one rounding
+            o.append(f"{fp(c, 'fma')} {c.v(yn(s))}, {c.v(yo(s))}, {c.v(pyy(s))}, {c.v(t)}")   # = fmac into the product: one rounding
         else:
-            o.append(f"{fp(c, 'fmac')} {c.v(yn(s))}, {c.v(yo(s))}, {c.v(c.PXX(s))}")
-        o.append(f"{fp(c, 'fmac')} {c.v(c.X(s))}, {c.v(yd)}, {c.v(c.GAPM(s))}")
+            o.append(f"{fp(c, 'fmac')} {c.v(yn(s))}, {c.v(yo(s))}, {c.v(pyy(s))}")
+        if inner:
+            o.append(f"{fp(c, 'fmac')} {c.v(c.X(s))}, {c.v(yd)}, {c.v(c.GAPM(s))}")
     o.append("s_waitcnt lgkmcnt(0)")
+    inner_of = lambda s: ni if (s == 0 and h2 is not None) else c.X(s)
     if general and not c.f64:
         # no haplotype base in the column: the lane's prior rows were read from beyond the LDS allocation, i.e. are 0
         # (prior_loads), and v_mul_legacy_f32 makes 0 * anything = 0, also for the Inf / NaN of an overflowed pair
         for s in range(R):
-            o.append(f"v_mul_legacy_f32 {c.v(c.M(s))}, {c.v(c.X(s))}, {c.v(c.PR(s))}")
+            o.append(f"v_mul_legacy_f32 {c.v(c.M(s))}, {c.v(inner_of(s))}, {c.v(c.PR(s))}")
     else:
         for s in range(R):
-            o.append(f"{fp(c, 'mul')} {c.v(c.M(s))}, {c.v(c.X(s))}, {c.v(c.PR(s))}")
+            o.append(f"{fp(c, 'mul')} {c.v(c.M(s))}, {c.v(inner_of(s))}, {c.v(c.PR(s))}")
         if general:
             for s in range(R):
                 o += and_mask(c, c.M(s), c.NSEP)     # no haplotype base in the column: M = 0 (bitwise: NaN / Inf too)
-    o.append(f"{fp(c, 'mul')} {c.v(c.X(0))}, {c.v(rM)}, {c.v(c.PMX(0))}")
-    o.append(f"{fp(c, 'fmac')} {c.v(c.X(0))}, {c.v(rX)}, {c.v(c.PXX(0))}")
+    if h2 is None:
+        o.append(f"{fp(c, 'mul')} {c.v(c.X(0))}, {c.v(rM)}, {c.v(c.PMX(0))}")
+        o.append(f"{fp(c, 'fmac')} {c.v(c.X(0))}, {c.v(rX)}, {c.v(c.PXX(0))}")
     for s in range(1, R):
         o.append(f"{fp(c, 'mul')} {c.v(c.X(s))}, {c.v(c.M(s - 1))}, {c.v(c.PMX(s))}")
-        o.append(f"{fp(c, 'fmac')} {c.v(c.X(s))}, {c.v(c.X(s - 1))}, {c.v(c.PXX(s))}")
-    o.append(f"{fp(c, 'add')} {c.v(c.SM)}, {c.v(c.SM)}, {c.v(c.M(R - 1))}")
+        o.append(f"{fp(c, 'fmac')} {c.v(c.X(s))}, {c.v(c.X(s - 1) if s > 1 else x0)}, {c.v(c.PXX(s))}")
+    if h2 is None:
+        o.append(f"{fp(c, 'add')} {c.v(c.SM)}, {c.v(c.SM)}, {c.v(c.M(R - 1))}")
     return o
 
 
@@ -320,38 +364,68 @@ def wide_publish(c):
             f"ds_write_b32 v{c.WADDR}, v{c.FV}", "s_mov_b64 exec, -1"]
 
 
-def fast_step(c, u, last, e, wide=False, lab=0):
-    """one stream column, every lane inside a haplotype.  fp32: Y ping-pongs between Ya and Yb (VOP2 v_fmac); fp64: in place."""
+def handoff(c, y_reg):
+    """Two-value hand-off, the sending side, once the lane's bottom row (M, X and Y in `y_reg`) is final for the column:
+        SNX = fma(X, nPXX, M * nPMX)                         X of row 0 of the lane below at its next column
+        SNI = fma(Y, nGAPM, fma(X, nGAPM, M * nPMM))         M-inner of that row at the column after that
+    -- the operations, in the order and on the values, that the lane below performs itself in the three-value form
+    (`recurrence`, row 0), with that lane's coefficients (WaveJob::setup loads them).  The lane below takes both through its
+    isolation mask: a first or idle lane receives +0, what its own arithmetic on masked inputs gives, and an overflowed
+    neighbour's Inf / NaN dies in the AND as before."""
+    R = c.R
+    m, x = c.M(R - 1), c.X(R - 1)
+    return [f"{fp(c, 'mul')} {c.v(c.SNI)}, {c.v(m)}, {c.v(c.NPMM)}",
+            f"{fp(c, 'mul')} {c.v(c.SNX)}, {c.v(m)}, {c.v(c.NPMX)}",
+            f"{fp(c, 'fmac')} {c.v(c.SNI)}, {c.v(x)}, {c.v(c.NGAPM)}",
+            f"{fp(c, 'fmac')} {c.v(c.SNX)}, {c.v(x)}, {c.v(c.NPXX)}",
+            f"{fp(c, 'fmac')} {c.v(c.SNI)}, {c.v(y_reg)}, {c.v(c.NGAPM)}"]
+
+
+def fast_step(c, u, last, e, wide=False, lab=0, two=False):
+    """one stream column, every lane inside a haplotype.  fp32: Y ping-pongs between Ya and Yb (VOP2 v_fmac); fp64: in place.
+    two: the two-value hand-off.  Both values live for two steps (X of row 0 is also the next column's diagonal input of
+    row 1; the M-inner is for the column after the next), so each has two registers that alternate with the step parity."""
     R = c.R
     if c.f64:
         yo = yn = c.YA
     else:
         yo, yn = (c.YA, c.YB) if u % 2 == 0 else (c.YB, c.YA)
     r, d = c.RS[u % 2], c.RS[(u + 1) % 2]   # r: the row above at THIS column; d: at the previous one, overwritten by this step's fetch
+    p = u % 2
     o = [f"v_and_or_b32 v{c.ENT}, {e}, v{c.DIRECT}, v{c.EAB}"]
     o += prior_loads(c, c.ENT)
-    o += recurrence(c, yo, yn, d, r, False)
+    if two:
+        o += recurrence(c, yo, yn, None, None, False, (c.NX[p], c.NX[1 - p], c.NI[p]))
+        o += handoff(c, yn(R - 1))
+    else:
+        o += recurrence(c, yo, yn, d, r, False)
     o.append("s_nop 1")
     if not last:
         o.append(f"v_and_b32_dpp v{c.EAB}, v{c.ENT}, v{c.NDIRECT} {DPP}")
-    o += dpp_recv(c, d[0], c.M(R - 1))
-    o += dpp_recv(c, d[2], yn(R - 1))
-    o += dpp_recv(c, d[1], c.X(R - 1))
+    if two:
+        o += dpp_recv(c, c.NX[1 - p], c.SNX)    # X of row 0 at the next column (this column's stays where it is)
+        o += dpp_recv(c, c.NI[p], c.SNI)        # M-inner of row 0 at the column after the next
+    else:
+        o += dpp_recv(c, d[0], c.M(R - 1))
+        o += dpp_recv(c, d[2], yn(R - 1))
+        o += dpp_recv(c, d[1], c.X(R - 1))
     o.append(f"{fp(c, 'add')} {c.v(c.SX)}, {c.v(c.SX)}, {c.v(c.X(R - 1))}")
     if wide:
         o += wide_handoff(c, d, yn(R - 1), lab)
     return o
 
 
-def fast_block(c, ents, wide=False):
+def fast_block(c, ents, wide=False, two=False):
     o = ["s_nop 1", f"v_and_b32_dpp v{c.EAB}, v{c.ENT}, v{c.NDIRECT} {DPP}"]
     for u in range(U):
-        o += fast_step(c, u, u == U - 1, ents[u], wide, 300 + 4 * u)
+        o += fast_step(c, u, u == U - 1, ents[u], wide, 300 + 4 * u, two)
     return o
 
 
-def general_step(c, e, lab, wide=False):
-    """one stream column, any entry kind; parity-neutral (Y in Ya in place, row-above set in RS[0], diagonal set in RS[1]).
+def general_step(c, e, lab, wide=False, two=False):
+    """one stream column, any entry kind; parity-neutral (Y in Ya in place, row-above set in RS[0], diagonal set in RS[1];
+    two-value hand-off: this column's X of row 0 and M-inner in NX[0] and NI[0], the previous column's X in NX[1], the
+    next column's M-inner in NI[1] -- two moves per step keep it so, where the three-value form has three).
     `lab`: base of this copy's local labels.  Scalar state: S_CNT steps left in this run (counted here), S_BT = the value of
     S_CNT at which the step feeds the haplotype's separator (0xffffffff: never), S_ORIG the output column of the separator in flight."""
     R = c.R
@@ -373,12 +447,19 @@ def general_step(c, e, lab, wide=False):
         # the zero prior the column needs, without touching the eight products afterwards
         o.append(f"v_min_u32 v{c.VAL}, {OOB_PLANE}, v{c.ENT}")
     o += prior_loads(c, c.VAL)
-    o += recurrence(c, c.YA, c.YA, d, r, True)
-    o.append(f"{fp(c, 'add')} {c.v(c.SX)}, {c.v(c.SX)}, {c.v(c.X(R - 1))}")
-    for k in range(3):
-        o += mov(c, d[k], r[k])
+    if two:
+        o += recurrence(c, c.YA, c.YA, None, None, True, (c.NX[0], c.NX[1], c.NI[0]))
+        o.append(f"{fp(c, 'add')} {c.v(c.SX)}, {c.v(c.SX)}, {c.v(c.X(R - 1))}")
+        o += mov(c, c.NX[1], c.NX[0])
+        o += mov(c, c.NI[0], c.NI[1])
+    else:
+        o += recurrence(c, c.YA, c.YA, d, r, True)
+        o.append(f"{fp(c, 'add')} {c.v(c.SX)}, {c.v(c.SX)}, {c.v(c.X(R - 1))}")
+        for k in range(3):
+            o += mov(c, d[k], r[k])
     # the pair's result: lanes that hold the LAST row of a read (%[outmask]) and are on the separator in flight
-    o.append(f"{fp(c, 'add')} {c.v(c.VAL)}, {c.v(c.SM)}, {c.v(c.SX)}")
+    # (two: the sum of M is the bottom row's Y of the storing lanes, this column's M already in -- before the mask below)
+    o.append(f"{fp(c, 'add')} {c.v(c.VAL)}, {c.v(c.YA(R - 1) if two else c.SM)}, {c.v(c.SX)}")
     # a haplotype's separator: any entry below the pre-roll words (signed; S_LIM = kEntNoEmit).  With one separator in the
     # array at a time its output column is S_ORIG; with several (%[multi]: a haplotype no longer than the array is deep)
     # every lane looks its own up by the stream-order index its separator carries
@@ -410,7 +491,8 @@ def general_step(c, e, lab, wide=False):
     o.append(f"{L(1)}:")
     for s in range(R):
         o += and_mask(c, c.YA(s), c.NSEP)                     # column-0 state of the next haplotype: Y = 0 ...
-    o += and_mask(c, c.SM, c.NSEP)
+    if not two:
+        o += and_mask(c, c.SM, c.NSEP)
     o += and_mask(c, c.SX, c.NSEP)
     # ... and, in the step that feeds the separator, Y0 of the next haplotype in the pad row of every read's first lane
     # (those lanes take the entry directly, so they are on the separator right now; PADSLOT is -1 in every other lane)
@@ -426,10 +508,16 @@ def general_step(c, e, lab, wide=False):
         for h in range(c.w):
             o.append(f"v_cndmask_b32_e32 v{c.YA(s) + h}, v{c.YA(s) + h}, v{c.Y0N + h}, vcc")
     o.append(f"{L(3)}:")
-    o.append("s_nop 1")
-    o += dpp_recv(c, r[0], c.M(R - 1))
-    o += dpp_recv(c, r[2], c.YA(R - 1))
-    o += dpp_recv(c, r[1], c.X(R - 1))
+    if two:
+        o += handoff(c, c.YA(R - 1))                          # (the bottom row is final: masks and Y0 are in)
+        o.append("s_nop 1")
+        o += dpp_recv(c, c.NX[0], c.SNX)
+        o += dpp_recv(c, c.NI[1], c.SNI)
+    else:
+        o.append("s_nop 1")
+        o += dpp_recv(c, r[0], c.M(R - 1))
+        o += dpp_recv(c, r[2], c.YA(R - 1))
+        o += dpp_recv(c, r[1], c.X(R - 1))
     if wide:
         o += wide_handoff(c, r, c.YA(R - 1), lab + 5)
     return o
@@ -438,6 +526,7 @@ def general_step(c, e, lab, wide=False):
 def program(c, wide=False):
     """the asm statement: general(%[n_pre]) -> fast(%[n_blk] blocks) -> general(%[n_post], its last step feeding the
     separator when %[has_sep])."""
+    two = c.two and not wide
     ents = [f"s{S_E0 + u}" for u in range(U)]
     load = [f"s_load_dwordx8 s[{S_E0}:{S_E0 + 7}], s[{S_SRC}:{S_SRC + 1}], 0x0",
             f"s_add_u32 s{S_SRC}, s{S_SRC}, 32", f"s_addc_u32 s{S_SRC + 1}, s{S_SRC + 1}, 0",
@@ -452,7 +541,7 @@ def program(c, wide=False):
     if wide:
         o += wide_wait(c, 200)
     for u in range(U):
-        o += general_step(c, ents[u], 100 + 10 * u, wide)
+        o += general_step(c, ents[u], 100 + 10 * u, wide, two)
         if wide and u == U - 1:
             o += wide_publish(c)
         o.append(f"s_sub_u32 {S_CNT}, {S_CNT}, 1")
@@ -480,7 +569,7 @@ def program(c, wide=False):
     o += load
     if wide:
         o += wide_wait(c, 210)
-    o += fast_block(c, ents, wide)
+    o += fast_block(c, ents, wide, two)
     if wide:
         o += wide_publish(c)
     o.append(f"s_sub_u32 {S_CNT}, {S_CNT}, 1")
@@ -495,22 +584,33 @@ def program(c, wide=False):
     return o
 
 
-def decls(c, o):
+def decls(c, o, two=False):
     R = c.R
     T = "double" if c.f64 else "float"
     inout, consts = [], []
     for s in range(R):
         inout.append((f"j.M[{s}]", c.M(s), f"m{s}"))
-    for s in range(R):
+    for s in range(1 if two else 0, R):
         inout.append((f"j.X[{s}]", c.X(s), f"x{s}"))
     for s in range(R):
         inout.append((f"j.Y[{s}]", c.YA(s), f"y{s}"))
-    inout += [("j.rM", c.RS[0][0], "rm"), ("j.rX", c.RS[0][1], "rx"), ("j.rY", c.RS[0][2], "ry"),
-              ("j.dM", c.RS[1][0], "dm"), ("j.dX", c.RS[1][1], "dx"), ("j.dY", c.RS[1][2], "dy"),
-              ("j.sM", c.SM, "sm"), ("j.sX", c.SX, "sx")]
-    for s in range(R):
+    if two:
+        # the job's three-value state (row above at this column r, at the previous one d) in the two-value form
+        inout += [("j.handoff_x0()", c.NX[0], "nx0"), ("j.X[0]", c.NX[1], "nx1"),
+                  ("j.handoff_inner_d()", c.NI[0], "ni0"), ("j.handoff_inner_r()", c.NI[1], "ni1")]
+    else:
+        inout += [("j.rM", c.RS[0][0], "rm"), ("j.rX", c.RS[0][1], "rx"), ("j.rY", c.RS[0][2], "ry"),
+                  ("j.dM", c.RS[1][0], "dm"), ("j.dX", c.RS[1][1], "dx"), ("j.dY", c.RS[1][2], "dy")]
+    inout += ([] if two else [("j.sM", c.SM, "sm")]) + [("j.sX", c.SX, "sx")]
+    if two:
+        # a read's last lane sums M in its bottom row's Y: Y' = fma(Y, 1, M * 1)
+        consts += [(f"(j.out_read >= 0 ? {T}(1) : j.pXX[{R - 1}])", c.PYYB, "pyyb"),
+                   (f"(j.out_read >= 0 ? {T}(1) : j.pMY[{R - 1}])", c.PMY(R - 1), f"pmy{R - 1}")]
+        consts += [("j.nMM", c.NPMM, "npmm"), ("j.nGAPM", c.NGAPM, "npgapm"), ("j.nMX", c.NPMX, "npmx"), ("j.nXX", c.NPXX, "npxx"),
+                   ("j.pXX[0]", c.PXX(0), "pxx0"), ("j.pMY[0]", c.PMY(0), "pmy0")]
+    for s in range(1 if two else 0, R):
         consts += [(f"j.pMM[{s}]", c.PMM(s), f"pmm{s}"), (f"j.pGAPM[{s}]", c.GAPM(s), f"pgapm{s}"), (f"j.pMX[{s}]", c.PMX(s), f"pmx{s}"),
-                   (f"j.pXX[{s}]", c.PXX(s), f"pxx{s}"), (f"j.pMY[{s}]", c.PMY(s), f"pmy{s}")]
+                   (f"j.pXX[{s}]", c.PXX(s), f"pxx{s}")] + ([] if two and s == R - 1 else [(f"j.pMY[{s}]", c.PMY(s), f"pmy{s}")])
     for expr, reg, name in inout + consts:
         o.append(f"  {T} {name} = {expr};")
     return inout, consts
@@ -531,9 +631,13 @@ def emit_asm(o, ins, outs, inp, clob, indent="    "):
     o.append(f"{indent}    : " + ", ".join(f"\"{x}\"" for x in clob) + ");")
 
 
-def clobbers(c):
+def clobbers(c, two=False):
     R = c.R
     cl = set()
+    if two:
+        for h in range(c.w):
+            cl.add(c.SNX + h)
+            cl.add(c.SNI + h)
     for s in range(R):
         for h in range(c.w):
             cl.add(c.YB(s) + h)
@@ -572,7 +676,8 @@ def driver(c, o, wide=False):
     o.append(f"  {CT}* y0s = ({CT}*)a.y0;")
     o.append("  const int sb = hap_pos[hap_begin];")
     o.append(f"  j.reset_state(y0s[hap_begin]);")
-    inout, consts = decls(c, o)
+    two = c.two and not wide
+    inout, consts = decls(c, o, two)
     o.append("  uint32_t ent = kEntPreroll;")
     o.append("  const uint32_t lmask = j.lmask, direct = j.direct, ndirect = ~j.direct;")
     o.append("  const uint32_t loff = (uint32_t)(uintptr_t)j.lds + (uint32_t)lane * (uint32_t)Job::kVecBytes;")
@@ -661,7 +766,7 @@ def driver(c, o, wide=False):
         ", [orig] \"s\"(orig), [orig_old] \"s\"(orig_old), [multi] \"s\"(multi_s), [haporig] \"s\"(haporig_s), [outmask] \"s\"(outmask), " \
         "[raw] \"s\"(raw), " + ("" if c.f64 else "[packed] \"s\"(packed), [minacc] \"s\"(minacc), ") + y0in + \
         ", [n_pre] \"s\"(n_pre), [n_blk] \"s\"(n_blk), [n_post] \"s\"(n_post), [has_sep] \"s\"(has_sep)"
-    clob = clobbers(c)
+    clob = clobbers(c, two)
     if wide:
         # early clobber: without it the compiler may keep an input of the same VALUE (orig = 0, n_blk = 0 in the pre-roll
         # call, where st is 0 too) in the very register the program counts its steps in
@@ -739,8 +844,8 @@ def main(path):
         driver(c, o)
         if wide:
             driver(c, o, wide=True)
-        fb = fast_block(c, [f"s{S_E0 + u}" for u in range(U)])
-        gs = general_step(c, "s72", 100)
+        fb = fast_block(c, [f"s{S_E0 + u}" for u in range(U)], two=c.two)
+        gs = general_step(c, "s72", 100, two=c.two)
         nv = lambda ins: sum(1 for i in ins if i.startswith("v_"))
         stats.append(f"{c.name}: fast block {nv(fb)} VALU = {nv(fb) / (U * c.R):.3f} per cell; general step {nv(gs)} VALU "
                      f"({nv(gs) - (6 + (2 if c.f64 else 1) + 2 * c.R * c.w // c.w)} without the rare store / Y0 sections: see the listing)")
