@@ -9,6 +9,7 @@
 // GKL_JNI_SERVER_PROBE (libgkl_pairhmm.so): with GKL_HIP_SERVER=PATH set the library is a client of the PairHMM server
 // on PATH, and the probe asks that server instead of the device -- no HIP call; a server that cannot be reached fails
 // the load the same way (GATK falls back to its Java PairHMM).
+// GKL_JNI_PDHMM_SERVER_PROBE (libgkl_pdhmm.so): the same for the PDHMM library, through gklhip_pdhmm_server_stats.
 #pragma once
 #include <hip/hip_runtime_api.h>
 
@@ -19,6 +20,10 @@
 // (weak: the JNI layer's CPU test build links the shim against a stub of the C ABI that has no client mode)
 extern "C" int gklhip_server_stats(const char* socket_path, gklhip_server_info* out) __attribute__((weak));
 #endif
+#ifdef GKL_JNI_PDHMM_SERVER_PROBE
+// (weak for the same reason: a CPU test build of the shim against a stub of the C ABI has no client mode)
+extern "C" int gklhip_pdhmm_server_stats(const char* socket_path, gklhip_pdhmm_server_info* out) __attribute__((weak));
+#endif
 
 extern "C" JNIEXPORT jint JNICALL JNI_OnLoad(JavaVM*, void*) {
   const char* force = getenv("GKL_HIP_LOAD_WITHOUT_DEVICE");
@@ -28,6 +33,13 @@ extern "C" JNIEXPORT jint JNICALL JNI_OnLoad(JavaVM*, void*) {
   if (server && *server) {
     gklhip_server_info info;
     return gklhip_server_stats && gklhip_server_stats(server, &info) == GKLHIP_OK ? JNI_VERSION_1_8 : JNI_ERR;
+  }
+#endif
+#ifdef GKL_JNI_PDHMM_SERVER_PROBE
+  const char* pd_server = getenv("GKL_HIP_SERVER");
+  if (pd_server && *pd_server) {
+    gklhip_pdhmm_server_info info;
+    return gklhip_pdhmm_server_stats && gklhip_pdhmm_server_stats(pd_server, &info) == GKLHIP_OK ? JNI_VERSION_1_8 : JNI_ERR;
   }
 #endif
   int n = 0;

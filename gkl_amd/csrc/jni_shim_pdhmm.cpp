@@ -5,6 +5,9 @@
 // computeLikelihoodsNative are marshalled like the PairHMM shim's (jni_shim.cpp: marshal_reads): 13 JNI calls per
 // read and 7 per haplotype inside a local frame per 32 holders (r05: 40 and 16, plus seven heap vectors per holder --
 // for the fixture's 276 x 48 region more JNI time in a real JVM than the 0.3 ms the call itself takes).
+// Client mode -- GKL_HIP_SERVER=PATH where the library loads: JNI_OnLoad asks the server on
+// PATH instead of probing a device, and gklhip_pdhmm_init (which reads the same variable) makes the context a client
+// context of that server.  Nothing else here touches HIP: the process then makes no HIP call at all.
 #include <algorithm>
 #include <cstdint>
 #include <cstdio>
@@ -18,6 +21,7 @@
 #include "../../include/gkl_hip_pairhmm.h"
 #include "../../include/gkl_hip_pdhmm.h"
 #include "../../include/gkl_pdhmm_jni.h"
+#define GKL_JNI_PDHMM_SERVER_PROBE 1   // (JNI_OnLoad: client mode pings the server)
 #include "jni_onload.h"
 
 #ifdef GKL_USE_SYSTEM_JNI

@@ -18,7 +18,9 @@
 namespace gklhip_wire {
 
 constexpr uint32_t kMagic = 0x534c4b47u;   // "GKLS"
-enum MsgType : uint32_t { kHello = 1, kArena = 2, kCompute = 3, kStats = 4 };
+// 5-7: the PDHMM side (pdhmm_remote.cpp).  A connection is of one kind, fixed by its first message: a PairHMM
+// connection (kHello) refuses kPdCompute, a PDHMM connection (kPdHello) refuses kCompute; kArena and kPdStats work on both.
+enum MsgType : uint32_t { kHello = 1, kArena = 2, kCompute = 3, kStats = 4, kPdHello = 5, kPdCompute = 6, kPdStats = 7 };
 
 struct Hello {
   int32_t abi_version;   // GKLHIP_ABI_VERSION of the client
@@ -35,6 +37,27 @@ struct Compute {
   // byte offsets into the arena: the two int64 offset arrays, the six byte arrays, the n_reads * n_haps output doubles
   uint64_t read_off, hap_off, read_bases, read_quals, ins_gop, del_gop, gcp, hap_bases, out;
 };
+struct PdHello {
+  int32_t abi_version;   // GKLHIP_ABI_VERSION of the client
+  int32_t protocol;      // GKLHIP_SERVER_PROTOCOL of the client
+  int32_t device;        // -1 = the server's choice
+  int32_t reserved;
+};
+struct PdCompute {
+  int32_t layout;        // 0 = paired (gklhip_pdhmm_compute), 1 = cross (gklhip_pdhmm_compute_cross_batched)
+  int32_t n_read_items, n_hap_items;   // paired: both = batch
+  int32_t max_hap_len, max_read_len;   // row strides of the haplotype and the read arrays
+  int32_t flags;         // bit 0 fma_mode, bit 1 tail_mode: per call (both can change on a context)
+  int64_t ref_batch_pairs;
+  // byte offsets into the arena: the seven byte arrays [items][stride], the two int64 length arrays, the output doubles
+  uint64_t hap_bases, hap_pdbases, read_bases, read_qual, read_ins_qual, read_del_qual, gcp, hap_lengths, read_lengths, out;
+};
+static_assert(sizeof(PdHello) == 16 && sizeof(PdCompute) == 112, "wire format");
+struct PdComputeReply {  // from the server's context after the call
+  float kernel_ms;
+  int32_t routing[3];
+};
+static_assert(sizeof(PdComputeReply) == 16, "wire format");
 struct Request {
   uint32_t magic;
   uint32_t type;
@@ -42,6 +65,8 @@ struct Request {
     Hello hello;
     Arena arena;
     Compute compute;
+    PdHello pd_hello;
+    PdCompute pd_compute;
     uint8_t raw[112];
   } u;
 };
@@ -50,7 +75,8 @@ static_assert(sizeof(Request) == 120, "wire format");
 struct ReplyHead {
   int32_t status;        // gklhip_status
   uint32_t text_len;     // error text (status != GKLHIP_OK)
-  uint32_t payload_len;  // Hello: HelloReply; Compute: gklhip_stats of the call; Stats: gklhip_server_info
+  uint32_t payload_len;  // Hello: HelloReply; Compute: gklhip_stats of the call; Stats: gklhip_server_info;
+                         // PdHello: int32 device; PdCompute: PdComputeReply; PdStats: gklhip_pdhmm_server_info
   uint32_t reserved;
 };
 struct HelloReply {

@@ -7,9 +7,16 @@
 // clients meet in the process's small-call combiner exactly as the calls of threads of one process do.  Prints `ready`
 // on stdout once it listens; SIGTERM (or SIGINT) stops accepting, lets the calls in flight finish, removes the socket
 // and exits 0.  Plain C++ over the C ABI (tests/test_server_cpu.py links it against a stub of that ABI).
+//
+// PDHMM: a connection that opens with a PdHello gets a gklhip_pdhmm context of its own; its calls go, one by one, through
+// gklhip_pdhmm_compute / _compute_cross_batched of libgklhip_pdhmm.so.  That library is loaded at run time when the
+// first such connection arrives (GKL_HIP_PDHMM_LIB, else next to this program): the server links no PDHMM symbol, and
+// without the library it serves PairHMM as before.  GKL_HIP_PDHMM_TABLE / GKL_HIP_PDHMM_PIPELINE are read here, by the
+// process that computes.
 #ifndef _GNU_SOURCE
 #define _GNU_SOURCE
 #endif
+#include <dlfcn.h>
 #include <errno.h>
 #include <fcntl.h>
 #include <poll.h>
@@ -33,6 +40,7 @@
 #include <vector>
 
 #include "../../include/gkl_hip_pairhmm.h"
+#include "../../include/gkl_hip_pdhmm.h"
 #include "pairhmm_remote.h"
 
 using namespace gklhip_wire;
@@ -48,6 +56,75 @@ std::vector<int32_t> g_used;             // without --devices: device ordinals c
 std::atomic<int64_t> g_calls{0}, g_failed{0}, g_conns_total{0}, g_registered{0}, g_copied{0}, g_refused{0};
 std::atomic<int32_t> g_active{0}, g_live{0};
 int g_stop_pipe[2] = {-1, -1};
+
+// ---- PDHMM: the library (loaded on the first PdHello) and its counters (gklhip_pdhmm_server_info) ----
+struct PdLib {
+  decltype(&gklhip_pdhmm_init) init = nullptr;
+  decltype(&gklhip_pdhmm_set_fma_mode) set_fma_mode = nullptr;
+  decltype(&gklhip_pdhmm_set_tail_mode) set_tail_mode = nullptr;
+  decltype(&gklhip_pdhmm_compute) compute = nullptr;
+  decltype(&gklhip_pdhmm_compute_cross_batched) compute_cross_batched = nullptr;
+  decltype(&gklhip_pdhmm_last_kernel_ms) last_kernel_ms = nullptr;
+  decltype(&gklhip_pdhmm_last_routing) last_routing = nullptr;
+  decltype(&gklhip_pdhmm_done) done = nullptr;
+  decltype(&gklhip_pdhmm_last_error) last_error = nullptr;
+} g_pd;
+std::mutex g_pd_mu;                      // guards the load and g_pd_load_err
+std::atomic<int32_t> g_pd_state{0};      // 0 not yet asked for, 1 loaded, -1 failed
+std::string g_pd_load_err;
+std::vector<int32_t> g_pd_conn_per_entry;   // live PDHMM connections per --devices entry (g_mu)
+std::atomic<int64_t> g_pd_calls{0}, g_pd_failed{0}, g_pd_conns_total{0}, g_pd_pairs{0};
+std::atomic<int32_t> g_pd_active{0}, g_pd_live{0};
+
+// Loads the PDHMM library once; false (and why, naming the file) when it or one of its functions is missing.
+bool pd_load(std::string* err) {
+  std::lock_guard<std::mutex> l(g_pd_mu);
+  if (g_pd_state == 0) {
+    std::string path;
+    if (const char* v = getenv("GKL_HIP_PDHMM_LIB")) path = v;
+    if (path.empty()) {
+      char exe[4096];
+      const ssize_t n = readlink("/proc/self/exe", exe, sizeof exe - 1);
+      path = n > 0 ? std::string(exe, (size_t)n) : std::string();
+      const size_t slash = path.rfind('/');
+      path = (slash == std::string::npos ? std::string() : path.substr(0, slash + 1)) + "libgklhip_pdhmm.so";
+    }
+    void* h = dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL);
+    if (!h) {
+      const char* e = dlerror();
+      g_pd_load_err = "this server cannot serve PDHMM: " + path + " does not load (" + (e ? e : "dlopen failed") + ")";
+    } else {
+      const char* missing = nullptr;
+      auto sym = [&](const char* name) { void* p = dlsym(h, name); if (!p && !missing) missing = name; return p; };
+      g_pd.init = reinterpret_cast<decltype(g_pd.init)>(sym("gklhip_pdhmm_init"));
+      g_pd.set_fma_mode = reinterpret_cast<decltype(g_pd.set_fma_mode)>(sym("gklhip_pdhmm_set_fma_mode"));
+      g_pd.set_tail_mode = reinterpret_cast<decltype(g_pd.set_tail_mode)>(sym("gklhip_pdhmm_set_tail_mode"));
+      g_pd.compute = reinterpret_cast<decltype(g_pd.compute)>(sym("gklhip_pdhmm_compute"));
+      g_pd.compute_cross_batched = reinterpret_cast<decltype(g_pd.compute_cross_batched)>(sym("gklhip_pdhmm_compute_cross_batched"));
+      g_pd.last_kernel_ms = reinterpret_cast<decltype(g_pd.last_kernel_ms)>(sym("gklhip_pdhmm_last_kernel_ms"));
+      g_pd.last_routing = reinterpret_cast<decltype(g_pd.last_routing)>(sym("gklhip_pdhmm_last_routing"));
+      g_pd.done = reinterpret_cast<decltype(g_pd.done)>(sym("gklhip_pdhmm_done"));
+      g_pd.last_error = reinterpret_cast<decltype(g_pd.last_error)>(sym("gklhip_pdhmm_last_error"));
+      if (missing) {
+        g_pd_load_err = "this server cannot serve PDHMM: " + path + " has no " + missing;
+        dlclose(h);
+      }
+    }
+    g_pd_state = g_pd_load_err.empty() ? 1 : -1;
+  }
+  *err = g_pd_load_err;
+  return g_pd_state == 1;
+}
+
+void fill_pd_info(gklhip_pdhmm_server_info* o) {
+  memset(o, 0, sizeof *o);
+  o->protocol = GKLHIP_SERVER_PROTOCOL;
+  o->pid = (int32_t)getpid();
+  o->library_state = g_pd_state;
+  o->calls_served = g_pd_calls; o->calls_failed = g_pd_failed; o->calls_active = g_pd_active;
+  o->live_connections = g_pd_live; o->connections_total = g_pd_conns_total;
+  o->pairs_served = g_pd_pairs;
+}
 
 void on_signal(int) {
   const char b = 1;
@@ -146,6 +223,9 @@ class Session {
   explicit Session(int fd) : fd_(fd) {}
   ~Session() {
     if (ctx_) gklhip_done(ctx_);
+    if (pd_ctx_) (void)g_pd.done(pd_ctx_);
+    if (pd_entry_ >= 0) { std::lock_guard<std::mutex> l(g_mu); g_pd_conn_per_entry[(size_t)pd_entry_]--; }
+    if (pd_counted_) g_pd_live--;
     if (stage_) gklhip_host_free(stage_);
     arena_.release();
     if (entry_ >= 0) { std::lock_guard<std::mutex> l(g_mu); g_conn_per_entry[(size_t)entry_]--; }
@@ -156,7 +236,7 @@ class Session {
     int pfd = -1;
     if (!read_request(fd_, &r, &pfd)) return;
     if (pfd >= 0) close(pfd);
-    if (!hello(r)) return;
+    if (r.magic == kMagic && r.type == kPdHello ? !pd_hello(r) : !hello(r)) return;
     while (read_request(fd_, &r, &pfd)) {
       const int keep_fd = pfd;
       pfd = -1;
@@ -165,6 +245,13 @@ class Session {
         if (keep_fd >= 0) close(keep_fd);
         gklhip_server_info info;
         fill_info(&info);
+        if (!reply(fd_, GKLHIP_OK, "", &info, sizeof info)) return;
+        continue;
+      }
+      if (r.type == kPdStats) {
+        if (keep_fd >= 0) close(keep_fd);
+        gklhip_pdhmm_server_info info;
+        fill_pd_info(&info);
         if (!reply(fd_, GKLHIP_OK, "", &info, sizeof info)) return;
         continue;
       }
@@ -182,8 +269,9 @@ class Session {
         continue;
       }
       if (keep_fd >= 0) close(keep_fd);
-      if (r.type != kCompute) { refuse(GKLHIP_ERR_INVALID_ARG, "unknown request type " + std::to_string(r.type)); return; }
-      if (!compute(r.u.compute)) return;
+      // a connection is of one kind: a PDHMM connection knows no Compute, a PairHMM connection no PdCompute
+      if (r.type != (pd_ ? kPdCompute : kCompute)) { refuse(GKLHIP_ERR_INVALID_ARG, "unknown request type " + std::to_string(r.type)); return; }
+      if (pd_ ? !pd_compute(r.u.pd_compute) : !compute(r.u.compute)) return;
     }
   }
 
@@ -196,6 +284,13 @@ class Session {
   uint8_t* stage_ = nullptr;
   size_t stage_cap_ = 0;
   std::vector<int64_t> read_off_, hap_off_;
+  // a PDHMM connection: its context, the modes that context is in (-1: as the library made it), its private copies of
+  // the two length arrays
+  bool pd_ = false, pd_counted_ = false;
+  int pd_entry_ = -1;
+  gklhip_pdhmm_ctx* pd_ctx_ = nullptr;
+  int pd_fma_ = -1, pd_tail_ = -1;
+  std::vector<int64_t> pd_hap_len_, pd_read_len_;
 
   void refuse(int status, const std::string& why) {
     g_refused++;
@@ -240,10 +335,45 @@ class Session {
     return reply(fd_, GKLHIP_OK, "", &hr, sizeof hr);
   }
 
+  bool pd_hello(const Request& r) {
+    const PdHello& h = r.u.pd_hello;
+    if (h.protocol != GKLHIP_SERVER_PROTOCOL || h.abi_version != GKLHIP_ABI_VERSION) {
+      refuse(GKLHIP_ERR_UNSUPPORTED, "client speaks protocol " + std::to_string(h.protocol) + " / ABI " + std::to_string(h.abi_version) +
+                                         ", this server protocol " + std::to_string(GKLHIP_SERVER_PROTOCOL) + " / ABI " + std::to_string(GKLHIP_ABI_VERSION));
+      return false;
+    }
+    std::string err;
+    if (!pd_load(&err)) { refuse(GKLHIP_ERR_UNSUPPORTED, err); return false; }
+    pd_ = true;
+    int32_t device = std::max(0, h.device);
+    if (!g_devices.empty()) {
+      // the listed device with the fewest connections of both kinds (the first of them on a tie)
+      std::lock_guard<std::mutex> l(g_mu);
+      pd_entry_ = 0;
+      for (size_t i = 1; i < g_devices.size(); i++)
+        if (g_conn_per_entry[i] + g_pd_conn_per_entry[i] < g_conn_per_entry[(size_t)pd_entry_] + g_pd_conn_per_entry[(size_t)pd_entry_]) pd_entry_ = (int)i;
+      g_pd_conn_per_entry[(size_t)pd_entry_]++;
+      device = g_devices[(size_t)pd_entry_];
+    }
+    const int st = g_pd.init(device, &pd_ctx_);
+    if (st != GKLHIP_OK) {
+      const char* e = g_pd.last_error();
+      pd_ctx_ = nullptr;
+      (void)reply(fd_, st, std::string("gklhip_pdhmm_init on the server: ") + (e ? e : ""));
+      return false;
+    }
+    pd_counted_ = true;
+    g_pd_live++;
+    g_pd_conns_total++;
+    return reply(fd_, GKLHIP_OK, "", &device, sizeof device);
+  }
+
   // [off, off + len) inside the arena, 8-byte aligned where `align8`
   bool inside(uint64_t off, uint64_t len, bool align8) const {
     return off <= arena_.bytes && len <= arena_.bytes - off && (!align8 || off % 8 == 0);
   }
+
+  bool pd_compute(const PdCompute& q);
 
   bool compute(const Compute& q) {
     if (!arena_.p) { refuse(GKLHIP_ERR_INVALID_ARG, "call before any arena"); return false; }
@@ -303,6 +433,81 @@ class Session {
     return reply(fd_, st, err, &stats, sizeof stats);
   }
 };
+
+bool Session::pd_compute(const PdCompute& q) {
+  auto bad = [&](const std::string& why) { refuse(GKLHIP_ERR_INVALID_ARG, why); return false; };
+  if (!arena_.p) return bad("call before any arena");
+  if (q.layout != 0 && q.layout != 1) return bad("unknown layout " + std::to_string(q.layout));
+  if (q.n_read_items < 0 || q.n_hap_items < 0) return bad("negative read or haplotype count");
+  if (q.max_hap_len <= 0 || q.max_read_len <= 0) return bad("row strides must be greater than 0");
+  if (q.layout == 0 && q.n_read_items != q.n_hap_items) return bad("the paired layout wants as many reads as haplotypes");
+  const uint64_t nr = (uint64_t)q.n_read_items, nh = (uint64_t)q.n_hap_items;
+  const uint64_t n_pairs = q.layout == 0 ? nr : nr * nh;   // (two counts below 2^31: no overflow)
+  if (n_pairs > 0x7fffffffull) return bad("more than 2^31 - 1 pairs");
+  uint64_t hap_bytes, read_bytes;
+  if (__builtin_mul_overflow(nh, (uint64_t)q.max_hap_len, &hap_bytes) || __builtin_mul_overflow(nr, (uint64_t)q.max_read_len, &read_bytes))
+    return bad("array size overflows");
+  if (!inside(q.hap_lengths, nh * 8, false) || !inside(q.read_lengths, nr * 8, false) || !inside(q.out, n_pairs * 8, true))
+    return bad("length array or output outside the arena");
+  const uint64_t hp[2] = {q.hap_bases, q.hap_pdbases};
+  const uint64_t rd[5] = {q.read_bases, q.read_qual, q.read_ins_qual, q.read_del_qual, q.gcp};
+  for (uint64_t o : hp) if (!inside(o, hap_bytes, false)) return bad("a haplotype array lies outside the arena");
+  for (uint64_t o : rd) if (!inside(o, read_bytes, false)) return bad("a read array lies outside the arena");
+  // the lengths are copied out of the shared pages before they are checked: the client cannot change them under the call
+  pd_hap_len_.resize((size_t)nh);
+  pd_read_len_.resize((size_t)nr);
+  if (nh) memcpy(pd_hap_len_.data(), arena_.p + q.hap_lengths, (size_t)nh * 8);
+  if (nr) memcpy(pd_read_len_.data(), arena_.p + q.read_lengths, (size_t)nr * 8);
+  for (int64_t v : pd_hap_len_) if (v < 1 || v > q.max_hap_len) return bad("a haplotype length outside 1.." + std::to_string(q.max_hap_len));
+  for (int64_t v : pd_read_len_) if (v < 1 || v > q.max_read_len) return bad("a read length outside 1.." + std::to_string(q.max_read_len));
+  const uint8_t* a = arena_.p;
+  const int8_t* arr[7];
+  if (arena_.registered) {
+    for (int i = 0; i < 2; i++) arr[i] = reinterpret_cast<const int8_t*>(a + hp[i]);
+    for (int i = 0; i < 5; i++) arr[2 + i] = reinterpret_cast<const int8_t*>(a + rd[i]);
+  } else {
+    const size_t need = 2 * (size_t)hap_bytes + 5 * (size_t)read_bytes + 1;
+    if (need > stage_cap_) {
+      if (stage_) gklhip_host_free(stage_);
+      stage_cap_ = std::max(need, 2 * stage_cap_);
+      stage_ = static_cast<uint8_t*>(gklhip_host_alloc(stage_cap_));
+      if (!stage_) { stage_cap_ = 0; g_pd_calls++; g_pd_failed++; return reply(fd_, GKLHIP_ERR_OOM, "pinned staging allocation failed"); }
+    }
+    uint8_t* s = stage_;
+    for (int i = 0; i < 2; i++) { memcpy(s, a + hp[i], (size_t)hap_bytes); arr[i] = reinterpret_cast<const int8_t*>(s); s += hap_bytes; }
+    for (int i = 0; i < 5; i++) { memcpy(s, a + rd[i], (size_t)read_bytes); arr[2 + i] = reinterpret_cast<const int8_t*>(s); s += read_bytes; }
+  }
+  double* out = reinterpret_cast<double*>(arena_.p + q.out);
+  g_pd_active++;
+  // fma_mode and tail_mode come with every call; the context is told only when one of them changes
+  const int fma = q.flags & 1, tail = (q.flags >> 1) & 1;
+  int st = GKLHIP_OK;
+  if (fma != pd_fma_ && (st = g_pd.set_fma_mode(pd_ctx_, fma)) == GKLHIP_OK) pd_fma_ = fma;
+  if (st == GKLHIP_OK && tail != pd_tail_ && (st = g_pd.set_tail_mode(pd_ctx_, tail)) == GKLHIP_OK) pd_tail_ = tail;
+  if (st == GKLHIP_OK) {
+    if (q.layout == 0) {
+      const gklhip_pdhmm_batch b = {q.n_read_items, q.max_hap_len, q.max_read_len, arr[0], arr[1], arr[2], arr[3], arr[4], arr[5], arr[6],
+                                    pd_hap_len_.data(), pd_read_len_.data()};
+      st = g_pd.compute(pd_ctx_, &b, out);
+    } else {
+      const gklhip_pdhmm_cross x = {q.n_read_items, q.n_hap_items, q.max_hap_len, q.max_read_len, arr[0], arr[1], arr[2], arr[3], arr[4],
+                                    arr[5], arr[6], pd_hap_len_.data(), pd_read_len_.data()};
+      st = g_pd.compute_cross_batched(pd_ctx_, &x, q.ref_batch_pairs, out);
+    }
+  }
+  // an error of the library goes back with its status and its exact text; the connection stays usable
+  const char* e = st == GKLHIP_OK ? "" : g_pd.last_error();
+  const std::string err = e ? e : "";
+  g_pd_active--;
+  g_pd_calls++;
+  if (st != GKLHIP_OK) g_pd_failed++; else g_pd_pairs += (int64_t)n_pairs;
+  PdComputeReply rep{};
+  if (st == GKLHIP_OK) {
+    rep.kernel_ms = g_pd.last_kernel_ms(pd_ctx_);
+    (void)g_pd.last_routing(pd_ctx_, rep.routing);
+  }
+  return reply(fd_, st, err, &rep, sizeof rep);
+}
 
 void fill_info(gklhip_server_info* o) {
   memset(o, 0, sizeof *o);
@@ -387,6 +592,7 @@ int main(int argc, char** argv) {
   unsetenv("GKL_HIP_SERVER");   // the server's own contexts are local (it must never connect to itself)
   if (const char* v = getenv("GKL_HIP_SERVER_REGISTER")) g_try_register = atoi(v) != 0;
   g_conn_per_entry.assign(g_devices.size(), 0);
+  g_pd_conn_per_entry.assign(g_devices.size(), 0);
   signal(SIGPIPE, SIG_IGN);
   if (pipe2(g_stop_pipe, O_CLOEXEC) != 0) { perror("gklhip_server: pipe"); return 1; }
   struct sigaction sa{};
@@ -436,6 +642,6 @@ int main(int argc, char** argv) {
   unlink(g_socket.c_str());
   for (auto& c : conns) shutdown(c->fd, SHUT_RD);
   for (auto& c : conns) { c->th.join(); close(c->fd); }
-  fprintf(stderr, "gklhip_server: stopped after %lld calls\n", (long long)g_calls.load());
+  fprintf(stderr, "gklhip_server: stopped after %lld calls\n", (long long)(g_calls.load() + g_pd_calls.load()));
   return 0;
 }

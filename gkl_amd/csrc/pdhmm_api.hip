@@ -21,6 +21,7 @@
 #include "../../include/gkl_hip_pairhmm.h"  // status codes
 #include "../../include/gkl_hip_pdhmm.h"
 #include "pdhmm_kernel.h"
+#include "pdhmm_remote.h"
 #include "pairhmm_plan.h"
 #include "pairhmm_host_finalize.h"   // gklhip::WorkerPool: persistent threads for the host log10
 
@@ -134,6 +135,9 @@ struct PinBuf {  // page-locked host memory
 }  // namespace
 
 struct gklhip_pdhmm_ctx {
+  // a client context of the server (gklhip_pdhmm_connect, GKL_HIP_SERVER): no stream, no event, no buffer -- no HIP
+  // call is made for it; fma_mode / tail_mode travel with every call, last_ms / last_routing come back with the reply
+  gklhip_pd_remote::Client* remote = nullptr;
   int device = 0;
   hipStream_t stream = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -168,7 +172,45 @@ int64_t gklhip_pdhmm_get_table(int which, double* dst, int64_t cap) {
   return (int64_t)v->size();
 }
 
+namespace {
+// "reference" (default) | "vector": read by the process that makes the context, a client included
+int pd_tail_mode_from_env() {
+  const char* tm = getenv("GKL_HIP_PDHMM_TAIL");
+  return (tm && (strcmp(tm, "vector") == 0 || strcmp(tm, "0") == 0)) ? 0 : 1;
+}
+}  // namespace
+
+int gklhip_pdhmm_connect(const char* socket_path, int device, gklhip_pdhmm_ctx** out_ctx) {
+  if (!out_ctx) return pd_fail(GKLHIP_ERR_INVALID_ARG, "out_ctx is NULL");
+  *out_ctx = nullptr;
+  gklhip_pdhmm_ctx* c = new (std::nothrow) gklhip_pdhmm_ctx();
+  if (!c) return pd_fail(GKLHIP_ERR_OOM, "context allocation failed");
+  std::string err;
+  int rc;
+  try { rc = gklhip_pd_remote::connect(socket_path, device, &c->remote, &err); }
+  catch (...) { rc = GKLHIP_ERR_OOM; err = "host memory allocation failed"; }
+  if (rc != GKLHIP_OK) { delete c; return pd_fail(rc, "%s", err.c_str()); }
+  c->device = device;
+  c->tail_mode = pd_tail_mode_from_env();
+  *out_ctx = c;
+  return GKLHIP_OK;
+}
+
+int gklhip_pdhmm_is_remote(gklhip_pdhmm_ctx* c) { return c && c->remote ? 1 : 0; }
+
+int gklhip_pdhmm_server_stats(const char* socket_path, gklhip_pdhmm_server_info* out) {
+  if (!out) return pd_fail(GKLHIP_ERR_INVALID_ARG, "NULL argument");
+  std::string err;
+  int rc;
+  try { rc = gklhip_pd_remote::server_stats(socket_path, out, &err); }
+  catch (...) { rc = GKLHIP_ERR_OOM; err = "host memory allocation failed"; }
+  return rc == GKLHIP_OK ? rc : pd_fail(rc, "%s", err.c_str());
+}
+
 int gklhip_pdhmm_init(int device, gklhip_pdhmm_ctx** out_ctx) {
+  // GKL_HIP_SERVER=PATH: every context of the process is a client context of the server on PATH
+  if (const char* path = getenv("GKL_HIP_SERVER"))
+    if (*path) return gklhip_pdhmm_connect(path, device, out_ctx);
   if (!out_ctx) return pd_fail(GKLHIP_ERR_INVALID_ARG, "out_ctx is NULL");
   *out_ctx = nullptr;
   int ndev = 0;
@@ -201,8 +243,7 @@ int gklhip_pdhmm_init(int device, gklhip_pdhmm_ctx** out_ctx) {
       hipMemcpy(c->tables.as<double>() + t.q2err.size(), t.mm.data(), t.mm.size() * 8, hipMemcpyHostToDevice) != hipSuccess)
     return bail(pd_fail(GKLHIP_ERR_HIP, "table upload failed"));
   {
-    const char* tm = getenv("GKL_HIP_PDHMM_TAIL");
-    c->tail_mode = (tm && (strcmp(tm, "vector") == 0 || strcmp(tm, "0") == 0)) ? 0 : 1;  // "reference" (default) | "vector"
+    c->tail_mode = pd_tail_mode_from_env();
     const char* tb = getenv("GKL_HIP_PDHMM_TABLE");
     c->use_table = (tb && tb[0] == '0') ? 0 : 1;
     const char* pl = getenv("GKL_HIP_PDHMM_PIPELINE");
@@ -243,6 +284,11 @@ int gklhip_pdhmm_set_tail_mode(gklhip_pdhmm_ctx* c, int mode) {
 
 int gklhip_pdhmm_done(gklhip_pdhmm_ctx* c) {
   if (!c) return GKLHIP_OK;
+  if (c->remote) {
+    gklhip_pd_remote::close(c->remote);
+    delete c;
+    return GKLHIP_OK;
+  }
   (void)hipSetDevice(c->device);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   if (c->up_stream) (void)hipStreamSynchronize(c->up_stream);
@@ -271,6 +317,7 @@ float gklhip_pdhmm_last_kernel_ms(gklhip_pdhmm_ctx* c) { return c ? c->last_ms :
 int64_t gklhip_pdhmm_buffer_bytes(gklhip_pdhmm_ctx* c) {
   if (!c) return 0;
   std::lock_guard<std::mutex> lock(c->mu);
+  if (c->remote) return (int64_t)gklhip_pd_remote::arena_bytes(c->remote);
   size_t total = 0;
   for (const Buf* b : {&c->tables, &c->inputs, &c->entries, &c->entries_tab, &c->sums, &c->misc, &c->carry, &c->jobs, &c->tabx}) total += b->cap;
   for (const PinBuf* b : {&c->stage_in, &c->stage_jobs, &c->sums_pin}) total += b->cap;
@@ -343,8 +390,26 @@ bool has_odd_base(const int8_t* b, int64_t n) {
 
 // An error return must not leave asynchronous copies from this call's host vectors (or the caller's arrays) in
 // flight when those go out of scope: drain the stream first.
+// A client context: the checked call goes to the server, which answers with its context's kernel time and routing.
+int pd_run_remote(gklhip_pdhmm_ctx* c, const PdProblem& q, double* out_host) {
+  const gklhip_pd_remote::Call call{q.cross_haps ? 1 : 0, q.n_read_items, q.n_hap_items, q.max_hap_len, q.max_read_len,
+                                    (c->fma_mode ? 1 : 0) | (c->tail_mode ? 2 : 0), q.ref_batch_pairs, q.n_pairs,
+                                    q.hap_bases, q.hap_pdbases, q.read_bases, q.read_qual, q.read_ins_qual, q.read_del_qual,
+                                    q.gcp, q.hap_lengths, q.read_lengths};
+  gklhip_wire::PdComputeReply rep{};
+  std::string err;
+  int rc;
+  try { rc = gklhip_pd_remote::compute(c->remote, call, out_host, &rep, &err); }
+  catch (...) { rc = GKLHIP_ERR_OOM; err = "host memory allocation failed"; }
+  if (rc != GKLHIP_OK) return pd_fail(rc, "%s", err.c_str());
+  c->last_ms = rep.kernel_ms;
+  for (int i = 0; i < 3; i++) c->last_routing[i] = rep.routing[i];
+  return GKLHIP_OK;
+}
+
 int pd_run(gklhip_pdhmm_ctx* c, const PdProblem& q, double* out_host) {
   std::lock_guard<std::mutex> lock(c->mu);
+  if (c->remote) return pd_run_remote(c, q, out_host);
   int rc;
   // no C++ exception leaves the C ABI (a host vector that cannot grow, a helper thread that cannot start): it becomes a
   // status like any other error -- after the same drain

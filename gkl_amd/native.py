@@ -421,6 +421,17 @@ class CPdhmmCross(C.Structure):
                 ("gcp", C.c_void_p), ("hap_lengths", C.c_void_p), ("read_lengths", C.c_void_p)]
 
 
+class PdhmmServerInfo(C.Structure):
+    """gklhip_pdhmm_server_info: the server's PDHMM counters (gklhip_pdhmm_server_stats)."""
+    _fields_ = [("protocol", C.c_int32), ("pid", C.c_int32), ("library_state", C.c_int32), ("reserved0", C.c_int32),
+                ("calls_served", C.c_int64), ("calls_failed", C.c_int64), ("calls_active", C.c_int32),
+                ("live_connections", C.c_int32), ("connections_total", C.c_int64), ("pairs_served", C.c_int64),
+                ("reserved", C.c_int64 * 9)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_ if not n.startswith("reserved")}
+
+
 _pd_lib = None
 
 
@@ -463,6 +474,12 @@ def load_pdhmm_library(path: Optional[str] = None):
     lib.gklhip_pdhmm_get_table.argtypes = [C.c_int, C.c_void_p, C.c_int64]
     lib.gklhip_pdhmm_get_table.restype = C.c_int64
     lib.gklhip_pdhmm_last_error.restype = C.c_char_p
+    lib.gklhip_pdhmm_connect.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_void_p)]
+    lib.gklhip_pdhmm_connect.restype = C.c_int
+    lib.gklhip_pdhmm_is_remote.argtypes = [C.c_void_p]
+    lib.gklhip_pdhmm_is_remote.restype = C.c_int
+    lib.gklhip_pdhmm_server_stats.argtypes = [C.c_char_p, C.POINTER(PdhmmServerInfo)]
+    lib.gklhip_pdhmm_server_stats.restype = C.c_int
     if path is None:
         _pd_lib = lib
     return lib
@@ -486,17 +503,43 @@ def pdhmm_available_memory_mb(max_memory_mb: int) -> int:
     return int(load_pdhmm_library().gklhip_pdhmm_available_memory_mb(max_memory_mb))
 
 
+def _raise_pdhmm(lib, status: int):
+    msg = (lib.gklhip_pdhmm_last_error() or b"").decode()
+    if status == ERR_INVALID_ARG:
+        raise IllegalArgumentException(msg)
+    if status == ERR_OOM:
+        raise OutOfMemoryError(msg)
+    raise RuntimeException(msg)
+
+
+def pdhmm_server_stats(socket_path: str) -> dict:
+    """PDHMM counters of the server on `socket_path` (gklhip_pdhmm_server_stats): whether it has loaded its PDHMM
+    library, calls served / failed / active, live PDHMM connections, pairs served.  Makes no HIP call."""
+    lib = load_pdhmm_library()
+    info = PdhmmServerInfo()
+    st = lib.gklhip_pdhmm_server_stats(os.fsencode(socket_path), C.byref(info))
+    if st != OK:
+        _raise_pdhmm(lib, st)
+    return info.as_dict()
+
+
 class PdhmmContext:
     """One gklhip_pdhmm context (= IntelPDHMM.initNative)."""
 
-    def __init__(self, device: int = -1, fma_mode: int = 1, reference_tail: Optional[bool] = None, lib_path: Optional[str] = None):
+    def __init__(self, device: int = -1, fma_mode: int = 1, reference_tail: Optional[bool] = None, lib_path: Optional[str] = None,
+                 server: Optional[str] = None):
         """fma_mode 1: bit-identical to GKL's AVX-512 PDHMM object, 0: to its AVX2 object.  reference_tail: the last
         `batch mod SIMD width` pairs of every reference batch take the scalar engine's arithmetic, as in GKL -- None:
         the library's setting (default: on; GKL_HIP_PDHMM_TAIL=vector turns it off), True / False: set it.
-        lib_path: another build of the library (the all-C++ cross-check build of the tests)."""
+        lib_path: another build of the library (the all-C++ cross-check build of the tests).
+        server: socket path of a running server (gkl_amd.server): a client context, whose calls that server computes
+        (no HIP call in this process).  GKL_HIP_SERVER in the environment makes every context a client context."""
         self.lib = load_pdhmm_library(lib_path)
         h = C.c_void_p()
-        st = self.lib.gklhip_pdhmm_init(device, C.byref(h))
+        if server is not None:
+            st = self.lib.gklhip_pdhmm_connect(os.fsencode(server), device, C.byref(h))
+        else:
+            st = self.lib.gklhip_pdhmm_init(device, C.byref(h))
         if st != OK:
             self._raise(st)
         self.handle = h
@@ -509,12 +552,12 @@ class PdhmmContext:
                 self._raise(st)
 
     def _raise(self, status):
-        msg = (self.lib.gklhip_pdhmm_last_error() or b"").decode()
-        if status == ERR_INVALID_ARG:
-            raise IllegalArgumentException(msg)
-        if status == ERR_OOM:
-            raise OutOfMemoryError(msg)
-        raise RuntimeException(msg)
+        _raise_pdhmm(self.lib, status)
+
+    @property
+    def is_remote(self) -> bool:
+        """True for a client context of the server (server=PATH or GKL_HIP_SERVER)."""
+        return bool(self.lib.gklhip_pdhmm_is_remote(self.handle))
 
     def compute(self, b) -> np.ndarray:
         keep = [np.ascontiguousarray(a, np.int8) for a in (b.hap_bases, b.hap_pdbases, b.read_bases, b.read_qual,

@@ -1,9 +1,9 @@
 """Start and stop the PairHMM server (gkl_amd/lib/gklhip_server).
 
 One server process per node owns the GPU; client processes (``GKL_HIP_SERVER=PATH``, or
-``native.PairHmmContext(server=PATH)``) send it their calls.  ``start`` runs the server as a fresh child process and
-waits for its ``ready`` line; ``stop`` sends SIGTERM (the server finishes the calls in flight, removes the socket and
-exits 0) and SIGKILL after 10 s.
+``native.PairHmmContext(server=PATH)`` / ``native.PdhmmContext(server=PATH)``) send it their calls.  ``start`` runs the
+server as a fresh child process and waits for its ``ready`` line; ``stop`` sends SIGTERM (the server finishes the calls
+in flight, removes the socket and exits 0) and SIGKILL after 10 s.
 """
 from __future__ import annotations
 
@@ -20,7 +20,7 @@ SERVER_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "g
 
 
 class ServerHandle:
-    """A running server: ``socket_path``, ``proc`` (the subprocess.Popen), ``stats()``, ``stop()``."""
+    """A running server: ``socket_path``, ``proc`` (the subprocess.Popen), ``stats()``, ``pdhmm_stats()``, ``stop()``."""
 
     def __init__(self, proc: subprocess.Popen, socket_path: str):
         self.proc = proc
@@ -33,6 +33,11 @@ class ServerHandle:
     def stats(self) -> dict:
         from . import native
         return native.server_stats(self.socket_path)
+
+    def pdhmm_stats(self) -> dict:
+        """The server's PDHMM counters (native.pdhmm_server_stats)."""
+        from . import native
+        return native.pdhmm_server_stats(self.socket_path)
 
     def stop(self, timeout: float = 10.0) -> Optional[int]:
         """SIGTERM, then SIGKILL after `timeout` seconds; returns the exit status."""

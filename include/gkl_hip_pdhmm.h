@@ -59,7 +59,34 @@ typedef struct {
   const int64_t* read_lengths; /* [n_reads] */
 } gklhip_pdhmm_cross;
 
+/* With GKL_HIP_SERVER=PATH (non-empty) in the environment this is gklhip_pdhmm_connect(PATH, device, out_ctx): the
+ * process makes no HIP call. */
 int gklhip_pdhmm_init(int device /* -1 = current */, gklhip_pdhmm_ctx** out_ctx);
+
+/* ---- client mode: the context's calls are computed by the server on socket_path (gkl_amd/lib/gklhip_server,
+ * INTEGRATION.md section 6), which loads libgklhip_pdhmm.so and keeps one context of its own per client context.  The
+ * client process makes no HIP call.  Every function of this header works on a client context: set_fma_mode /
+ * set_tail_mode are kept here and travel with every call (GKL_HIP_PDHMM_TAIL is read by the client at init, as
+ * always), the compute calls check their arguments here first, with the same statuses and messages, last_kernel_ms /
+ * last_routing return what the server's context reported for the call, buffer_bytes is the size of the shared-memory
+ * arena.  GKL_HIP_PDHMM_TABLE and GKL_HIP_PDHMM_PIPELINE belong to the process that computes: the server.
+ * device: -1 = the server's choice (its --devices list, else its current device). */
+int gklhip_pdhmm_connect(const char* socket_path, int device, gklhip_pdhmm_ctx** out_ctx);
+int gklhip_pdhmm_is_remote(gklhip_pdhmm_ctx* ctx);
+/* The server's PDHMM counters (its PairHMM ones: gklhip_server_stats of gkl_hip_pairhmm.h).  Fixed size. */
+typedef struct {
+  int32_t protocol, pid;
+  int32_t library_state;     /* 0: no client has asked for PDHMM yet, 1: libgklhip_pdhmm.so loaded, -1: loading failed */
+  int32_t reserved0;
+  int64_t calls_served, calls_failed;
+  int32_t calls_active;
+  int32_t live_connections;  /* PDHMM connections = PDHMM contexts the server holds */
+  int64_t connections_total;
+  int64_t pairs_served;      /* pairs of the calls that succeeded */
+  int64_t reserved[9];
+} gklhip_pdhmm_server_info;
+int gklhip_pdhmm_server_stats(const char* socket_path, gklhip_pdhmm_server_info* out);
+
 /* 1 (default) = bit-identical to GKL's AVX-512 PDHMM object (avx512_impl.cc: a*b + c*d contracted to
  * fma(c, d, a*b)); 0 = bit-identical to its AVX2 object (avx2_impl.cc: no FMA).  Same switch as
  * gklhip_config.fma_mode of the PairHMM. */
