@@ -68,6 +68,7 @@ struct PdLib {
   decltype(&gklhip_pdhmm_last_routing) last_routing = nullptr;
   decltype(&gklhip_pdhmm_done) done = nullptr;
   decltype(&gklhip_pdhmm_last_error) last_error = nullptr;
+  decltype(&gklhip_pdhmm_combine_counts) combine_counts = nullptr;   // (optional: reported when the library has it)
 } g_pd;
 std::mutex g_pd_mu;                      // guards the load and g_pd_load_err
 std::atomic<int32_t> g_pd_state{0};      // 0 not yet asked for, 1 loaded, -1 failed
@@ -105,7 +106,9 @@ bool pd_load(std::string* err) {
       g_pd.last_routing = reinterpret_cast<decltype(g_pd.last_routing)>(sym("gklhip_pdhmm_last_routing"));
       g_pd.done = reinterpret_cast<decltype(g_pd.done)>(sym("gklhip_pdhmm_done"));
       g_pd.last_error = reinterpret_cast<decltype(g_pd.last_error)>(sym("gklhip_pdhmm_last_error"));
+      g_pd.combine_counts = reinterpret_cast<decltype(g_pd.combine_counts)>(dlsym(h, "gklhip_pdhmm_combine_counts"));
       if (missing) {
+        g_pd.combine_counts = nullptr;
         g_pd_load_err = "this server cannot serve PDHMM: " + path + " has no " + missing;
         dlclose(h);
       }
@@ -124,6 +127,7 @@ void fill_pd_info(gklhip_pdhmm_server_info* o) {
   o->calls_served = g_pd_calls; o->calls_failed = g_pd_failed; o->calls_active = g_pd_active;
   o->live_connections = g_pd_live; o->connections_total = g_pd_conns_total;
   o->pairs_served = g_pd_pairs;
+  if (g_pd_state == 1 && g_pd.combine_counts) (void)g_pd.combine_counts(-1, o->combine_counts, 0);
 }
 
 void on_signal(int) {

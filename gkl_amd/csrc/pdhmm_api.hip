@@ -16,6 +16,8 @@
 #include <string>
 #include <thread>
 #include <chrono>
+#include <condition_variable>
+#include <functional>
 #include <vector>
 
 #include "../../include/gkl_hip_pairhmm.h"  // status codes
@@ -428,10 +430,167 @@ int pd_run(gklhip_pdhmm_ctx* c, const PdProblem& q, double* out_host) {
 }
 
 constexpr size_t kPdStageBytes = (size_t)4 << 20;
+// misc: 64 int32 of flags and job counters (the first 256 bytes, cleared by every call), then the per-region input-error
+// flags of a multi-region call
+constexpr size_t kPdMiscBytes = 256 + 4 * (size_t)kPdMaxRegions;
+constexpr size_t kPdMultiMaxPairs = 131072;   // a multi-region call's sums go straight into pinned memory (sums_direct)
 // Cross layout: reads are packed into 64-lane chunks by best fit within windows of this many reads.  The chunks are reused
 // for every haplotype, so a fuller chunk pays off nh times: 2048 fills 99.2 % of the lanes on the reference's fixture
 // (192, the paired layout's window: 97.7 %).
 constexpr int kPdCrossWindow = 2048;
+// The cross layout's plan of ONE region call (one computeLikelihoods cross product): the packing of its reads, the
+// order and routing of its haplotypes, its striped reads and its tail pairs -- everything in the call's own indices.
+// pd_run_locked launches one plan; pd_run_multi_locked (below) concatenates several.
+struct PdCrossPlan {
+  std::vector<int32_t> job_pair, job_steps;    // listed jobs: one per (read that needs more than 64 lanes, haplotype)
+  std::vector<uint8_t> job_striped;
+  std::vector<PlanLane> cross_lanes;           // [chunk][64] = {read item, block}
+  std::vector<int32_t> hap_order, chunk_steps, chunk_rep;
+  size_t n_tail = 0;
+  std::vector<PlanLane> tail_lanes;
+  std::vector<int32_t> tail_pair, tail_steps;
+  std::vector<uint8_t> tail_striped;
+  std::vector<uint8_t> hap_ncls;
+  std::vector<uint32_t> class_codes;
+  size_t n_clean_haps = 0, n_tab_haps = 0;
+};
+
+void pd_plan_cross_jobs(gklhip_pdhmm_ctx* c, const PdProblem& q, PdCrossPlan* plan) {
+  const size_t n = (size_t)q.n_pairs, nh = (size_t)q.n_hap_items, nr = (size_t)q.n_read_items;
+  const int cross = q.cross_haps;
+  auto read_len_of = [&](size_t p) { return (int)q.read_lengths[p / (size_t)cross]; };
+  auto hap_len_of = [&](size_t p) { return (int)q.hap_lengths[p % (size_t)cross]; };
+  auto &job_pair = plan->job_pair, &job_steps = plan->job_steps, &hap_order = plan->hap_order, &chunk_steps = plan->chunk_steps,
+       &chunk_rep = plan->chunk_rep, &tail_pair = plan->tail_pair, &tail_steps = plan->tail_steps;
+  auto &job_striped = plan->job_striped, &tail_striped = plan->tail_striped;
+  auto &cross_lanes = plan->cross_lanes, &tail_lanes = plan->tail_lanes;
+  size_t& n_tail = plan->n_tail;
+  // reads are packed into 64-lane chunks ONCE; every chunk meets every haplotype (longest haplotypes first).
+  std::vector<int64_t> read_off(nr + 1, 0);
+  for (size_t r = 0; r < nr; r++) read_off[r + 1] = read_off[r] + q.read_lengths[r];
+  std::vector<int32_t> shorts;
+  shorts.reserve(nr);
+  for (size_t r = 0; r < nr; r++) {
+    if (blocks_for((int)q.read_lengths[r], kPdRpl) <= kLanes) { shorts.push_back((int32_t)r); continue; }
+    for (size_t h = 0; h < nh; h++) {  // a read that needs more than 64 lanes (64 x kPdRpl = 384 bases or more): one striped job per haplotype
+      job_pair.push_back((int32_t)(r * nh + h)); job_striped.push_back(1); job_steps.push_back(0);
+    }
+  }
+  const int made = pack_reads_windowed(shorts.data(), (int)shorts.size(), read_off.data(), kPdRpl, kPdCrossWindow, &cross_lanes, nullptr);
+  chunk_steps.assign((size_t)made, 0);
+  chunk_rep.assign((size_t)made, 0);
+  for (int k = 0; k < made; k++) {
+    const PlanLane* row = cross_lanes.data() + (size_t)k * kLanes;
+    int32_t rep = -1, top = 0;
+    for (int l = 0; l < kLanes; l++) {
+      if (row[l].read < 0) continue;
+      if (rep < 0) rep = row[l].read;
+      top = std::max(top, row[l].block);
+    }
+    chunk_steps[(size_t)k] = top;
+    chunk_rep[(size_t)k] = rep;
+  }
+  hap_order.resize(nh);
+  for (size_t h = 0; h < nh; h++) hap_order[h] = (int32_t)h;
+  std::stable_sort(hap_order.begin(), hap_order.end(),
+                   [&](int32_t x, int32_t y) { return q.hap_lengths[x] > q.hap_lengths[y]; });
+  // "Reference tail" of the cross product: computeLikelihoods expands it into read-major pairs, batch by batch
+  // (JavaData.h:177-242), and computePDHMM finishes the last `batch mod SIMD width` pairs of EVERY batch with the
+  // scalar engine (pdhmm.h:1264-1268).  The main launch computes all pairs with the vector arithmetic; the pairs at
+  // those positions are then recomputed by the scalar-arithmetic instantiation and overwrite their sums.
+  if (c->tail_mode == 1) {
+    const size_t width = c->fma_mode ? 8 : 4;
+    const size_t per = q.ref_batch_pairs > 0 ? (size_t)std::min<int64_t>(q.ref_batch_pairs, (int64_t)n) : n;
+    for (size_t start = 0; start < n; start += per) {
+      const size_t nb_pairs = std::min(per, n - start);
+      for (size_t i = start + nb_pairs / width * width; i < start + nb_pairs; i++) {
+        const int nb = blocks_for(read_len_of(i), kPdRpl);
+        tail_pair.push_back((int32_t)i);
+        tail_striped.push_back(nb > kLanes ? 1 : 0);
+        tail_steps.push_back(hap_len_of(i) + std::min(nb, kLanes) - 1);
+        tail_lanes.resize(tail_lanes.size() + kLanes, PlanLane{-1, 0});
+        if (nb <= kLanes)
+          for (int b = 0; b < nb; b++) tail_lanes[tail_lanes.size() - kLanes + (size_t)b] = PlanLane{(int32_t)i, b};
+      }
+    }
+    n_tail = tail_pair.size();
+  }
+}
+
+void pd_plan_cross_routing(gklhip_pdhmm_ctx* c, const PdProblem& q, PdCrossPlan* plan) {
+  const size_t nh = (size_t)q.n_hap_items;
+  const int cross = q.cross_haps;
+  auto& hap_order = plan->hap_order;
+  auto& hap_ncls = plan->hap_ncls;
+  auto& class_codes = plan->class_codes;
+  size_t &n_clean_haps = plan->n_clean_haps, &n_tab_haps = plan->n_tab_haps;
+  std::vector<uint8_t> hap_odd;
+  if (cross) {
+    hap_odd.assign(nh, 0);
+    for (size_t h = 0; h < nh; h++) hap_odd[h] = has_odd_base(q.hap_bases + h * (size_t)q.max_hap_len, q.hap_lengths[h]) ? 1 : 0;
+  }
+  n_clean_haps = nh; n_tab_haps = 0;
+  // cross layout: a clean haplotype whose columns fall into at most kPdTabClasses classes of (base, SNP alleles, 'N')
+  // goes to the table kernel (pdhmm_fwd_tab_kernel); class c of haplotype h has the match bits class_codes[8 h + c]
+  if (cross) {
+    hap_ncls.assign(nh, 0);
+    class_codes.assign(nh * 8, 0u);
+    for (size_t h = 0; h < nh && c->use_table; h++) {
+      if (hap_odd[h]) continue;
+      const int8_t* hb = q.hap_bases + h * (size_t)q.max_hap_len;
+      const int8_t* pd = q.hap_pdbases + h * (size_t)q.max_hap_len;
+      uint32_t* codes = class_codes.data() + h * 8;
+      int ncls = 0;
+      // (a column's class is a function of its (base, flags) pair: 2^15 of them, a haplotype shows a handful -- a stamp
+      //  per pair and haplotype skips the columns whose pair has been seen; this loop was 0.06 of a region call's 0.33 ms)
+      if (c->class_stamp.empty()) c->class_stamp.assign(1u << 15, 0u);
+      if (++c->class_stamp_id == 0u) { std::fill(c->class_stamp.begin(), c->class_stamp.end(), 0u); c->class_stamp_id = 1u; }
+      const uint32_t stamp_id = c->class_stamp_id;
+      uint32_t* const stamp = c->class_stamp.data();
+      for (int64_t j = 0; j < q.hap_lengths[h] && ncls <= kPdTabClasses; j++) {
+        // (as pdhmm_entries_kernel builds the entry's match bits)
+        const uint32_t yb = (uint32_t)hb[j] & 0xffu, flags = (uint32_t)pd[j] & 0x7fu;
+        uint32_t& seen = stamp[(yb << 7) | flags];
+        if (seen == stamp_id) continue;
+        seen = stamp_id;
+        const uint32_t hot = yb == (uint32_t)'A' ? 1u : yb == (uint32_t)'C' ? 2u : yb == (uint32_t)'G' ? 4u : yb == (uint32_t)'T' ? 8u : 0u;
+        const uint32_t allele = (flags & kPdSnp) ? ((flags >> 3) & 0xfu) : 0u;
+        const uint32_t code = (hot << 20) | (allele << 24) | (1u << 28) | (yb == (uint32_t)'N' ? 1u << 29 : 0u);
+        int k = 0;
+        while (k < ncls && codes[k] != code) k++;
+        if (k == ncls) {
+          if (ncls < kPdTabClasses) codes[ncls] = code;
+          ncls++;
+        }
+      }
+      hap_ncls[h] = ncls <= kPdTabClasses ? (uint8_t)ncls : 0;
+    }
+    // order: table haplotypes, then the other clean ones, then those with odd bases (each group longest first)
+    std::stable_partition(hap_order.begin(), hap_order.end(), [&](int32_t h) { return hap_odd[(size_t)h] == 0; });
+    n_clean_haps = 0;
+    for (size_t h = 0; h < nh; h++) n_clean_haps += hap_odd[h] == 0;
+    std::stable_partition(hap_order.begin(), hap_order.begin() + (ptrdiff_t)n_clean_haps, [&](int32_t h) { return hap_ncls[(size_t)h] != 0; });
+    for (size_t h = 0; h < nh; h++) n_tab_haps += hap_ncls[h] != 0;
+    // The haplotypes of one region share their variant sites, hence their column classes: when the union of the table
+    // haplotypes' classes still fits the table, every one of them gets the union as its list -- a wavefront that takes
+    // several haplotypes with the same chunk of reads (tab_group_start below) then builds the table once.
+    {
+      uint32_t uni[kPdTabClasses + 1];
+      int n_uni = 0;
+      for (size_t h = 0; h < nh && n_uni <= kPdTabClasses; h++)
+        for (int k = 0; k < (int)hap_ncls[h] && n_uni <= kPdTabClasses; k++) {
+          const uint32_t code = class_codes[h * 8 + (size_t)k];
+          int at = 0;
+          while (at < n_uni && uni[at] != code) at++;
+          if (at == n_uni) { if (n_uni < kPdTabClasses) uni[n_uni] = code; n_uni++; }
+        }
+      if (n_uni <= kPdTabClasses)
+        for (size_t h = 0; h < nh; h++)
+          if (hap_ncls[h]) { for (int k = 0; k < n_uni; k++) class_codes[h * 8 + (size_t)k] = uni[k]; hap_ncls[h] = (uint8_t)n_uni; }
+    }
+  }
+}
+
 int pd_run_locked(gklhip_pdhmm_ctx* c, const PdProblem& q, double* out_host) {
   static const bool timing = getenv("GKLHIP_TIMING") != nullptr;
   const auto t_begin = std::chrono::steady_clock::now();
@@ -520,66 +679,16 @@ int pd_run_locked(gklhip_pdhmm_ctx* c, const PdProblem& q, double* out_host) {
   std::vector<int32_t> place_chunk;            // paired layout: compact packing of the pairs (pack_reads_place)
   std::vector<uint8_t> place_lane, chunk_used;
   size_t n_striped = 0;
-  std::vector<int32_t> job_pair, job_steps;
-  std::vector<uint8_t> job_striped;
-  std::vector<PlanLane> cross_lanes;           // cross layout: [chunk][64] = {read item, block}
-  std::vector<int32_t> hap_order, chunk_steps, chunk_rep;
+  PdCrossPlan plan;                            // (cross layout: filled by pd_plan_cross_jobs / _routing; paired layout: its listed and tail jobs)
+  auto &job_pair = plan.job_pair, &job_steps = plan.job_steps, &hap_order = plan.hap_order, &chunk_steps = plan.chunk_steps,
+       &chunk_rep = plan.chunk_rep, &tail_pair = plan.tail_pair, &tail_steps = plan.tail_steps;
+  auto &job_striped = plan.job_striped, &tail_striped = plan.tail_striped, &hap_ncls = plan.hap_ncls;
+  auto &cross_lanes = plan.cross_lanes, &tail_lanes = plan.tail_lanes;
+  auto& class_codes = plan.class_codes;
   int32_t slice_chunk0[gklhip_pdhmm_ctx::kMaxSlices + 1] = {0, 0};   // paired layout: slice k = chunks [slice_chunk0[k], slice_chunk0[k + 1]) = listed jobs n_striped + those
-  size_t n_tail = 0;                           // paired layout, tail mode: the last n_tail pairs
-  std::vector<PlanLane> tail_lanes;
-  std::vector<int32_t> tail_pair, tail_steps;
-  std::vector<uint8_t> tail_striped;
+  size_t& n_tail = plan.n_tail;                // paired layout, tail mode: the last n_tail pairs
   if (cross) {
-    // reads are packed into 64-lane chunks ONCE; every chunk meets every haplotype (longest haplotypes first).
-    std::vector<int64_t> read_off(nr + 1, 0);
-    for (size_t r = 0; r < nr; r++) read_off[r + 1] = read_off[r] + q.read_lengths[r];
-    std::vector<int32_t> shorts;
-    shorts.reserve(nr);
-    for (size_t r = 0; r < nr; r++) {
-      if (blocks_for((int)q.read_lengths[r], kPdRpl) <= kLanes) { shorts.push_back((int32_t)r); continue; }
-      for (size_t h = 0; h < nh; h++) {  // a read that needs more than 64 lanes (64 x kPdRpl = 384 bases or more): one striped job per haplotype
-        job_pair.push_back((int32_t)(r * nh + h)); job_striped.push_back(1); job_steps.push_back(0);
-      }
-    }
-    const int made = pack_reads_windowed(shorts.data(), (int)shorts.size(), read_off.data(), kPdRpl, kPdCrossWindow, &cross_lanes, nullptr);
-    chunk_steps.assign((size_t)made, 0);
-    chunk_rep.assign((size_t)made, 0);
-    for (int k = 0; k < made; k++) {
-      const PlanLane* row = cross_lanes.data() + (size_t)k * kLanes;
-      int32_t rep = -1, top = 0;
-      for (int l = 0; l < kLanes; l++) {
-        if (row[l].read < 0) continue;
-        if (rep < 0) rep = row[l].read;
-        top = std::max(top, row[l].block);
-      }
-      chunk_steps[(size_t)k] = top;
-      chunk_rep[(size_t)k] = rep;
-    }
-    hap_order.resize(nh);
-    for (size_t h = 0; h < nh; h++) hap_order[h] = (int32_t)h;
-    std::stable_sort(hap_order.begin(), hap_order.end(),
-                     [&](int32_t x, int32_t y) { return q.hap_lengths[x] > q.hap_lengths[y]; });
-    // "Reference tail" of the cross product: computeLikelihoods expands it into read-major pairs, batch by batch
-    // (JavaData.h:177-242), and computePDHMM finishes the last `batch mod SIMD width` pairs of EVERY batch with the
-    // scalar engine (pdhmm.h:1264-1268).  The main launch computes all pairs with the vector arithmetic; the pairs at
-    // those positions are then recomputed by the scalar-arithmetic instantiation and overwrite their sums.
-    if (c->tail_mode == 1) {
-      const size_t width = c->fma_mode ? 8 : 4;
-      const size_t per = q.ref_batch_pairs > 0 ? (size_t)std::min<int64_t>(q.ref_batch_pairs, (int64_t)n) : n;
-      for (size_t start = 0; start < n; start += per) {
-        const size_t nb_pairs = std::min(per, n - start);
-        for (size_t i = start + nb_pairs / width * width; i < start + nb_pairs; i++) {
-          const int nb = blocks_for(read_len_of(i), kPdRpl);
-          tail_pair.push_back((int32_t)i);
-          tail_striped.push_back(nb > kLanes ? 1 : 0);
-          tail_steps.push_back(hap_len_of(i) + std::min(nb, kLanes) - 1);
-          tail_lanes.resize(tail_lanes.size() + kLanes, PlanLane{-1, 0});
-          if (nb <= kLanes)
-            for (int b = 0; b < nb; b++) tail_lanes[tail_lanes.size() - kLanes + (size_t)b] = PlanLane{(int32_t)i, b};
-        }
-      }
-      n_tail = tail_pair.size();
-    }
+    pd_plan_cross_jobs(c, q, &plan);
   } else {
     // "Reference tail": GKL finishes the last `batch mod SIMD width` pairs of every vector batch with its SCALAR
     // engine (pdhmm.h:1264-1270; 8 doubles per AVX-512 vector, 4 per AVX2 vector), whose arithmetic differs in the
@@ -644,72 +753,9 @@ int pd_run_locked(gklhip_pdhmm_ctx* c, const PdProblem& q, double* out_host) {
   // the rest -- rare -- go to a second launch of the full kernel.  Cross layout: the host looks at the (few)
   // haplotypes and orders them by kernel.  Listed jobs (paired layout: every job): routed on the device
   // (PdArgs::job_flags) -- a host scan of a haplotype per PAIR is ~100 MB for 400k pairs.
-  std::vector<uint8_t> hap_odd;
+  if (cross) pd_plan_cross_routing(c, q, &plan);
+  const size_t n_clean_haps = cross ? plan.n_clean_haps : nh, n_tab_haps = plan.n_tab_haps;
   if (cross) {
-    hap_odd.assign(nh, 0);
-    for (size_t h = 0; h < nh; h++) hap_odd[h] = has_odd_base(q.hap_bases + h * (size_t)q.max_hap_len, q.hap_lengths[h]) ? 1 : 0;
-  }
-  size_t n_clean_haps = nh, n_tab_haps = 0;
-  // cross layout: a clean haplotype whose columns fall into at most kPdTabClasses classes of (base, SNP alleles, 'N')
-  // goes to the table kernel (pdhmm_fwd_tab_kernel); class c of haplotype h has the match bits class_codes[8 h + c]
-  std::vector<uint8_t> hap_ncls;
-  std::vector<uint32_t> class_codes;
-  if (cross) {
-    hap_ncls.assign(nh, 0);
-    class_codes.assign(nh * 8, 0u);
-    for (size_t h = 0; h < nh && c->use_table; h++) {
-      if (hap_odd[h]) continue;
-      const int8_t* hb = q.hap_bases + h * (size_t)q.max_hap_len;
-      const int8_t* pd = q.hap_pdbases + h * (size_t)q.max_hap_len;
-      uint32_t* codes = class_codes.data() + h * 8;
-      int ncls = 0;
-      // (a column's class is a function of its (base, flags) pair: 2^15 of them, a haplotype shows a handful -- a stamp
-      //  per pair and haplotype skips the columns whose pair has been seen; this loop was 0.06 of a region call's 0.33 ms)
-      if (c->class_stamp.empty()) c->class_stamp.assign(1u << 15, 0u);
-      if (++c->class_stamp_id == 0u) { std::fill(c->class_stamp.begin(), c->class_stamp.end(), 0u); c->class_stamp_id = 1u; }
-      const uint32_t stamp_id = c->class_stamp_id;
-      uint32_t* const stamp = c->class_stamp.data();
-      for (int64_t j = 0; j < q.hap_lengths[h] && ncls <= kPdTabClasses; j++) {
-        // (as pdhmm_entries_kernel builds the entry's match bits)
-        const uint32_t yb = (uint32_t)hb[j] & 0xffu, flags = (uint32_t)pd[j] & 0x7fu;
-        uint32_t& seen = stamp[(yb << 7) | flags];
-        if (seen == stamp_id) continue;
-        seen = stamp_id;
-        const uint32_t hot = yb == (uint32_t)'A' ? 1u : yb == (uint32_t)'C' ? 2u : yb == (uint32_t)'G' ? 4u : yb == (uint32_t)'T' ? 8u : 0u;
-        const uint32_t allele = (flags & kPdSnp) ? ((flags >> 3) & 0xfu) : 0u;
-        const uint32_t code = (hot << 20) | (allele << 24) | (1u << 28) | (yb == (uint32_t)'N' ? 1u << 29 : 0u);
-        int k = 0;
-        while (k < ncls && codes[k] != code) k++;
-        if (k == ncls) {
-          if (ncls < kPdTabClasses) codes[ncls] = code;
-          ncls++;
-        }
-      }
-      hap_ncls[h] = ncls <= kPdTabClasses ? (uint8_t)ncls : 0;
-    }
-    // order: table haplotypes, then the other clean ones, then those with odd bases (each group longest first)
-    std::stable_partition(hap_order.begin(), hap_order.end(), [&](int32_t h) { return hap_odd[(size_t)h] == 0; });
-    n_clean_haps = 0;
-    for (size_t h = 0; h < nh; h++) n_clean_haps += hap_odd[h] == 0;
-    std::stable_partition(hap_order.begin(), hap_order.begin() + (ptrdiff_t)n_clean_haps, [&](int32_t h) { return hap_ncls[(size_t)h] != 0; });
-    for (size_t h = 0; h < nh; h++) n_tab_haps += hap_ncls[h] != 0;
-    // The haplotypes of one region share their variant sites, hence their column classes: when the union of the table
-    // haplotypes' classes still fits the table, every one of them gets the union as its list -- a wavefront that takes
-    // several haplotypes with the same chunk of reads (tab_group_start below) then builds the table once.
-    {
-      uint32_t uni[kPdTabClasses + 1];
-      int n_uni = 0;
-      for (size_t h = 0; h < nh && n_uni <= kPdTabClasses; h++)
-        for (int k = 0; k < (int)hap_ncls[h] && n_uni <= kPdTabClasses; k++) {
-          const uint32_t code = class_codes[h * 8 + (size_t)k];
-          int at = 0;
-          while (at < n_uni && uni[at] != code) at++;
-          if (at == n_uni) { if (n_uni < kPdTabClasses) uni[n_uni] = code; n_uni++; }
-        }
-      if (n_uni <= kPdTabClasses)
-        for (size_t h = 0; h < nh; h++)
-          if (hap_ncls[h]) { for (int k = 0; k < n_uni; k++) class_codes[h * 8 + (size_t)k] = uni[k]; hap_ncls[h] = (uint8_t)n_uni; }
-    }
     c->last_routing[0] = (int32_t)n_tab_haps; c->last_routing[1] = (int32_t)(n_clean_haps - n_tab_haps); c->last_routing[2] = (int32_t)(nh - n_clean_haps);
   } else {
     c->last_routing[0] = c->last_routing[1] = c->last_routing[2] = 0;
@@ -755,7 +801,7 @@ int pd_run_locked(gklhip_pdhmm_ctx* c, const PdProblem& q, double* out_host) {
   if (n_tab_haps && (rc = c->entries_tab.reserve(2 * nh * (size_t)entry_stride * 4))) return rc;   // + the next-special-column table
   if (tab_paired && ((rc = c->entries_tab.reserve(nh * (size_t)entry_stride * 4)) || (rc = c->tabx.reserve(x_total)))) return rc;
   if ((rc = c->sums.reserve(n * 8))) return rc;
-  if ((rc = c->misc.reserve(256))) return rc;
+  if ((rc = c->misc.reserve(kPdMiscBytes))) return rc;
   if ((rc = c->carry.reserve((size_t)n_blocks * 2 * (6 * (size_t)carry_len + 64) * 8))) return rc;
   const size_t o_jl = 0, o_jp = up((size_t)n_general * kLanes * sizeof(PlanLane)), o_jn = o_jp + up((size_t)n_general * 4),
                o_js = o_jn + up((size_t)n_general * 4), o_cl = o_js + up((size_t)n_general),
@@ -881,6 +927,7 @@ int pd_run_locked(gklhip_pdhmm_ctx* c, const PdProblem& q, double* out_host) {
 #endif
 
   a.item_base = 0; a.job_base = 0;
+  a.regions = nullptr; a.n_regions = 0; a.multi_launch = 0;
   const bool paired_packed = !cross && !chunk_used.empty();
   if (!paired_packed && n_slices > 1) {
     // A sliced call without one packed chunk (every read striped): nothing below waits slice by slice, and the helper
@@ -1062,6 +1109,461 @@ int pd_run_locked(gklhip_pdhmm_ctx* c, const PdProblem& q, double* out_host) {
   }
   return GKLHIP_OK;
 }
+
+// ---- several region calls in one set of launches (gklhip_pdhmm_compute_cross_multi) ----
+struct PdMultiRegion {
+  PdProblem q;
+  double* out;
+  int32_t flag = 0;                     // out: the region's input-error flag (PDHMM_INPUT_DATA_ERROR)
+  int32_t routing[3] = {0, 0, 0};       // out: its haplotypes by kernel
+};
+
+// Bytes of the regions' inputs in the layout of a multi-region call: one common row stride per side.
+size_t pd_input_bytes(size_t nh, size_t nr, size_t mh, size_t mr) {
+  auto up = [](size_t x) { return (x + 255) / 256 * 256; };
+  return 2 * up(nh * mh) + 5 * up(nr * mr) + up(nh * 8) + up(nr * 8);
+}
+size_t pd_multi_input_bytes(const std::vector<PdMultiRegion>& R) {
+  size_t nh = 0, nr = 0, mh = 0, mr = 0;
+  for (const PdMultiRegion& r : R) {
+    nh += (size_t)r.q.n_hap_items; nr += (size_t)r.q.n_read_items;
+    mh = std::max(mh, (size_t)r.q.max_hap_len); mr = std::max(mr, (size_t)r.q.max_read_len);
+  }
+  return pd_input_bytes(nh, nr, mh, mr);
+}
+
+// The regions of R (all valid, same context settings; at most kPdMaxRegions, kPdMultiMaxPairs pairs, kPdStageBytes of
+// inputs) as ONE problem: planned region by region exactly as pd_run_locked plans a single call, then concatenated -- one
+// pinned block and one copy for the inputs, one for the job tables, one pdhmm_entries_kernel, at most one launch each of the
+// table, predicate and full kernels and one tail launch, the sums straight into pinned memory, one host finalisation.
+// The return value is the status of the launch set (a HIP failure fails every region); R[k].flag != 0: region k had a
+// negative quality (PDHMM_INPUT_DATA_ERROR), its output is not written.
+int pd_run_multi_locked(gklhip_pdhmm_ctx* c, std::vector<PdMultiRegion>& R) {
+  PD_HIP_TRY(hipSetDevice(c->device));
+  hipStream_t s = c->stream;
+  const int K = (int)R.size();
+  std::vector<PdCrossPlan> plans((size_t)K);
+  std::vector<PdRegionShape> shapes((size_t)K);
+  size_t NH = 0, NR = 0, NP = 0, mh = 0, mr = 0;
+  size_t n_tab_haps = 0, n_hot_haps = 0, n_full_haps = 0, n_chunks = 0, n_general = 0, n_tail = 0;
+  int64_t n_cross_tab = 0;   // (haplotype, chunk) jobs of the table launch
+  for (int k = 0; k < K; k++) {
+    const PdProblem& q = R[(size_t)k].q;
+    pd_plan_cross_jobs(c, q, &plans[(size_t)k]);
+    pd_plan_cross_routing(c, q, &plans[(size_t)k]);
+    const PdCrossPlan& pl = plans[(size_t)k];
+    NH += (size_t)q.n_hap_items; NR += (size_t)q.n_read_items; NP += (size_t)q.n_pairs;
+    mh = std::max(mh, (size_t)q.max_hap_len); mr = std::max(mr, (size_t)q.max_read_len);
+    n_tab_haps += pl.n_tab_haps; n_hot_haps += pl.n_clean_haps - pl.n_tab_haps; n_full_haps += (size_t)q.n_hap_items - pl.n_clean_haps;
+    n_chunks += pl.chunk_steps.size(); n_general += pl.job_pair.size(); n_tail += pl.n_tail;
+    n_cross_tab += (int64_t)pl.chunk_steps.size() * (int64_t)pl.n_tab_haps;
+  }
+  // Table launch: groups of consecutive table haplotypes of ONE region (see pd_run_locked), sized by the units of the
+  // whole launch -- many small regions together fill the device, so they get the full groups a single one would not --
+  // and shrinking to single haplotypes over the last part of the launch's list.
+  std::vector<int32_t> tab_group_start;
+  {
+    const int64_t per_wave = n_cross_tab / (256 * 8);
+    const size_t group_max = (size_t)std::max<int64_t>(1, std::min<int64_t>(6, per_wave / 6));
+    size_t left = n_tab_haps, at = 0;
+    for (int k = 0; k < K; k++) {
+      const size_t mine = plans[(size_t)k].n_tab_haps;
+      int32_t groups = 0;
+      for (size_t i = 0; i < mine; groups++) {
+        const size_t g = std::max<size_t>(1, std::min(std::min(group_max, left / 7), mine - i));
+        tab_group_start.push_back((int32_t)(at + i));
+        i += g; left -= g;
+      }
+      at += mine;
+      shapes[(size_t)k] = PdRegionShape{R[(size_t)k].q.n_read_items, R[(size_t)k].q.n_hap_items, (int32_t)plans[(size_t)k].chunk_steps.size(),
+                                        {groups, (int32_t)(plans[(size_t)k].n_clean_haps - mine),
+                                         (int32_t)((size_t)R[(size_t)k].q.n_hap_items - plans[(size_t)k].n_clean_haps)}};
+    }
+    tab_group_start.push_back((int32_t)n_tab_haps);
+  }
+  std::vector<PdRegion> regions((size_t)K + 1);
+  pd_build_regions(shapes.data(), K, regions.data());
+  const int n_tab_units = regions[(size_t)K].unit_start[kPdLaunchTab], n_hot_units = regions[(size_t)K].unit_start[kPdLaunchHot],
+            n_full_units = regions[(size_t)K].unit_start[kPdLaunchFull];
+
+  // ---- inputs: one pinned block, every region's rows at the common strides, one copy ----
+  auto up = [](size_t x) { return (x + 255) / 256 * 256; };
+  const size_t hap_bytes = NH * mh, read_bytes = NR * mr;
+  const size_t o_hb = 0, o_hp = up(hap_bytes), o_rb = o_hp + up(hap_bytes), o_rq = o_rb + up(read_bytes),
+               o_ri = o_rq + up(read_bytes), o_rd = o_ri + up(read_bytes), o_gc = o_rd + up(read_bytes),
+               o_hl = o_gc + up(read_bytes), o_rl = o_hl + up(NH * 8), total = o_rl + up(NR * 8);
+  int rc;
+  if ((rc = c->inputs.reserve(total)) || (rc = c->stage_in.reserve(total))) return rc;
+  unsigned char* d = c->inputs.as<unsigned char>();
+  {
+    unsigned char* h = c->stage_in.as<unsigned char>();
+    auto rows = [](unsigned char* dst, size_t dst_stride, const int8_t* src, size_t src_stride, size_t n_rows) {
+      if (dst_stride == src_stride) { memcpy(dst, src, n_rows * src_stride); return; }
+      for (size_t i = 0; i < n_rows; i++) memcpy(dst + i * dst_stride, src + i * src_stride, src_stride);
+    };
+    for (int k = 0; k < K; k++) {
+      const PdProblem& q = R[(size_t)k].q;
+      const size_t h0 = (size_t)regions[(size_t)k].hap_base, r0 = (size_t)regions[(size_t)k].read_base;
+      const size_t nh = (size_t)q.n_hap_items, nr = (size_t)q.n_read_items, qh = (size_t)q.max_hap_len, qr = (size_t)q.max_read_len;
+      rows(h + o_hb + h0 * mh, mh, q.hap_bases, qh, nh); rows(h + o_hp + h0 * mh, mh, q.hap_pdbases, qh, nh);
+      rows(h + o_rb + r0 * mr, mr, q.read_bases, qr, nr); rows(h + o_rq + r0 * mr, mr, q.read_qual, qr, nr);
+      rows(h + o_ri + r0 * mr, mr, q.read_ins_qual, qr, nr); rows(h + o_rd + r0 * mr, mr, q.read_del_qual, qr, nr);
+      rows(h + o_gc + r0 * mr, mr, q.gcp, qr, nr);
+      memcpy(h + o_hl + h0 * 8, q.hap_lengths, nh * 8); memcpy(h + o_rl + r0 * 8, q.read_lengths, nr * 8);
+    }
+    PD_HIP_TRY(hipMemcpyAsync(d, h, total, hipMemcpyHostToDevice, s));
+  }
+
+  // ---- job tables: the regions' plans, shifted to the concatenated indices, in one more pinned block ----
+  const int entry_stride = ((int)mh + 2 * kLanes + 4 + 63) / 64 * 64;
+  const int carry_len = entry_stride;
+  const int n_jobs_max = std::max(std::max(n_tab_units, n_hot_units), n_full_units + (int)n_general);
+  const int n_blocks = std::max(1, std::min(std::max(n_jobs_max, (int)n_tail), 256 * 8));
+  if ((rc = c->entries.reserve(NH * (size_t)entry_stride * 4))) return rc;
+  if (n_tab_haps && (rc = c->entries_tab.reserve(2 * NH * (size_t)entry_stride * 4))) return rc;
+  if ((rc = c->misc.reserve(kPdMiscBytes))) return rc;
+  if ((rc = c->carry.reserve((size_t)n_blocks * 2 * (6 * (size_t)carry_len + 64) * 8))) return rc;
+  if ((rc = c->sums_pin.reserve(NP * 8 + 4 * (64 + (size_t)kPdMaxRegions)))) return rc;
+  const size_t o_rg = 0, o_cl = o_rg + up(((size_t)K + 1) * sizeof(PdRegion)), o_cs = o_cl + up(n_chunks * kLanes * sizeof(PlanLane)),
+               o_cr = o_cs + up(n_chunks * 4), o_ho = o_cr + up(n_chunks * 4), o_tg = o_ho + up(NH * 4),
+               o_nc = o_tg + up(tab_group_start.size() * 4), o_cc = o_nc + up(NH), o_jp = o_cc + up(NH * 32), o_jn = o_jp + up(n_general * 4),
+               o_js = o_jn + up(n_general * 4), o_jf = o_js + up(n_general), o_fj = o_jf + up(n_general), o_fc = o_fj + up(n_general * 4),
+               o_tl = o_fc + 256, o_tp = o_tl + up(n_tail * kLanes * sizeof(PlanLane)), o_tn = o_tp + up(n_tail * 4),
+               o_ts = o_tn + up(n_tail * 4), staged_total = o_ts + up(n_tail),
+               o_jl = staged_total, jobs_total = o_jl + up(n_general * kLanes * sizeof(PlanLane));   // (a striped job's lane row stays unused)
+  if ((rc = c->jobs.reserve(jobs_total + 256)) || (rc = c->stage_jobs.reserve(staged_total + 256))) return rc;
+  unsigned char* dj = c->jobs.as<unsigned char>();
+  {
+    unsigned char* hj = c->stage_jobs.as<unsigned char>();
+    memcpy(hj + o_rg, regions.data(), ((size_t)K + 1) * sizeof(PdRegion));
+    memcpy(hj + o_tg, tab_group_start.data(), tab_group_start.size() * 4);
+    PlanLane* cl = reinterpret_cast<PlanLane*>(hj + o_cl);
+    int32_t *cs = reinterpret_cast<int32_t*>(hj + o_cs), *cr = reinterpret_cast<int32_t*>(hj + o_cr);
+    int32_t* ho = reinterpret_cast<int32_t*>(hj + o_ho);   // [table launch's list | predicate launch's | byte-comparing launch's]
+    int32_t *ho_tab = ho, *ho_hot = ho + n_tab_haps, *ho_full = ho + n_tab_haps + n_hot_haps;
+    uint8_t* nc = hj + o_nc;
+    uint32_t* cc = reinterpret_cast<uint32_t*>(hj + o_cc);
+    int32_t *jp = reinterpret_cast<int32_t*>(hj + o_jp), *fj = reinterpret_cast<int32_t*>(hj + o_fj);
+    PlanLane* tl = reinterpret_cast<PlanLane*>(hj + o_tl);
+    int32_t *tp = reinterpret_cast<int32_t*>(hj + o_tp), *tn = reinterpret_cast<int32_t*>(hj + o_tn);
+    uint8_t* ts = hj + o_ts;
+    memset(hj + o_js, 1, n_general);
+    memset(hj + o_jf, 0, n_general);
+    memset(hj + o_jn, 0, n_general * 4);   // (job_steps: unused by striped jobs)
+    for (size_t j = 0; j < n_general; j++) fj[j] = (int32_t)j;
+    *reinterpret_cast<int32_t*>(hj + o_fc) = (int32_t)n_general;
+    for (int k = 0; k < K; k++) {
+      const PdCrossPlan& pl = plans[(size_t)k];
+      const PdRegion& rg = regions[(size_t)k];
+      for (const PlanLane& l : pl.cross_lanes) *cl++ = PlanLane{l.read < 0 ? -1 : l.read + rg.read_base, l.block};
+      for (const int32_t v : pl.chunk_steps) *cs++ = v;
+      for (const int32_t v : pl.chunk_rep) *cr++ = v + rg.read_base;
+      const size_t nh = (size_t)rg.n_haps;
+      for (size_t i = 0; i < nh; i++) {
+        int32_t*& dst = i < pl.n_tab_haps ? ho_tab : i < pl.n_clean_haps ? ho_hot : ho_full;
+        *dst++ = pl.hap_order[i] + rg.hap_base;
+      }
+      memcpy(nc, pl.hap_ncls.data(), nh); nc += nh;
+      memcpy(cc, pl.class_codes.data(), nh * 32); cc += nh * 8;
+      for (const int32_t v : pl.job_pair) *jp++ = v + rg.pair_base;
+      for (const PlanLane& l : pl.tail_lanes) *tl++ = PlanLane{l.read < 0 ? -1 : l.read + rg.pair_base, l.block};
+      for (const int32_t v : pl.tail_pair) *tp++ = v + rg.pair_base;
+      for (const int32_t v : pl.tail_steps) *tn++ = v;
+      for (const uint8_t v : pl.tail_striped) *ts++ = v;
+    }
+    PD_HIP_TRY(hipMemcpyAsync(dj, hj, staged_total, hipMemcpyHostToDevice, s));
+  }
+  PD_HIP_TRY(hipMemsetAsync(c->misc.p, 0, kPdMiscBytes, s));
+
+  const PdTables& t = pd_tables();
+  PdArgs a;
+  memset(&a, 0, sizeof a);
+  a.hap_bases = reinterpret_cast<const int8_t*>(d + o_hb);
+  a.hap_pdbases = reinterpret_cast<const int8_t*>(d + o_hp);
+  a.read_bases = reinterpret_cast<const int8_t*>(d + o_rb);
+  a.read_qual = reinterpret_cast<const int8_t*>(d + o_rq);
+  a.read_ins = reinterpret_cast<const int8_t*>(d + o_ri);
+  a.read_del = reinterpret_cast<const int8_t*>(d + o_rd);
+  a.gcp = reinterpret_cast<const int8_t*>(d + o_gc);
+  a.hap_len = reinterpret_cast<const int64_t*>(d + o_hl);
+  a.read_len = reinterpret_cast<const int64_t*>(d + o_rl);
+  a.batch = (int32_t)NP; a.max_hap = (int32_t)mh; a.max_read = (int32_t)mr;
+  a.cross_haps = 1;   // (cross layout; the pair index comes from the region table)
+  a.n_hap_items = (int32_t)NH;
+  a.q2err = c->tables.as<double>();
+  a.mm_prob = c->tables.as<double>() + t.q2err.size();
+  a.entries = c->entries.as<uint32_t>();
+  a.entry_stride = entry_stride;
+  {
+    void* dp = nullptr;
+    PD_HIP_TRY(hipHostGetDevicePointer(&dp, c->sums_pin.p, 0));
+    a.sums = static_cast<double*>(dp);
+  }
+  a.status = c->misc.as<int32_t>() + 64;   // one flag per region
+  a.next = c->misc.as<int32_t>() + 1;
+  a.carry = c->carry.as<double>();
+  a.carry_len = carry_len;
+  a.lanes = reinterpret_cast<const LaneSlot*>(dj + o_jl);
+  a.job_pair = reinterpret_cast<const int32_t*>(dj + o_jp);
+  a.job_steps = reinterpret_cast<const int32_t*>(dj + o_jn);
+  a.job_striped = dj + o_js;
+  a.n_chunks_cross = 1;
+  a.cross_lanes = reinterpret_cast<const LaneSlot*>(dj + o_cl);
+  a.chunk_steps = reinterpret_cast<const int32_t*>(dj + o_cs);
+  a.chunk_rep = reinterpret_cast<const int32_t*>(dj + o_cr);
+  a.hap_ncls = n_tab_haps ? dj + o_nc : nullptr;
+  a.class_codes = reinterpret_cast<const uint32_t*>(dj + o_cc);
+  a.entries_tab = c->entries_tab.as<uint32_t>();
+  a.next_special = n_tab_haps ? reinterpret_cast<int32_t*>(c->entries_tab.as<uint32_t>() + NH * (size_t)entry_stride) : nullptr;
+  a.tab_group_start = reinterpret_cast<const int32_t*>(dj + o_tg);
+  a.job_flags = dj + o_jf;
+  a.full_jobs = reinterpret_cast<const int32_t*>(dj + o_fj);
+  a.full_count = reinterpret_cast<const int32_t*>(dj + o_fc);
+  a.sb_stride = entry_stride / 64; a.ns_stride = entry_stride;
+  a.regions = reinterpret_cast<const PdRegion*>(dj + o_rg);
+  a.n_regions = K;
+#ifdef GKL_PD_PROF
+  a.prof = reinterpret_cast<unsigned long long*>(c->misc.as<char>() + 128);
+#endif
+  const int32_t* d_ho = reinterpret_cast<const int32_t*>(dj + o_ho);
+
+  hipLaunchKernelGGL(pdhmm_entries_kernel, dim3((unsigned)NH), dim3(kLanes), 0, s, a);   // one wavefront per haplotype item
+  PD_HIP_TRY(hipEventRecord(c->ev0, s));
+  if (n_tab_units > 0) {
+    PdArgs at = a;
+    at.hap_order = d_ho;
+    at.n_cross_jobs = at.n_jobs = n_tab_units;
+    at.multi_launch = kPdLaunchTab;
+    at.next = c->misc.as<int32_t>() + 4;
+    if (c->fma_mode) hipLaunchKernelGGL((pdhmm_fwd_tab_kernel<true, true>), dim3(std::min(n_tab_units, n_blocks)), dim3(64), 0, s, at, t.initial_condition);
+    else             hipLaunchKernelGGL((pdhmm_fwd_tab_kernel<false, true>), dim3(std::min(n_tab_units, n_blocks)), dim3(64), 0, s, at, t.initial_condition);
+  }
+  if (n_hot_units > 0) {
+    PdArgs ah = a;
+    ah.hap_order = d_ho + n_tab_haps;
+    ah.n_cross_jobs = ah.n_jobs = n_hot_units;
+    ah.multi_launch = kPdLaunchHot;
+    ah.full_jobs = nullptr;
+    if (c->fma_mode) hipLaunchKernelGGL((pdhmm_fwd_kernel<true, false, true, true>), dim3(std::min(n_hot_units, n_blocks)), dim3(64), 0, s, ah, t.initial_condition);
+    else             hipLaunchKernelGGL((pdhmm_fwd_kernel<false, false, true, true>), dim3(std::min(n_hot_units, n_blocks)), dim3(64), 0, s, ah, t.initial_condition);
+  }
+  if (n_full_units + (int)n_general > 0) {   // the listed jobs: the striped reads, all from the host's list
+    PdArgs af = a;
+    af.hap_order = d_ho + n_tab_haps + n_hot_haps;
+    af.n_cross_jobs = n_full_units;
+    af.n_jobs = n_full_units + (int)n_general;
+    af.multi_launch = kPdLaunchFull;
+    af.next = c->misc.as<int32_t>() + 3;
+    if (c->fma_mode) hipLaunchKernelGGL((pdhmm_fwd_kernel<true, false, false, true>), dim3(std::min(af.n_jobs, n_blocks)), dim3(64), 0, s, af, t.initial_condition);
+    else             hipLaunchKernelGGL((pdhmm_fwd_kernel<false, false, false, true>), dim3(std::min(af.n_jobs, n_blocks)), dim3(64), 0, s, af, t.initial_condition);
+  }
+  if (n_tail > 0) {   // every region's tail pairs, scalar-engine arithmetic (same stream: the carry rows are free again)
+    PdArgs at = a;
+    at.lanes = reinterpret_cast<const LaneSlot*>(dj + o_tl);
+    at.job_pair = reinterpret_cast<const int32_t*>(dj + o_tp);
+    at.job_steps = reinterpret_cast<const int32_t*>(dj + o_tn);
+    at.job_striped = dj + o_ts;
+    at.n_jobs = (int32_t)n_tail;
+    at.n_cross_jobs = 0;
+    at.job_flags = nullptr;
+    at.full_jobs = nullptr;
+    at.next = c->misc.as<int32_t>() + 2;
+    hipLaunchKernelGGL((pdhmm_fwd_kernel<false, true, false, true>), dim3((unsigned)std::min<size_t>(n_tail, (size_t)n_blocks)), dim3(64), 0, s, at, t.initial_condition);
+  }
+  PD_HIP_TRY(hipEventRecord(c->ev1, s));
+  PD_HIP_TRY(hipGetLastError());
+  double* sums = c->sums_pin.as<double>();
+  int32_t* status = reinterpret_cast<int32_t*>(sums + NP);
+  PD_HIP_TRY(hipMemcpyAsync(status, c->misc.p, 4 * (64 + (size_t)K), hipMemcpyDeviceToHost, s));
+  PD_HIP_TRY(hipStreamSynchronize(s));
+  PD_HIP_TRY(hipEventElapsedTime(&c->last_ms, c->ev0, c->ev1));
+  c->last_routing[0] = (int32_t)n_tab_haps; c->last_routing[1] = (int32_t)n_hot_haps; c->last_routing[2] = (int32_t)n_full_haps;
+  for (int k = 0; k < K; k++) {
+    PdMultiRegion& r = R[(size_t)k];
+    r.flag = status[64 + k];
+    r.routing[0] = (int32_t)plans[(size_t)k].n_tab_haps; r.routing[1] = (int32_t)(plans[(size_t)k].n_clean_haps - plans[(size_t)k].n_tab_haps);
+    r.routing[2] = (int32_t)((size_t)r.q.n_hap_items - plans[(size_t)k].n_clean_haps);
+  }
+  // one finalisation over all pairs (log10 with the host libm, see pd_run_locked); a region with an input error keeps its output untouched
+  const std::function<void(int64_t, int64_t)> finalise = [&](int64_t lo, int64_t hi) {
+    int k = pd_region_of_pair(regions.data(), K, (int)lo);
+    for (int64_t i = lo; i < hi; i++) {
+      while (i >= regions[(size_t)k + 1].pair_base) k++;
+      if (status[64 + k] == 0) R[(size_t)k].out[i - regions[(size_t)k].pair_base] = std::log10(sums[i]) - t.initial_condition_log10;
+    }
+  };
+  static const int fin_threads = std::max(1, std::min(4, (int)std::thread::hardware_concurrency()));
+  try {
+    c->workers.parallel_for((int64_t)NP, fin_threads, finalise, 4096);
+  } catch (const std::bad_alloc&) {
+    return pd_fail(GKLHIP_ERR_OOM, "out of memory in the host finalisation");
+  }
+  return GKLHIP_OK;
+}
+
+// process-wide, per device (gklhip_pdhmm_combine_counts): region calls computed, region calls that shared a launch set
+// with another, launch sets
+constexpr int kPdCountDevices = 64;
+std::atomic<int64_t> g_pd_counts[kPdCountDevices][3];
+void pd_count(int device, int64_t calls, int64_t shared, int64_t sets) {
+  if (device < 0 || device >= kPdCountDevices) return;
+  g_pd_counts[device][0] += calls; g_pd_counts[device][1] += shared; g_pd_counts[device][2] += sets;
+}
+
+constexpr const char* kPdInputErrorText = "Error while calculating pdhmm. Input arrays aren't valid.";
+
+// pd_run_multi_locked behind the same fence as pd_run_locked: no C++ exception leaves, a failed launch set is drained.
+int pd_run_multi_guarded(gklhip_pdhmm_ctx* c, std::vector<PdMultiRegion>& R) {
+  int rc;
+  try { rc = pd_run_multi_locked(c, R); }
+  catch (const std::bad_alloc&) { rc = pd_fail(GKLHIP_ERR_OOM, "host memory allocation failed"); }
+  catch (const std::exception& e) { rc = pd_fail(GKLHIP_ERR_HIP, "%s", e.what()); }
+  catch (...) { rc = pd_fail(GKLHIP_ERR_HIP, "unexpected C++ exception"); }
+  if (rc != GKLHIP_OK) {
+    const std::string keep = g_pd_err;
+    if (c->stream) (void)hipStreamSynchronize(c->stream);
+    (void)hipGetLastError();
+    g_pd_err = keep;
+  }
+  return rc;
+}
+
+// Does the cross call fit a multi-region launch set on its own?
+bool pd_fits_multi(const PdProblem& q) {
+  return q.cross_haps && (size_t)q.n_pairs <= kPdMultiMaxPairs &&
+         pd_input_bytes((size_t)q.n_hap_items, (size_t)q.n_read_items, (size_t)q.max_hap_len, (size_t)q.max_read_len) <= kPdStageBytes;
+}
+
+// ---- concurrent cross calls share launches (GKL_HIP_PDHMM_COMBINE=1; off by default) ----
+// One combiner per device, like SmallCombiner of pairhmm_host_call.h: a call queues a ticket; the first thread that finds
+// the combiner free leads -- it takes every queued ticket with its own fma and tail mode, up to the limits of a multi-region
+// call, runs them as one on ITS context (stream, buffers) and hands every follower its status, error text, routing and the
+// kernel time; the followers' doubles are written by the leader's finalisation.  Every thread holds its own context's lock
+// throughout and never another's.
+struct PdTicket {
+  PdProblem q;
+  double* out;
+  int fma_mode, tail_mode;
+  bool done = false;
+  int rc = GKLHIP_OK;
+  char err[256] = {0};
+  int32_t routing[3] = {0, 0, 0};
+  float ms = 0.f;
+  PdTicket* next = nullptr;   // the queue: a list through the tickets, no allocation
+};
+struct PdCombiner {
+  std::mutex mu;
+  std::condition_variable cv;
+  PdTicket *head = nullptr, *tail = nullptr;
+  bool busy = false;   // a leader is collecting or running
+};
+PdCombiner g_pd_combiners[kPdCountDevices];
+struct PdCombineConfig { bool on; int min; int64_t wait_us; };
+const PdCombineConfig* pd_combine_config() {
+  static const PdCombineConfig cfg = [] {
+    PdCombineConfig r{false, 1, 0};
+    const char* v = getenv("GKL_HIP_PDHMM_COMBINE");
+    r.on = v && *v && strcmp(v, "0") != 0;
+    if (const char* m = getenv("GKL_HIP_PDHMM_COMBINE_MIN")) r.min = std::max(1, std::min(kPdMaxRegions, atoi(m)));
+    if (const char* w = getenv("GKL_HIP_PDHMM_COMBINE_WAIT_US")) r.wait_us = std::max<int64_t>(0, std::min<int64_t>(atoll(w), 60ll * 1000 * 1000));
+    return r;
+  }();
+  return &cfg;
+}
+
+// c->mu is held.  The call's own result: status (and g_pd_err), c->last_ms, c->last_routing.
+int pd_run_combined(gklhip_pdhmm_ctx* c, const PdProblem& q, double* out_host) {
+  const PdCombineConfig& cfg = *pd_combine_config();
+  PdCombiner& cb = g_pd_combiners[c->device];
+  PdTicket me;
+  me.q = q; me.out = out_host; me.fma_mode = c->fma_mode; me.tail_mode = c->tail_mode;
+  auto mine = [&](const PdTicket* t) { return t->fma_mode == me.fma_mode && t->tail_mode == me.tail_mode; };
+  PdTicket* taken[kPdMaxRegions];
+  int n_taken = 0;
+  {
+    std::unique_lock<std::mutex> lk(cb.mu);
+    (cb.tail ? cb.tail->next : cb.head) = &me;
+    cb.tail = &me;
+    cb.cv.notify_all();   // (a leader that waits for company counts the queue)
+    while (!me.done && cb.busy) cb.cv.wait(lk);
+    if (!me.done) {
+      cb.busy = true;   // lead
+      if (cfg.min > 1 && cfg.wait_us > 0) {   // bounded: company that does not arrive in time is not waited for
+        const auto deadline = std::chrono::steady_clock::now() + std::chrono::microseconds(cfg.wait_us);
+        cb.cv.wait_until(lk, deadline, [&] {
+          int have = 0;
+          for (const PdTicket* t = cb.head; t; t = t->next) have += mine(t);
+          return have >= cfg.min;
+        });
+      }
+      // its own ticket first, then the queue in order while the set still fits
+      size_t pairs = 0, nh = 0, nr = 0, mh = 0, mr = 0;
+      auto fits_with = [&](const PdTicket* t) {
+        const size_t p2 = pairs + (size_t)t->q.n_pairs, nh2 = nh + (size_t)t->q.n_hap_items, nr2 = nr + (size_t)t->q.n_read_items,
+                     mh2 = std::max(mh, (size_t)t->q.max_hap_len), mr2 = std::max(mr, (size_t)t->q.max_read_len);
+        return p2 <= kPdMultiMaxPairs && pd_input_bytes(nh2, nr2, mh2, mr2) <= kPdStageBytes;
+      };
+      auto take = [&](PdTicket* t) {
+        pairs += (size_t)t->q.n_pairs; nh += (size_t)t->q.n_hap_items; nr += (size_t)t->q.n_read_items;
+        mh = std::max(mh, (size_t)t->q.max_hap_len); mr = std::max(mr, (size_t)t->q.max_read_len);
+        taken[n_taken++] = t;
+      };
+      take(&me);
+      PdTicket *prev = nullptr, *t = cb.head;
+      while (t) {
+        PdTicket* nx = t->next;
+        const bool go = t == &me || (n_taken < kPdMaxRegions && mine(t) && fits_with(t));
+        if (go) {
+          if (t != &me) take(t);
+          (prev ? prev->next : cb.head) = nx;
+          if (cb.tail == t) cb.tail = prev;
+          t->next = nullptr;
+        } else {
+          prev = t;
+        }
+        t = nx;
+      }
+    }
+  }
+  if (n_taken > 0) {
+    // the launch set, on this context; whatever happens every taken ticket gets an answer
+    int rc;
+    std::string err;
+    try {
+      std::vector<PdMultiRegion> R((size_t)n_taken);
+      for (int k = 0; k < n_taken; k++) { R[(size_t)k].q = taken[k]->q; R[(size_t)k].out = taken[k]->out; }
+      rc = pd_run_multi_guarded(c, R);
+      if (rc != GKLHIP_OK) err = g_pd_err;
+      for (int k = 0; k < n_taken; k++) {
+        PdTicket* t = taken[k];
+        t->rc = rc != GKLHIP_OK ? rc : (R[(size_t)k].flag != 0 ? GKLHIP_ERR_INVALID_ARG : GKLHIP_OK);
+        snprintf(t->err, sizeof t->err, "%s", rc != GKLHIP_OK ? err.c_str() : (R[(size_t)k].flag != 0 ? kPdInputErrorText : ""));
+        for (int i = 0; i < 3; i++) t->routing[i] = R[(size_t)k].routing[i];
+        t->ms = c->last_ms;
+      }
+    } catch (...) {
+      for (int k = 0; k < n_taken; k++) { taken[k]->rc = GKLHIP_ERR_OOM; snprintf(taken[k]->err, sizeof taken[k]->err, "host memory allocation failed"); }
+    }
+    pd_count(c->device, n_taken, n_taken > 1 ? n_taken : 0, 1);
+    std::lock_guard<std::mutex> lk(cb.mu);
+    for (int k = 0; k < n_taken; k++) taken[k]->done = true;   // (a follower's ticket lives on its stack: not touched after this)
+    cb.busy = false;
+    cb.cv.notify_all();
+  }
+  c->last_ms = me.ms;
+  for (int i = 0; i < 3; i++) c->last_routing[i] = me.routing[i];
+  return me.rc == GKLHIP_OK ? GKLHIP_OK : pd_fail(me.rc, "%s", me.err);
+}
+
+// a cross call on a context of this process, counted (gklhip_pdhmm_combine_counts); with the combiner on, through it
+int pd_run_cross(gklhip_pdhmm_ctx* c, const PdProblem& q, double* out_host) {
+  if (!c->remote && pd_combine_config()->on && c->device >= 0 && c->device < kPdCountDevices && pd_fits_multi(q)) {
+    std::lock_guard<std::mutex> lock(c->mu);
+    return pd_run_combined(c, q, out_host);
+  }
+  if (!c->remote) pd_count(c->device, 1, 0, 1);
+  return pd_run(c, q, out_host);
+}
 }  // namespace
 
 int gklhip_pdhmm_compute(gklhip_pdhmm_ctx* c, const gklhip_pdhmm_batch* b, double* out_host) {
@@ -1105,7 +1607,85 @@ int gklhip_pdhmm_compute_cross_batched(gklhip_pdhmm_ctx* c, const gklhip_pdhmm_c
               x->hap_bases, x->hap_pdbases, x->read_bases, x->read_qual, x->read_ins_qual, x->read_del_qual, x->gcp,
               x->hap_lengths, x->read_lengths, ref_batch_pairs};
   const int rc = pd_validate(q, out_host);
-  return rc ? rc : pd_run(c, q, out_host);
+  return rc ? rc : pd_run_cross(c, q, out_host);
+}
+
+int gklhip_pdhmm_compute_cross_multi(gklhip_pdhmm_ctx* c, int32_t n_regions, const gklhip_pdhmm_cross* regions, const int64_t* ref_batch_pairs,
+                                     double* const* out_host, int32_t* status_out) {
+  if (!c) return pd_fail(GKLHIP_ERR_INVALID_ARG, "context is NULL (initNative not called)");
+  if (n_regions <= 0) return pd_fail(GKLHIP_ERR_INVALID_ARG, "no regions to process");
+  if (!regions || !out_host) return pd_fail(GKLHIP_ERR_INVALID_ARG, "regions / out_host is NULL");
+  int first_rc = GKLHIP_OK, first_k = n_regions;   // the failing region with the lowest index
+  std::string first_err;
+  auto note = [&](int k, int rc) {   // (g_pd_err holds region k's message)
+    if (status_out) status_out[k] = rc;
+    if (rc != GKLHIP_OK && k < first_k) { first_k = k; first_rc = rc; first_err = g_pd_err; }
+  };
+  try {
+    // the argument checks of gklhip_pdhmm_compute_cross_batched, region by region, before anything touches the device
+    std::vector<PdMultiRegion> R;
+    std::vector<int32_t> index;
+    R.reserve((size_t)n_regions);
+    for (int32_t k = 0; k < n_regions; k++) {
+      const gklhip_pdhmm_cross* x = &regions[k];
+      const int64_t rb = ref_batch_pairs ? ref_batch_pairs[k] : 0;
+      int rc = GKLHIP_OK;
+      if (rb < 0) rc = pd_fail(GKLHIP_ERR_INVALID_ARG, "ref_batch_pairs must not be negative");
+      else if (x->n_reads <= 0 || x->n_haps <= 0) rc = pd_fail(GKLHIP_ERR_INVALID_ARG, "no pairs to process");
+      PdMultiRegion r;
+      if (rc == GKLHIP_OK) {
+        r.q = PdProblem{(int64_t)x->n_reads * x->n_haps, x->n_reads, x->n_haps, x->n_haps, x->max_hap_len, x->max_read_len,
+                        x->hap_bases, x->hap_pdbases, x->read_bases, x->read_qual, x->read_ins_qual, x->read_del_qual, x->gcp,
+                        x->hap_lengths, x->read_lengths, rb};
+        r.out = out_host[k];
+        rc = pd_validate(r.q, r.out);
+      }
+      note(k, rc);
+      if (rc == GKLHIP_OK) { R.push_back(r); index.push_back(k); }
+    }
+    if (R.empty()) return pd_fail(first_rc, "%s", first_err.c_str());
+    size_t pairs = 0;
+    for (const PdMultiRegion& r : R) pairs += (size_t)r.q.n_pairs;
+    const bool fits = !c->remote && R.size() <= (size_t)kPdMaxRegions && pairs <= kPdMultiMaxPairs && pd_multi_input_bytes(R) <= kPdStageBytes;
+    if (!fits) {
+      // a client context, or a call over the limits: region by region through the single-call path (same results).
+      // last_routing: the sums, last_kernel_ms: the sum of the calls' kernel times
+      int32_t routing[3] = {0, 0, 0};
+      float ms = 0.f;
+      for (size_t i = 0; i < R.size(); i++) {
+        if (!c->remote) pd_count(c->device, 1, 0, 1);
+        note(index[i], pd_run(c, R[i].q, R[i].out));
+        std::lock_guard<std::mutex> lock(c->mu);
+        ms += c->last_ms;
+        for (int j = 0; j < 3; j++) routing[j] += c->last_routing[j];
+      }
+      std::lock_guard<std::mutex> lock(c->mu);
+      c->last_ms = ms;
+      for (int j = 0; j < 3; j++) c->last_routing[j] = routing[j];
+    } else {
+      std::lock_guard<std::mutex> lock(c->mu);
+      const int rc = pd_run_multi_guarded(c, R);
+      pd_count(c->device, (int64_t)R.size(), R.size() > 1 ? (int64_t)R.size() : 0, 1);
+      for (size_t i = 0; i < R.size(); i++) {
+        if (rc != GKLHIP_OK) { note(index[i], rc); continue; }   // (g_pd_err: the launch set's message)
+        note(index[i], R[i].flag != 0 ? pd_fail(GKLHIP_ERR_INVALID_ARG, "%s", kPdInputErrorText) : GKLHIP_OK);
+      }
+    }
+  } catch (const std::bad_alloc&) {
+    return pd_fail(GKLHIP_ERR_OOM, "host memory allocation failed");
+  } catch (...) {
+    return pd_fail(GKLHIP_ERR_HIP, "unexpected C++ exception");
+  }
+  return first_rc == GKLHIP_OK ? GKLHIP_OK : pd_fail(first_rc, "%s", first_err.c_str());
+}
+
+int gklhip_pdhmm_combine_counts(int device, int64_t out[3], int reset) {
+  if (!out) return pd_fail(GKLHIP_ERR_INVALID_ARG, "NULL argument");
+  if (device >= kPdCountDevices) return pd_fail(GKLHIP_ERR_INVALID_ARG, "device %d", device);
+  out[0] = out[1] = out[2] = 0;
+  for (int d = device < 0 ? 0 : device; d < (device < 0 ? kPdCountDevices : device + 1); d++)
+    for (int i = 0; i < 3; i++) out[i] += reset ? g_pd_counts[d][i].exchange(0) : g_pd_counts[d][i].load();
+  return GKLHIP_OK;
 }
 
 }  // extern "C"

@@ -26,6 +26,7 @@
 #include <stdint.h>
 
 #include "pairhmm_fwd_kernel.h"  // recv_above, read_lane, kLanes
+#include "pdhmm_multi_plan.h"   // PdRegion: the multi-region launches
 
 namespace gklhip {
 
@@ -149,6 +150,11 @@ struct PdArgs {
   // a launch over one slice of a big paired call (pdhmm_api.hip): pdhmm_entries_kernel's first haplotype item; the first
   // listed job of a launch that walks the list (n_jobs is then where it ends)
   int32_t item_base, job_base;
+  // multi-region launches (the kMulti instantiations; pdhmm_multi_plan.h): the cross products of n_regions calls lie
+  // concatenated in the arrays above, `regions` (n_regions + 1 entries) says where; multi_launch: which of the table's three
+  // launches this is; status then holds one flag per region.  The other instantiations never read these.
+  const PdRegion* regions;
+  int32_t n_regions, multi_launch;
 #ifdef GKL_PD_PROF
   unsigned long long* prof;     // development build: cycle and step counters of the table kernel
 #endif
@@ -482,13 +488,16 @@ struct PdJob {
   }
 
   __device__ __forceinline__ void setup(const PdArgs& a, int p, int block, int n_blocks, bool active, double init) {
-    const int ri = pd_read_of(a, p);
+    setup_at(a, pd_read_of(a, p), a.status, block, n_blocks, active, init);
+  }
+  // ... of read item `ri`, input errors reported to `status` (a multi-region launch: the region's own flag)
+  __device__ __forceinline__ void setup_at(const PdArgs& a, int ri, int32_t* status, int block, int n_blocks, bool active, double init) {
     const int R = (int)a.read_len[ri];
     const int pads = n_blocks * RPL - R;
     const int first = block * RPL - pads;
     const int64_t ro = (int64_t)ri * a.max_read;
     holds_last = active && block == n_blocks - 1;
-    status_flag = a.status;
+    status_flag = status;
     row1_slot = (active && first <= 0 && -first < RPL) ? -first : -1;
     pad_slot = (active && first < 0 && -1 - first < RPL) ? -1 - first : -1;
     has_non_acgt = false;
@@ -503,7 +512,7 @@ struct PdJob {
       xinfo[s] = 0;
       if (active && v >= 0) {
         const int8_t qi = a.read_ins[ro + v], qd = a.read_del[ro + v], qc = a.gcp[ro + v];
-        if (qi < 0 || qd < 0 || qc < 0) atomicOr(a.status, 2);  // PDHMM_INPUT_DATA_ERROR
+        if (qi < 0 || qd < 0 || qc < 0) atomicOr(status, 2);  // PDHMM_INPUT_DATA_ERROR
         const int ia = qi & 0xff, ib = qd & 0xff, ic = qc & 0xff;
         const int mn = ia <= ib ? ia : ib, mx = ia <= ib ? ib : ia;
         tmm[s] = mx > 254 ? 0.0 : a.mm_prob[((mx * (mx + 1)) >> 1) + mn];
@@ -964,7 +973,10 @@ struct PdJob {
 // Without the compute-and-select step the kernel needs 234 VGPRs at 6 rows per lane and spills nothing; with it 256 and
 // 72-138 spilled registers, which is why the full kernel alone ran best at 5 rows (x32 fixture: 6.0 ms full at 5 rows,
 // 5.5 ms hot at 6).  Both instantiations use the same rows per lane: they share the packing.
-template <bool FMA, bool kSerial = false, bool kHot = false>
+// kMulti: the units of several regions in one launch (PdArgs::regions): a cross job finds its region by a search over
+// the launch's unit prefix sums, a listed job (striped read, tail pair) by one over the regions' first output pairs --
+// both uniform over the wavefront, once per job.
+template <bool FMA, bool kSerial = false, bool kHot = false, bool kMulti = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void pdhmm_fwd_kernel(PdArgs a, double init_condition) {
   const int lane = threadIdx.x;
   const int64_t cstride = 6 * (int64_t)a.carry_len + 64;
@@ -979,15 +991,22 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void pd
     if (!listed_by_index) j += a.job_base;
     if (j >= (listed_by_index ? a.n_cross_jobs + a.full_count[0] : a.n_jobs)) break;
     if (j < a.n_cross_jobs) {
-      const int k = j / a.n_chunks_cross, chunk = j - k * a.n_chunks_cross;
+      int k, chunk, kr = 0;
+      if constexpr (kMulti) {
+        kr = pd_region_of_unit(a.regions, a.n_regions, a.multi_launch, j);
+        pd_unit_split(a.regions[kr], a.multi_launch, j, &k, &chunk);
+      } else {
+        k = j / a.n_chunks_cross; chunk = j - k * a.n_chunks_cross;
+      }
       const int hi = a.hap_order[k];
       const LaneSlot sl = a.cross_lanes[(int64_t)chunk * kLanes + lane];
       const bool active = sl.read >= 0;
       const int ri = active ? sl.read : a.chunk_rep[chunk];
-      const int p = ri * a.cross_haps + hi;
+      const int p = kMulti ? pd_pair_index(a.regions[kr], ri, hi) : ri * a.cross_haps + hi;
       const int H = (int)a.hap_len[hi];
       const int n_blocks = ((int)a.read_len[ri] + Job::RPL) / Job::RPL;
-      job.setup(a, p, sl.block, n_blocks, active, init_condition / (double)H);
+      if constexpr (kMulti) job.setup_at(a, ri, a.status + kr, sl.block, n_blocks, active, init_condition / (double)H);
+      else job.setup(a, p, sl.block, n_blocks, active, init_condition / (double)H);
       const uint32_t* e0 = a.entries + (int64_t)hi * a.entry_stride;
       job.run_packed(e0 + kLanes - sl.block, H + a.chunk_steps[chunk], __ballot((e0[0] & kPdOdd) != 0u) != 0);
       if (job.holds_last) a.sums[p] = job.sum;
@@ -997,27 +1016,34 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void pd
     if (listed_by_index) j = a.full_jobs[j];
     else if (kHot && a.job_flags && (a.job_striped[j] != 0 || a.job_flags[j] != 0)) continue;  // the full launch's
     const int rep = a.job_pair[j];
+    // kMulti: a listed job holds ONE pair (a striped read's, a tail pair's): its region is the job's
+    const int kr = kMulti ? pd_region_of_pair(a.regions, a.n_regions, rep) : 0;
     if (kHot || !a.job_striped[j]) {
       const LaneSlot sl = a.lanes[(int64_t)j * kLanes + lane];
       const bool active = sl.read >= 0;
       const int p = active ? sl.read : rep;
-      const int hi = pd_hap_of(a, p);
-      const int n_blocks = ((int)a.read_len[pd_read_of(a, p)] + Job::RPL) / Job::RPL;
+      int m_ri = 0, m_hi = 0;
+      if constexpr (kMulti) pd_pair_split(a.regions[kr], p, &m_ri, &m_hi);
+      const int hi = kMulti ? m_hi : pd_hap_of(a, p);
+      const int n_blocks = ((int)a.read_len[kMulti ? m_ri : pd_read_of(a, p)] + Job::RPL) / Job::RPL;
       const int H = (int)a.hap_len[hi];
       const double init = init_condition / (double)H;  // pdhmm.h:867-878 (IEEE division, as on the host)
-      job.setup(a, p, sl.block, n_blocks, active, init);
+      if constexpr (kMulti) job.setup_at(a, m_ri, a.status + kr, sl.block, n_blocks, active, init);
+      else job.setup(a, p, sl.block, n_blocks, active, init);
       // block k of a pair sees column j at step j + k
       const uint32_t* e0 = a.entries + (int64_t)hi * a.entry_stride;
       job.run_packed(e0 + kLanes - sl.block, a.job_steps[j], __ballot((e0[0] & kPdOdd) != 0u) != 0);
       if (job.holds_last) a.sums[p] = job.sum;
       continue;
     }
-    const int rep_hap = pd_hap_of(a, rep);
+    int m_read = 0, m_hap = 0;
+    if constexpr (kMulti) pd_pair_split(a.regions[kr], rep, &m_read, &m_hap);
+    const int rep_hap = kMulti ? m_hap : pd_hap_of(a, rep);
     const int H = (int)a.hap_len[rep_hap];
     const double init = init_condition / (double)H;
     const uint32_t* ep = a.entries + (int64_t)rep_hap * a.entry_stride + kLanes - lane;  // lane l sees column j at step j + l
     const int n_steps = H + kLanes - 1;
-    const int R = (int)a.read_len[pd_read_of(a, rep)];
+    const int R = (int)a.read_len[kMulti ? m_read : pd_read_of(a, rep)];
     const int n_blocks = (R + Job::RPL) / Job::RPL;
     const int n_stripes = (n_blocks + kLanes - 1) / kLanes;
     const int first_cnt = n_blocks - kLanes * (n_stripes - 1);
@@ -1026,7 +1052,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void pd
       bool active;
       if (st == 0) { active = lane >= kLanes - first_cnt; block = lane - (kLanes - first_cnt); }
       else { active = true; block = first_cnt + (st - 1) * kLanes + lane; }
-      job.setup(a, rep, block, n_blocks, active, init);
+      if constexpr (kMulti) job.setup_at(a, m_read, a.status + kr, block, n_blocks, active, init);
+      else job.setup(a, rep, block, n_blocks, active, init);
       const double* cin = st > 0 ? my + (int64_t)((st + 1) & 1) * cstride : nullptr;
       double* cout = st + 1 < n_stripes ? my + (int64_t)(st & 1) * cstride : nullptr;
       job.run(ep, n_steps, lane, cin, cout, a.carry_len);
@@ -1038,7 +1065,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void pd
 
 // The table launch: cross jobs over the haplotypes whose columns fall into at most kPdTabClasses classes (see the
 // table entry format).  18 KB of LDS per wavefront: eight wavefronts per CU, the two per SIMD the register budget allows.
-template <bool FMA>
+// kMulti: the units of several regions in one launch (see pdhmm_fwd_kernel); the region's values die before the step
+// loops: what survives a haplotype is the lane's pair offset (in place of ri * cross_haps) and the region's status address.
+template <bool FMA, bool kMulti = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void pdhmm_fwd_tab_kernel(PdArgs a, double init_condition) {
   __shared__ __attribute__((aligned(16))) unsigned char lds[kPdTabClasses * kPdTabClassBytes];
   const int lane = threadIdx.x;
@@ -1053,17 +1082,24 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void pd
     if (lane == 0) u = atomicAdd(a.next, 1);
     u = __builtin_amdgcn_readfirstlane(u);
     if (u >= a.n_cross_jobs) break;   // (units: haplotype group x chunk)
-    const int g = u / a.n_chunks_cross, chunk = u - g * a.n_chunks_cross;
+    int g, chunk, kr = 0;
+    if constexpr (kMulti) {
+      kr = pd_region_of_unit(a.regions, a.n_regions, kPdLaunchTab, u);
+      pd_unit_split(a.regions[kr], kPdLaunchTab, u, &g, &chunk);
+    } else {
+      g = u / a.n_chunks_cross; chunk = u - g * a.n_chunks_cross;
+    }
     const int k0 = a.tab_group_start[g], k1 = a.tab_group_start[g + 1];
     const LaneSlot sl = a.cross_lanes[(int64_t)chunk * kLanes + lane];
     const bool active = sl.read >= 0;
     const int ri = active ? sl.read : a.chunk_rep[chunk];
+    const int pair0 = kMulti ? pd_pair_index(a.regions[kr], ri, 0) : 0;   // the lane's pair with haplotype item 0
     const int n_blocks = ((int)a.read_len[ri] + Job::RPL) / Job::RPL;
     const int top = __builtin_amdgcn_readfirstlane(a.chunk_steps[chunk]);
     int hi_built = -1;   // the haplotype whose classes the table in LDS was built for
     for (int k = k0; k < k1; k++) {
       const int hi = a.hap_order[k];
-      const int p = ri * a.cross_haps + hi;
+      const int p = kMulti ? pair0 + hi : ri * a.cross_haps + hi;
       const int H = (int)a.hap_len[hi];
 #ifdef GKL_PD_PROF
       const unsigned long long pt_setup = __builtin_readcyclecounter();
@@ -1077,7 +1113,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void pd
       if (same) {
         job.restart(init_condition / (double)H);
       } else {
-        job.setup(a, p, sl.block, n_blocks, active, init_condition / (double)H);
+        if constexpr (kMulti) job.setup_at(a, ri, a.status + kr, sl.block, n_blocks, active, init_condition / (double)H);
+        else job.setup(a, p, sl.block, n_blocks, active, init_condition / (double)H);
         job.build_table(lds_base, lane, a.class_codes + (int64_t)hi * 8, (int)a.hap_ncls[hi]);
         hi_built = hi;
       }

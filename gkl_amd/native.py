@@ -426,10 +426,12 @@ class PdhmmServerInfo(C.Structure):
     _fields_ = [("protocol", C.c_int32), ("pid", C.c_int32), ("library_state", C.c_int32), ("reserved0", C.c_int32),
                 ("calls_served", C.c_int64), ("calls_failed", C.c_int64), ("calls_active", C.c_int32),
                 ("live_connections", C.c_int32), ("connections_total", C.c_int64), ("pairs_served", C.c_int64),
-                ("reserved", C.c_int64 * 9)]
+                ("combine_counts", C.c_int64 * 3), ("reserved", C.c_int64 * 6)]
 
     def as_dict(self):
-        return {n: getattr(self, n) for n, _ in self._fields_ if not n.startswith("reserved")}
+        d = {n: getattr(self, n) for n, _ in self._fields_ if not n.startswith("reserved")}
+        d["combine_counts"] = tuple(int(v) for v in self.combine_counts)
+        return d
 
 
 _pd_lib = None
@@ -459,6 +461,11 @@ def load_pdhmm_library(path: Optional[str] = None):
     lib.gklhip_pdhmm_compute_cross.restype = C.c_int
     lib.gklhip_pdhmm_compute_cross_batched.argtypes = [C.c_void_p, C.POINTER(CPdhmmCross), C.c_int64, C.c_void_p]
     lib.gklhip_pdhmm_compute_cross_batched.restype = C.c_int
+    lib.gklhip_pdhmm_compute_cross_multi.argtypes = [C.c_void_p, C.c_int32, C.POINTER(CPdhmmCross), C.POINTER(C.c_int64),
+                                                     C.POINTER(C.c_void_p), C.POINTER(C.c_int32)]
+    lib.gklhip_pdhmm_compute_cross_multi.restype = C.c_int
+    lib.gklhip_pdhmm_combine_counts.argtypes = [C.c_int, C.POINTER(C.c_int64), C.c_int]
+    lib.gklhip_pdhmm_combine_counts.restype = C.c_int
     lib.gklhip_pdhmm_reference_batch_pairs.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int64]
     lib.gklhip_pdhmm_reference_batch_pairs.restype = C.c_int64
     lib.gklhip_pdhmm_available_memory_mb.argtypes = [C.c_int32]
@@ -501,6 +508,36 @@ def pdhmm_reference_batch_pairs(max_memory_mb: int, max_read_len: int, max_hap_l
 def pdhmm_available_memory_mb(max_memory_mb: int) -> int:
     """min(maxMemoryInMB, free RAM of the host): what the reference's initNative keeps (pdhmm-implementation.h:204-235)."""
     return int(load_pdhmm_library().gklhip_pdhmm_available_memory_mb(max_memory_mb))
+
+
+def pdhmm_combine_counts(device: int = -1, reset: bool = False, lib_path: Optional[str] = None):
+    """(region calls computed, region calls that shared a launch set with another, launch sets) of the cross calls this
+    process computed on `device` (-1: all devices) -- gklhip_pdhmm_combine_counts.  Client contexts count nothing here: the
+    server's counts are pdhmm_server_stats()["combine_counts"]."""
+    lib = load_pdhmm_library(lib_path)
+    out = (C.c_int64 * 3)()
+    st = lib.gklhip_pdhmm_combine_counts(device, out, 1 if reset else 0)
+    if st != OK:
+        _raise_pdhmm(lib, st)
+    return int(out[0]), int(out[1]), int(out[2])
+
+
+class PdhmmMultiError(Exception):
+    """compute_cross_multi: some regions failed.  results[k] is region k's array or None, statuses[k] its status code,
+    errors[k] the exception a single call would have raised (None for a region that succeeded)."""
+
+    def __init__(self, results, statuses, errors):
+        first = next(e for e in errors if e is not None)
+        super().__init__(f"{sum(e is not None for e in errors)} of {len(errors)} regions failed; the first: {first}")
+        self.results, self.statuses, self.errors = results, statuses, errors
+
+
+def _pdhmm_exception(status: int, msg: str):
+    if status == ERR_INVALID_ARG:
+        return IllegalArgumentException(msg)
+    if status == ERR_OOM:
+        return OutOfMemoryError(msg)
+    return RuntimeException(msg)
 
 
 def _raise_pdhmm(lib, status: int):
@@ -590,6 +627,37 @@ class PdhmmContext:
         if st != OK:
             self._raise(st)
         return out
+
+    def compute_cross_multi(self, regions, ref_batch_pairs=None):
+        """Several region calls in one set of launches (gklhip_pdhmm_compute_cross_multi): regions is a list of
+        (reads, haps) as compute_cross takes them, ref_batch_pairs None or one number per region; returns the list of
+        their arrays, each byte for byte what compute_cross returns for it alone.  When regions fail, the others are still
+        computed: PdhmmMultiError carries their arrays and every region's status and exception."""
+        n = len(regions)
+        keep, crosses, outs = [], (CPdhmmCross * max(n, 1))(), []
+        for k, (reads, haps) in enumerate(regions):
+            arrs = [np.ascontiguousarray(a, np.int8) for a in (haps.hap_bases, haps.hap_pdbases, reads.read_bases, reads.read_qual,
+                                                               reads.read_ins_qual, reads.read_del_qual, reads.gcp)]
+            hl = np.ascontiguousarray(haps.hap_lengths, np.int64)
+            rl = np.ascontiguousarray(reads.read_lengths, np.int64)
+            keep.append((arrs, hl, rl))
+            crosses[k] = CPdhmmCross(reads.batch, haps.batch, haps.max_hap_len, reads.max_read_len, *[a.ctypes.data for a in arrs],
+                                     hl.ctypes.data, rl.ctypes.data)
+            outs.append(np.empty(max(reads.batch * haps.batch, 0), np.float64))
+        out_ptrs = (C.c_void_p * max(n, 1))(*[o.ctypes.data for o in outs])
+        rb = None if ref_batch_pairs is None else (C.c_int64 * max(n, 1))(*[int(v) for v in ref_batch_pairs])
+        status = (C.c_int32 * max(n, 1))()
+        st = self.lib.gklhip_pdhmm_compute_cross_multi(self.handle, n, crosses, rb, out_ptrs, status)
+        if st == OK:
+            return outs
+        if n <= 0 or all(status[k] == OK for k in range(n)):
+            self._raise(st)   # the call itself was refused
+        # the library keeps the first failing region's message; the reference has one text per status for the others
+        msg = (self.lib.gklhip_pdhmm_last_error() or b"").decode()
+        first = next(k for k in range(n) if status[k] != OK)
+        errors = [None if status[k] == OK else _pdhmm_exception(status[k], msg if k == first or status[k] == status[first] else
+                                                                f"region {k} failed with status {status[k]}") for k in range(n)]
+        raise PdhmmMultiError([o if status[k] == OK else None for k, o in enumerate(outs)], [int(status[k]) for k in range(n)], errors)
 
     def last_kernel_ms(self) -> float:
         return float(self.lib.gklhip_pdhmm_last_kernel_ms(self.handle))

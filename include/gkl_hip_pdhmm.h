@@ -83,7 +83,8 @@ typedef struct {
   int32_t live_connections;  /* PDHMM connections = PDHMM contexts the server holds */
   int64_t connections_total;
   int64_t pairs_served;      /* pairs of the calls that succeeded */
-  int64_t reserved[9];
+  int64_t combine_counts[3]; /* gklhip_pdhmm_combine_counts of the server process, summed over its devices */
+  int64_t reserved[6];
 } gklhip_pdhmm_server_info;
 int gklhip_pdhmm_server_stats(const char* socket_path, gklhip_pdhmm_server_info* out);
 
@@ -113,6 +114,38 @@ int gklhip_pdhmm_compute_cross(gklhip_pdhmm_ctx* ctx, const gklhip_pdhmm_cross* 
  * initialisation like the reference's getMaxMemoryAvailable (pdhmm-implementation.h:204-235), so that identical calls
  * are cut -- and therefore rounded -- identically.  What the JNI shim's computeLikelihoodsNative calls. */
 int gklhip_pdhmm_compute_cross_batched(gklhip_pdhmm_ctx* ctx, const gklhip_pdhmm_cross* batch, int64_t ref_batch_pairs, double* out_host);
+/* Several region calls in ONE set of launches: region k's output is, byte for byte, what
+ * gklhip_pdhmm_compute_cross_batched(ctx, &regions[k], ref_batch_pairs[k], out_host[k]) writes on the same context -- whichever
+ * other regions ride along, in whatever order, in both fma modes and both tail modes (tail mode 1: every region is cut into
+ * its own reference batches with its own scalar tails).  The regions are planned one by one as single calls are; their
+ * inputs then cross PCIe in one copy, their job tables in another, and the device runs one entries kernel, at most one
+ * launch each of the table, predicate and byte-comparing kernels and one tail launch for all of them; one host
+ * finalisation.  ref_batch_pairs: [n_regions], NULL = all 0.  out_host: [n_regions] pointers, region k's n_reads * n_haps
+ * doubles.  status_out: [n_regions] or NULL.
+ * Returns GKLHIP_OK when every region succeeded, else the status of the first failing region (gklhip_pdhmm_last_error: its
+ * message); the per-region statuses are in status_out and the regions that succeeded have valid results.  The argument
+ * checks of the single call run per region before anything touches the device: a region that fails them is left out and
+ * the rest still run; so does a region with a negative quality (GKLHIP_ERR_INVALID_ARG) -- the others are not affected.  A
+ * HIP failure of the shared launches fails every region in them.
+ * Limits of a shared launch set: 64 regions, 4 MB of inputs at the common row strides (the largest max_read_len /
+ * max_hap_len of the regions), 131 072 pairs in total.  A call over any of them -- and every call on a client context, whose
+ * wire protocol has no multi request -- is computed region by region through the single-call path, with the same results.
+ * Afterwards gklhip_pdhmm_last_routing holds the sums over the regions and gklhip_pdhmm_last_kernel_ms the time of the
+ * shared launches (region by region: the sum of the calls' times). */
+int gklhip_pdhmm_compute_cross_multi(gklhip_pdhmm_ctx* ctx, int32_t n_regions, const gklhip_pdhmm_cross* regions,
+                                     const int64_t* ref_batch_pairs, double* const* out_host, int32_t* status_out);
+/* Process-wide counters of the cross calls computed on `device` by contexts of this process (-1: summed over the devices;
+ * client contexts compute nothing and count nothing): out[0] region calls computed, out[1] region calls that shared a
+ * launch set with another (gklhip_pdhmm_compute_cross_multi with two or more regions in the set; concurrent calls joined
+ * by the combiner), out[2] launch sets.  reset != 0 zeroes them.
+ * The combiner (off by default): with GKL_HIP_PDHMM_COMBINE=1 in the environment of the process that computes, cross calls
+ * that fit the limits above and meet on a device -- the threads of one JVM, the session threads of the server -- leave as
+ * one multi call: the first thread that finds the device's combiner free leads, takes every queued call with its own fma
+ * and tail mode up to the limits and runs them on its context.  GKL_HIP_PDHMM_COMBINE_MIN=k (default 1) with
+ * GKL_HIP_PDHMM_COMBINE_WAIT_US=t (default 0) lets a leader wait up to t microseconds for k calls; the wait is bounded, a
+ * leader whose company does not arrive runs with what it has.  Results are the single call's, byte for byte.  The paired
+ * entry point (gklhip_pdhmm_compute) is never combined. */
+int gklhip_pdhmm_combine_counts(int device, int64_t out[3], int reset);
 int32_t gklhip_pdhmm_available_memory_mb(int32_t max_memory_mb);
 int64_t gklhip_pdhmm_reference_batch_pairs(int32_t max_memory_mb, int32_t max_read_len, int32_t max_hap_len, int64_t total_pairs);
 /* HIP-event time of the forward kernel of the last call, milliseconds. */

@@ -2,13 +2,14 @@
 """P one-caller processes of PDHMM region calls -- the reference's 276 reads x 48 haplotypes holders fixture
 (tests/golden/pdhmm_new.txt) as ONE gklhip_pdhmm_compute_cross_batched call per iteration -- run DIRECTLY (every process
 opens the GPU) and THROUGH ONE SERVER (every process a client: GKL_HIP_SERVER; only the server opens the GPU), on
-device 0, the two arms alternating count by count.  Per arm: aggregate TCUPS, calls per second, median, p99 and slowest
+device 0, and THROUGH ONE SERVER THAT COMBINES concurrent calls into shared launches (GKL_HIP_PDHMM_COMBINE=1 in the server's
+environment; --combine-min / --combine-wait-us set the leader's hold), the three arms alternating count by count.  Per arm: aggregate TCUPS, calls per second, median, p99 and slowest
 call.  Also the per-call cost of one client over one direct caller (the P = 1 rows).
 
 This parent never opens the GPU, and at most 16 processes hold it at once (the server is stopped before the next direct
 arm starts).  Every child runs under its own `timeout`; an arm with a child that exits non-zero ends the script.
 
-usage: tools/pdhmm_server_scaling.py [--counts 1,4,8,16] [--seconds 1.5] [--out FILE]
+usage: tools/pdhmm_server_scaling.py [--counts 1,4,8,16] [--seconds 1.5] [--combine-min K] [--combine-wait-us T] [--out FILE]
 Prints one JSON line per arm; --out FILE also writes the whole record there."""
 import argparse
 import ctypes as C
@@ -105,6 +106,8 @@ def main():
     ap.add_argument("--counts", default="1,4,8,16")
     ap.add_argument("--seconds", type=float, default=1.5)
     ap.add_argument("--out", default="")
+    ap.add_argument("--combine-min", type=int, default=1)
+    ap.add_argument("--combine-wait-us", type=int, default=0)
     ap.add_argument("--child", action="store_true")
     ap.add_argument("--go", default="")
     a = ap.parse_args()
@@ -117,8 +120,13 @@ def main():
         raise SystemExit("at most 16 processes may hold the GPU at once")
     env = dict(os.environ)
     env.pop("GKL_HIP_SERVER", None)
+    for k in [k for k in env if k.startswith("GKL_HIP_PDHMM_COMBINE")]:
+        del env[k]
+    combine_env = dict(env, GKL_HIP_PDHMM_COMBINE="1", GKL_HIP_PDHMM_COMBINE_MIN=str(a.combine_min),
+                       GKL_HIP_PDHMM_COMBINE_WAIT_US=str(a.combine_wait_us))
     tmp = tempfile.mkdtemp(prefix="gklpdsrv")
-    result = {"counts": counts, "seconds": a.seconds, "direct": {}, "server": {}}
+    result = {"counts": counts, "seconds": a.seconds, "direct": {}, "server": {}, "server_combined": {},
+              "combine_min": a.combine_min, "combine_wait_us": a.combine_wait_us}
     for n in counts:
         result["direct"][n] = run_arm(n, a.seconds, env, tmp, f"direct{n}")
         print(json.dumps({"direct": result["direct"][n]}), flush=True)
@@ -133,6 +141,17 @@ def main():
             if h.stop() != 0:
                 raise SystemExit("the server did not stop cleanly")
         print(json.dumps({"server": result["server"][n]}), flush=True)
+        sock = os.path.join(tmp, f"sc{n}.sock")
+        h = server.start(sock, env=combine_env, timeout=120)
+        try:
+            result["server_combined"][n] = run_arm(n, a.seconds, dict(env, GKL_HIP_SERVER=sock), tmp, f"combined{n}")
+            st = h.pdhmm_stats()
+            result["server_combined"][n]["server_calls"] = st["calls_served"]
+            result["server_combined"][n]["combine_counts"] = list(st["combine_counts"])   # calls, calls that shared a launch set, launch sets
+        finally:
+            if h.stop() != 0:
+                raise SystemExit("the server did not stop cleanly")
+        print(json.dumps({"server_combined": result["server_combined"][n]}), flush=True)
     if 1 in counts:
         d, s = result["direct"][1]["p50_ms"], result["server"][1]["p50_ms"]
         result["single_client_per_call_us"] = {"direct_p50_ms": d, "server_p50_ms": s, "overhead_us": round((s - d) * 1e3, 1)}
