@@ -84,7 +84,7 @@ constexpr const char* kRTE = "java/lang/RuntimeException";
 
 // Page-locked byte arena (one per marshalled field and slot): grows with the biggest call, and an arena above 32 MB that the
 // last 16 calls each filled to less than a quarter -- and that has not grown for 64 calls: hipHostFree synchronises the whole
-// device -- is given back (like the context's own buffers, pairhmm_api.hip: trim_due) -- one 1.28 M-pair call must not keep
+// device -- is given back (like the context's own buffers, hip_host_common.h: trim_due) -- one 1.28 M-pair call must not keep
 // ~100 MB pinned per slot for the life of the JVM.  clear() runs at the start of a call, when nothing of the slot's previous
 // call is in flight any more.
 const bool g_client_mode = [] { const char* v = getenv("GKL_HIP_SERVER"); return v && *v; }();   // (read at load)

@@ -8,7 +8,6 @@
 #include <algorithm>
 #include <atomic>
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <mutex>
@@ -25,33 +24,12 @@
 #include "pdhmm_kernel.h"
 #include "pdhmm_remote.h"
 #include "pairhmm_plan.h"
+#include "hip_host_common.h"       // g_err / fail / guarded / HIP_TRY, DevBuf, PinBuf
 #include "pairhmm_host_finalize.h"   // gklhip::WorkerPool: persistent threads for the host log10
 
 using namespace gklhip;
 
 namespace {
-thread_local std::string g_pd_err;
-
-int pd_fail(int status, const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof buf, fmt, ap);
-  va_end(ap);
-  g_pd_err = buf;
-  return status;
-}
-
-#define PD_HIP_TRY(expr)                                                                          \
-  do {                                                                                            \
-    hipError_t e__ = (expr);                                                                      \
-    if (e__ != hipSuccess) {                                                                      \
-      (void)hipGetLastError();                                                                    \
-      return pd_fail(e__ == hipErrorOutOfMemory ? GKLHIP_ERR_OOM : GKLHIP_ERR_HIP, "%s: %s", #expr, \
-                     hipGetErrorString(e__));                                                     \
-    }                                                                                             \
-  } while (0)
-
 // ---- host tables: ProbabilityCache of pdhmm-common.h:139-192 (exact 1/ln10 here, unlike PairHMM) ----
 constexpr int kPdMaxQual = 254;
 constexpr int kPdMmSize = ((kPdMaxQual + 1) * (kPdMaxQual + 2)) >> 1;
@@ -89,51 +67,6 @@ const PdTables& pd_tables() {
   return t;
 }
 
-// (like libgklhip_pairhmm's buffers: grown by the biggest call, given back when the last 16 calls each needed less than a
-//  quarter of a buffer above 32 MB -- a 424k-pair call holds ~3 GB of streams and tables -- but not within 64 calls of the
-//  buffer's last growth: hipFree / hipHostFree synchronise the whole device, and a workload that alternates one big call
-//  with a few small ones must not free and re-make its buffers every round)
-constexpr int kPdTrimCalls = 16, kPdTrimQuiet = 64;
-inline bool pd_trim_due(size_t n, size_t cap, int* small_uses, int* since_grow) {
-  if (*since_grow < kPdTrimQuiet) ++*since_grow;
-  if (cap <= ((size_t)32 << 20) || n >= cap / 4) { *small_uses = 0; return false; }
-  if (*small_uses < kPdTrimCalls) ++*small_uses;
-  return *small_uses >= kPdTrimCalls && *since_grow >= kPdTrimQuiet;
-}
-struct Buf {
-  void* p = nullptr;
-  size_t cap = 0;
-  int small_uses = 0, since_grow = kPdTrimQuiet;
-  int reserve(size_t n) {
-    if (n <= cap && !pd_trim_due(n, cap, &small_uses, &since_grow)) return GKLHIP_OK;
-    if (n > cap) since_grow = 0;
-    small_uses = 0;
-    if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
-    const size_t want = n + n / 4 + 256;
-    PD_HIP_TRY(hipMalloc(&p, want));
-    cap = want;
-    return GKLHIP_OK;
-  }
-  void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-  template <typename T> T* as() const { return static_cast<T*>(p); }
-};
-struct PinBuf {  // page-locked host memory
-  void* p = nullptr;
-  size_t cap = 0;
-  int small_uses = 0, since_grow = kPdTrimQuiet;
-  int reserve(size_t n) {
-    if (n <= cap && !pd_trim_due(n, cap, &small_uses, &since_grow)) return GKLHIP_OK;
-    if (n > cap) since_grow = 0;
-    small_uses = 0;
-    if (p) { (void)hipHostFree(p); p = nullptr; cap = 0; }
-    const size_t want = n + n / 4 + 256;
-    PD_HIP_TRY(hipHostMalloc(&p, want, hipHostMallocDefault));
-    cap = want;
-    return GKLHIP_OK;
-  }
-  void release() { if (p) (void)hipHostFree(p); p = nullptr; cap = 0; }
-  template <typename T> T* as() const { return static_cast<T*>(p); }
-};
 }  // namespace
 
 struct gklhip_pdhmm_ctx {
@@ -152,7 +85,7 @@ struct gklhip_pdhmm_ctx {
   hipEvent_t up_ev[kMaxSlices] = {}, sl_ev0[kMaxSlices] = {}, sl_ev1[kMaxSlices] = {};
   int pipeline = 1;                     // GKL_HIP_PDHMM_PIPELINE=0: one slice whatever the size
   std::mutex mu;
-  Buf tables, inputs, entries, entries_tab, sums, misc, carry, jobs, tabx;
+  DevBuf tables, inputs, entries, entries_tab, sums, misc, carry, jobs, tabx;
   PackScratch pack_scratch;
   PinBuf stage_in, stage_jobs, sums_pin;   // small calls: ONE copy per device buffer instead of one per array (9 + 17 of them)
   float last_ms = 0.f;
@@ -162,9 +95,28 @@ struct gklhip_pdhmm_ctx {
   int tail_mode = 1; // 1 (default) = the last `batch mod SIMD width` pairs of every reference batch take the scalar engine's arithmetic, like GKL; 0 = vector arithmetic everywhere
 };
 
+namespace {
+// The fence around a launch path (pd_run_locked, pd_run_multi_locked; c->mu is held).  No C++ exception leaves the C ABI
+// (a host vector that cannot grow, a helper thread that cannot start): it becomes a status like any other error.  An error
+// return must not leave asynchronous copies from the call's host vectors (or the caller's arrays) in flight when those go
+// out of scope: both streams are drained first (a multi-region call never uses up_stream: idle there, the wait returns at once).
+template <typename F>
+int pd_fenced(gklhip_pdhmm_ctx* c, F&& launch_path) {
+  const int rc = guarded(launch_path);
+  if (rc != GKLHIP_OK) {
+    const std::string keep = g_err;
+    if (c->stream) (void)hipStreamSynchronize(c->stream);
+    if (c->up_stream) (void)hipStreamSynchronize(c->up_stream);
+    (void)hipGetLastError();
+    g_err = keep;
+  }
+  return rc;
+}
+}  // namespace
+
 extern "C" {
 
-const char* gklhip_pdhmm_last_error(void) { return g_pd_err.c_str(); }
+const char* gklhip_pdhmm_last_error(void) { return g_err.c_str(); }
 
 int64_t gklhip_pdhmm_get_table(int which, double* dst, int64_t cap) {
   const PdTables& t = pd_tables();
@@ -183,15 +135,15 @@ int pd_tail_mode_from_env() {
 }  // namespace
 
 int gklhip_pdhmm_connect(const char* socket_path, int device, gklhip_pdhmm_ctx** out_ctx) {
-  if (!out_ctx) return pd_fail(GKLHIP_ERR_INVALID_ARG, "out_ctx is NULL");
+  if (!out_ctx) return fail(GKLHIP_ERR_INVALID_ARG, "out_ctx is NULL");
   *out_ctx = nullptr;
   gklhip_pdhmm_ctx* c = new (std::nothrow) gklhip_pdhmm_ctx();
-  if (!c) return pd_fail(GKLHIP_ERR_OOM, "context allocation failed");
+  if (!c) return fail(GKLHIP_ERR_OOM, "context allocation failed");
   std::string err;
   int rc;
   try { rc = gklhip_pd_remote::connect(socket_path, device, &c->remote, &err); }
   catch (...) { rc = GKLHIP_ERR_OOM; err = "host memory allocation failed"; }
-  if (rc != GKLHIP_OK) { delete c; return pd_fail(rc, "%s", err.c_str()); }
+  if (rc != GKLHIP_OK) { delete c; return fail(rc, "%s", err.c_str()); }
   c->device = device;
   c->tail_mode = pd_tail_mode_from_env();
   *out_ctx = c;
@@ -201,49 +153,49 @@ int gklhip_pdhmm_connect(const char* socket_path, int device, gklhip_pdhmm_ctx**
 int gklhip_pdhmm_is_remote(gklhip_pdhmm_ctx* c) { return c && c->remote ? 1 : 0; }
 
 int gklhip_pdhmm_server_stats(const char* socket_path, gklhip_pdhmm_server_info* out) {
-  if (!out) return pd_fail(GKLHIP_ERR_INVALID_ARG, "NULL argument");
+  if (!out) return fail(GKLHIP_ERR_INVALID_ARG, "NULL argument");
   std::string err;
   int rc;
   try { rc = gklhip_pd_remote::server_stats(socket_path, out, &err); }
   catch (...) { rc = GKLHIP_ERR_OOM; err = "host memory allocation failed"; }
-  return rc == GKLHIP_OK ? rc : pd_fail(rc, "%s", err.c_str());
+  return rc == GKLHIP_OK ? rc : fail(rc, "%s", err.c_str());
 }
 
 int gklhip_pdhmm_init(int device, gklhip_pdhmm_ctx** out_ctx) {
   // GKL_HIP_SERVER=PATH: every context of the process is a client context of the server on PATH
   if (const char* path = getenv("GKL_HIP_SERVER"))
     if (*path) return gklhip_pdhmm_connect(path, device, out_ctx);
-  if (!out_ctx) return pd_fail(GKLHIP_ERR_INVALID_ARG, "out_ctx is NULL");
+  if (!out_ctx) return fail(GKLHIP_ERR_INVALID_ARG, "out_ctx is NULL");
   *out_ctx = nullptr;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
     (void)hipGetLastError();
-    return pd_fail(GKLHIP_ERR_NO_DEVICE, "no HIP device visible (this library has no CPU compute path)");
+    return fail(GKLHIP_ERR_NO_DEVICE, "no HIP device visible (this library has no CPU compute path)");
   }
-  if (device < 0) PD_HIP_TRY(hipGetDevice(&device));
-  if (device >= ndev) return pd_fail(GKLHIP_ERR_INVALID_ARG, "device %d of %d", device, ndev);
-  PD_HIP_TRY(hipSetDevice(device));
+  if (device < 0) HIP_TRY(hipGetDevice(&device));
+  if (device >= ndev) return fail(GKLHIP_ERR_INVALID_ARG, "device %d of %d", device, ndev);
+  HIP_TRY(hipSetDevice(device));
   hipDeviceProp_t prop;
-  PD_HIP_TRY(hipGetDeviceProperties(&prop, device));
+  HIP_TRY(hipGetDeviceProperties(&prop, device));
   if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-    return pd_fail(GKLHIP_ERR_NO_DEVICE, "device %d is %s; this library is built for gfx950 only", device, prop.gcnArchName);
+    return fail(GKLHIP_ERR_NO_DEVICE, "device %d is %s; this library is built for gfx950 only", device, prop.gcnArchName);
   gklhip_pdhmm_ctx* c = new (std::nothrow) gklhip_pdhmm_ctx();
-  if (!c) return pd_fail(GKLHIP_ERR_OOM, "context allocation failed");
+  if (!c) return fail(GKLHIP_ERR_OOM, "context allocation failed");
   c->device = device;
   auto bail = [&](int st) { gklhip_pdhmm_done(c); return st; };
-  if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) return bail(pd_fail(GKLHIP_ERR_HIP, "hipStreamCreate failed"));
-  if (hipEventCreate(&c->ev0) != hipSuccess || hipEventCreate(&c->ev1) != hipSuccess) return bail(pd_fail(GKLHIP_ERR_HIP, "hipEventCreate failed"));
-  if (hipStreamCreateWithFlags(&c->up_stream, hipStreamNonBlocking) != hipSuccess) return bail(pd_fail(GKLHIP_ERR_HIP, "hipStreamCreate failed"));
+  if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) return bail(fail(GKLHIP_ERR_HIP, "hipStreamCreate failed"));
+  if (hipEventCreate(&c->ev0) != hipSuccess || hipEventCreate(&c->ev1) != hipSuccess) return bail(fail(GKLHIP_ERR_HIP, "hipEventCreate failed"));
+  if (hipStreamCreateWithFlags(&c->up_stream, hipStreamNonBlocking) != hipSuccess) return bail(fail(GKLHIP_ERR_HIP, "hipStreamCreate failed"));
   for (int k = 0; k < gklhip_pdhmm_ctx::kMaxSlices; k++)
     if (hipEventCreateWithFlags(&c->up_ev[k], hipEventDisableTiming) != hipSuccess || hipEventCreate(&c->sl_ev0[k]) != hipSuccess ||
         hipEventCreate(&c->sl_ev1[k]) != hipSuccess)
-      return bail(pd_fail(GKLHIP_ERR_HIP, "hipEventCreate failed"));
+      return bail(fail(GKLHIP_ERR_HIP, "hipEventCreate failed"));
   const PdTables& t = pd_tables();
   int rc = c->tables.reserve((t.q2err.size() + t.mm.size()) * sizeof(double));
   if (rc) return bail(rc);
   if (hipMemcpy(c->tables.p, t.q2err.data(), t.q2err.size() * 8, hipMemcpyHostToDevice) != hipSuccess ||
       hipMemcpy(c->tables.as<double>() + t.q2err.size(), t.mm.data(), t.mm.size() * 8, hipMemcpyHostToDevice) != hipSuccess)
-    return bail(pd_fail(GKLHIP_ERR_HIP, "table upload failed"));
+    return bail(fail(GKLHIP_ERR_HIP, "table upload failed"));
   {
     c->tail_mode = pd_tail_mode_from_env();
     const char* tb = getenv("GKL_HIP_PDHMM_TABLE");
@@ -261,7 +213,7 @@ int gklhip_pdhmm_init(int device, gklhip_pdhmm_ctx** out_ctx) {
     if (checked[(size_t)device] == 0) {
       uint32_t* d_out = nullptr;
       uint32_t h_out = 1u;
-      if (hipMalloc(reinterpret_cast<void**>(&d_out), 4) != hipSuccess) return bail(pd_fail(GKLHIP_ERR_OOM, "hipMalloc failed"));
+      if (hipMalloc(reinterpret_cast<void**>(&d_out), 4) != hipSuccess) return bail(fail(GKLHIP_ERR_OOM, "hipMalloc failed"));
       bool ok = hipMemsetAsync(d_out, 0, 4, c->stream) == hipSuccess;
       hipLaunchKernelGGL(pdhmm_idle_class_selftest_kernel, dim3(64), dim3(64), 0, c->stream, d_out);
       ok = ok && hipMemcpyAsync(&h_out, d_out, 4, hipMemcpyDeviceToHost, c->stream) == hipSuccess && hipStreamSynchronize(c->stream) == hipSuccess;
@@ -277,8 +229,8 @@ int gklhip_pdhmm_init(int device, gklhip_pdhmm_ctx** out_ctx) {
 }
 
 int gklhip_pdhmm_set_tail_mode(gklhip_pdhmm_ctx* c, int mode) {
-  if (!c) return pd_fail(GKLHIP_ERR_INVALID_ARG, "context is NULL");
-  if (mode != 0 && mode != 1) return pd_fail(GKLHIP_ERR_INVALID_ARG, "tail mode %d (0 or 1)", mode);
+  if (!c) return fail(GKLHIP_ERR_INVALID_ARG, "context is NULL");
+  if (mode != 0 && mode != 1) return fail(GKLHIP_ERR_INVALID_ARG, "tail mode %d (0 or 1)", mode);
   std::lock_guard<std::mutex> lock(c->mu);
   c->tail_mode = mode;
   return GKLHIP_OK;
@@ -298,7 +250,7 @@ int gklhip_pdhmm_done(gklhip_pdhmm_ctx* c) {
     for (hipEvent_t e : {c->up_ev[k], c->sl_ev0[k], c->sl_ev1[k]})
       if (e) (void)hipEventDestroy(e);
   if (c->up_stream) (void)hipStreamDestroy(c->up_stream);
-  for (Buf* b : {&c->tables, &c->inputs, &c->entries, &c->entries_tab, &c->sums, &c->misc, &c->carry, &c->jobs, &c->tabx}) b->release();
+  for (DevBuf* b : {&c->tables, &c->inputs, &c->entries, &c->entries_tab, &c->sums, &c->misc, &c->carry, &c->jobs, &c->tabx}) b->release();
   for (PinBuf* b : {&c->stage_in, &c->stage_jobs, &c->sums_pin}) b->release();
   if (c->ev0) (void)hipEventDestroy(c->ev0);
   if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -308,8 +260,8 @@ int gklhip_pdhmm_done(gklhip_pdhmm_ctx* c) {
 }
 
 int gklhip_pdhmm_set_fma_mode(gklhip_pdhmm_ctx* c, int fma_mode) {
-  if (!c) return pd_fail(GKLHIP_ERR_INVALID_ARG, "context is NULL");
-  if (fma_mode != 0 && fma_mode != 1) return pd_fail(GKLHIP_ERR_INVALID_ARG, "fma_mode %d (0 or 1)", fma_mode);
+  if (!c) return fail(GKLHIP_ERR_INVALID_ARG, "context is NULL");
+  if (fma_mode != 0 && fma_mode != 1) return fail(GKLHIP_ERR_INVALID_ARG, "fma_mode %d (0 or 1)", fma_mode);
   std::lock_guard<std::mutex> lock(c->mu);
   c->fma_mode = fma_mode;
   return GKLHIP_OK;
@@ -321,12 +273,12 @@ int64_t gklhip_pdhmm_buffer_bytes(gklhip_pdhmm_ctx* c) {
   std::lock_guard<std::mutex> lock(c->mu);
   if (c->remote) return (int64_t)gklhip_pd_remote::arena_bytes(c->remote);
   size_t total = 0;
-  for (const Buf* b : {&c->tables, &c->inputs, &c->entries, &c->entries_tab, &c->sums, &c->misc, &c->carry, &c->jobs, &c->tabx}) total += b->cap;
+  for (const DevBuf* b : {&c->tables, &c->inputs, &c->entries, &c->entries_tab, &c->sums, &c->misc, &c->carry, &c->jobs, &c->tabx}) total += b->cap;
   for (const PinBuf* b : {&c->stage_in, &c->stage_jobs, &c->sums_pin}) total += b->cap;
   return (int64_t)total;
 }
 int gklhip_pdhmm_last_routing(gklhip_pdhmm_ctx* c, int32_t out[3]) {
-  if (!c || !out) return pd_fail(GKLHIP_ERR_INVALID_ARG, "NULL argument");
+  if (!c || !out) return fail(GKLHIP_ERR_INVALID_ARG, "NULL argument");
   std::lock_guard<std::mutex> lock(c->mu);
   for (int i = 0; i < 3; i++) out[i] = c->last_routing[i];
   return GKLHIP_OK;
@@ -347,18 +299,29 @@ struct PdProblem {
 
 int pd_validate(const PdProblem& q, const double* out_host) {
   if (q.max_hap_len <= 0 || q.max_read_len <= 0)
-    return pd_fail(GKLHIP_ERR_INVALID_ARG, "maxHapLength / maxReadLength must be greater than 0");
+    return fail(GKLHIP_ERR_INVALID_ARG, "maxHapLength / maxReadLength must be greater than 0");
   if (!q.hap_bases || !q.hap_pdbases || !q.read_bases || !q.read_qual || !q.read_ins_qual || !q.read_del_qual ||
       !q.gcp || !q.hap_lengths || !q.read_lengths || !out_host)
-    return pd_fail(GKLHIP_ERR_INVALID_ARG, "Input arrays aren't valid.");
-  if (q.n_pairs > 0x7fffffffLL) return pd_fail(GKLHIP_ERR_INVALID_ARG, "more than 2^31 pairs");
+    return fail(GKLHIP_ERR_INVALID_ARG, "Input arrays aren't valid.");
+  if (q.n_pairs > 0x7fffffffLL) return fail(GKLHIP_ERR_INVALID_ARG, "more than 2^31 pairs");
   for (int i = 0; i < q.n_hap_items; i++)
     if (q.hap_lengths[i] < 1 || q.hap_lengths[i] > q.max_hap_len)
-      return pd_fail(GKLHIP_ERR_INVALID_ARG, "hap_lengths[%d] = %lld outside 1..%d", i, (long long)q.hap_lengths[i], q.max_hap_len);
+      return fail(GKLHIP_ERR_INVALID_ARG, "hap_lengths[%d] = %lld outside 1..%d", i, (long long)q.hap_lengths[i], q.max_hap_len);
   for (int i = 0; i < q.n_read_items; i++)
     if (q.read_lengths[i] < 1 || q.read_lengths[i] > q.max_read_len)
-      return pd_fail(GKLHIP_ERR_INVALID_ARG, "read_lengths[%d] = %lld outside 1..%d", i, (long long)q.read_lengths[i], q.max_read_len);
+      return fail(GKLHIP_ERR_INVALID_ARG, "read_lengths[%d] = %lld outside 1..%d", i, (long long)q.read_lengths[i], q.max_read_len);
   return GKLHIP_OK;
+}
+
+// One cross call's arguments (gklhip_pdhmm_compute_cross_batched; a region of _compute_cross_multi) as a checked problem.
+int pd_cross_problem(const gklhip_pdhmm_cross* x, int64_t ref_batch_pairs, const double* out_host, PdProblem* q) {
+  if (ref_batch_pairs < 0) return fail(GKLHIP_ERR_INVALID_ARG, "ref_batch_pairs must not be negative");
+  if (!x) return fail(GKLHIP_ERR_INVALID_ARG, "batch is NULL");
+  if (x->n_reads <= 0 || x->n_haps <= 0) return fail(GKLHIP_ERR_INVALID_ARG, "no pairs to process");
+  *q = PdProblem{(int64_t)x->n_reads * x->n_haps, x->n_reads, x->n_haps, x->n_haps, x->max_hap_len, x->max_read_len,
+                 x->hap_bases, x->hap_pdbases, x->read_bases, x->read_qual, x->read_ins_qual, x->read_del_qual, x->gcp,
+                 x->hap_lengths, x->read_lengths, ref_batch_pairs};
+  return pd_validate(*q, out_host);
 }
 
 int pd_run_locked(gklhip_pdhmm_ctx* c, const PdProblem& q, double* out_host);
@@ -390,8 +353,6 @@ bool has_odd_base(const int8_t* b, int64_t n) {
   return avx2 ? has_odd_base_avx2(b, n) : has_odd_base_scalar(b, n);
 }
 
-// An error return must not leave asynchronous copies from this call's host vectors (or the caller's arrays) in
-// flight when those go out of scope: drain the stream first.
 // A client context: the checked call goes to the server, which answers with its context's kernel time and routing.
 int pd_run_remote(gklhip_pdhmm_ctx* c, const PdProblem& q, double* out_host) {
   const gklhip_pd_remote::Call call{q.cross_haps ? 1 : 0, q.n_read_items, q.n_hap_items, q.max_hap_len, q.max_read_len,
@@ -403,7 +364,7 @@ int pd_run_remote(gklhip_pdhmm_ctx* c, const PdProblem& q, double* out_host) {
   int rc;
   try { rc = gklhip_pd_remote::compute(c->remote, call, out_host, &rep, &err); }
   catch (...) { rc = GKLHIP_ERR_OOM; err = "host memory allocation failed"; }
-  if (rc != GKLHIP_OK) return pd_fail(rc, "%s", err.c_str());
+  if (rc != GKLHIP_OK) return fail(rc, "%s", err.c_str());
   c->last_ms = rep.kernel_ms;
   for (int i = 0; i < 3; i++) c->last_routing[i] = rep.routing[i];
   return GKLHIP_OK;
@@ -412,28 +373,30 @@ int pd_run_remote(gklhip_pdhmm_ctx* c, const PdProblem& q, double* out_host) {
 int pd_run(gklhip_pdhmm_ctx* c, const PdProblem& q, double* out_host) {
   std::lock_guard<std::mutex> lock(c->mu);
   if (c->remote) return pd_run_remote(c, q, out_host);
-  int rc;
-  // no C++ exception leaves the C ABI (a host vector that cannot grow, a helper thread that cannot start): it becomes a
-  // status like any other error -- after the same drain
-  try { rc = pd_run_locked(c, q, out_host); }
-  catch (const std::bad_alloc&) { rc = pd_fail(GKLHIP_ERR_OOM, "host memory allocation failed"); }
-  catch (const std::exception& e) { rc = pd_fail(GKLHIP_ERR_HIP, "%s", e.what()); }
-  catch (...) { rc = pd_fail(GKLHIP_ERR_HIP, "unexpected C++ exception"); }
-  if (rc != GKLHIP_OK) {
-    const std::string keep = g_pd_err;
-    if (c->stream) (void)hipStreamSynchronize(c->stream);
-    if (c->up_stream) (void)hipStreamSynchronize(c->up_stream);
-    (void)hipGetLastError();
-    g_pd_err = keep;
-  }
-  return rc;
+  return pd_fenced(c, [&] { return pd_run_locked(c, q, out_host); });
 }
 
 constexpr size_t kPdStageBytes = (size_t)4 << 20;
 // misc: 64 int32 of flags and job counters (the first 256 bytes, cleared by every call), then the per-region input-error
 // flags of a multi-region call
 constexpr size_t kPdMiscBytes = 256 + 4 * (size_t)kPdMaxRegions;
-constexpr size_t kPdMultiMaxPairs = 131072;   // a multi-region call's sums go straight into pinned memory (sums_direct)
+// Up to this many pairs (1 MB of sums) the kernels store the sums straight into pinned host memory (pd_run_locked:
+// sums_direct).  A multi-region call has no other way to return them, so this is also the most pairs it takes: both
+// paths depend on the one constant.
+constexpr size_t kPdMultiMaxPairs = 131072;
+inline size_t pd_up(size_t x) { return (x + 255) / 256 * 256; }
+// The nine input arrays of a call (of a multi-region call: of all its regions, at the common row strides) in ONE block,
+// each 256-byte aligned: the layout of the device buffer `inputs` and of the pinned block `stage_in`, and the size that
+// decides whether a call is staged (kPdStageBytes) or fits a multi-region launch set.
+struct PdInputLayout {
+  size_t hap_bytes, read_bytes;
+  size_t o_hb, o_hp, o_rb, o_rq, o_ri, o_rd, o_gc, o_hl, o_rl, total;
+  PdInputLayout(size_t n_hap_items, size_t n_read_items, size_t max_hap_len, size_t max_read_len)
+      : hap_bytes(n_hap_items * max_hap_len), read_bytes(n_read_items * max_read_len),
+        o_hb(0), o_hp(pd_up(hap_bytes)), o_rb(o_hp + pd_up(hap_bytes)), o_rq(o_rb + pd_up(read_bytes)), o_ri(o_rq + pd_up(read_bytes)),
+        o_rd(o_ri + pd_up(read_bytes)), o_gc(o_rd + pd_up(read_bytes)), o_hl(o_gc + pd_up(read_bytes)),
+        o_rl(o_hl + pd_up(n_hap_items * 8)), total(o_rl + pd_up(n_read_items * 8)) {}
+};
 // Cross layout: reads are packed into 64-lane chunks by best fit within windows of this many reads.  The chunks are reused
 // for every haplotype, so a fuller chunk pays off nh times: 2048 fills 99.2 % of the lanes on the reference's fixture
 // (192, the paired layout's window: 97.7 %).
@@ -455,16 +418,28 @@ struct PdCrossPlan {
   size_t n_clean_haps = 0, n_tab_haps = 0;
 };
 
+// Appends the reference-tail job of one pair: a job of its own for the scalar-arithmetic launch (a lane row of the pair's
+// row blocks, or a striped job when the read needs more than 64 lanes).
+void pd_push_tail_job(PdCrossPlan* plan, int32_t pair, int read_len, int hap_len) {
+  const int nb = blocks_for(read_len, kPdRpl);
+  plan->tail_pair.push_back(pair);
+  plan->tail_striped.push_back(nb > kLanes ? 1 : 0);
+  plan->tail_steps.push_back(hap_len + std::min(nb, kLanes) - 1);
+  plan->tail_lanes.resize(plan->tail_lanes.size() + kLanes, PlanLane{-1, 0});
+  if (nb <= kLanes)
+    for (int b = 0; b < nb; b++) plan->tail_lanes[plan->tail_lanes.size() - kLanes + (size_t)b] = PlanLane{pair, b};
+  plan->n_tail = plan->tail_pair.size();
+}
+
 void pd_plan_cross_jobs(gklhip_pdhmm_ctx* c, const PdProblem& q, PdCrossPlan* plan) {
   const size_t n = (size_t)q.n_pairs, nh = (size_t)q.n_hap_items, nr = (size_t)q.n_read_items;
   const int cross = q.cross_haps;
   auto read_len_of = [&](size_t p) { return (int)q.read_lengths[p / (size_t)cross]; };
   auto hap_len_of = [&](size_t p) { return (int)q.hap_lengths[p % (size_t)cross]; };
   auto &job_pair = plan->job_pair, &job_steps = plan->job_steps, &hap_order = plan->hap_order, &chunk_steps = plan->chunk_steps,
-       &chunk_rep = plan->chunk_rep, &tail_pair = plan->tail_pair, &tail_steps = plan->tail_steps;
-  auto &job_striped = plan->job_striped, &tail_striped = plan->tail_striped;
-  auto &cross_lanes = plan->cross_lanes, &tail_lanes = plan->tail_lanes;
-  size_t& n_tail = plan->n_tail;
+       &chunk_rep = plan->chunk_rep;
+  auto& job_striped = plan->job_striped;
+  auto& cross_lanes = plan->cross_lanes;
   // reads are packed into 64-lane chunks ONCE; every chunk meets every haplotype (longest haplotypes first).
   std::vector<int64_t> read_off(nr + 1, 0);
   for (size_t r = 0; r < nr; r++) read_off[r + 1] = read_off[r] + q.read_lengths[r];
@@ -503,17 +478,9 @@ void pd_plan_cross_jobs(gklhip_pdhmm_ctx* c, const PdProblem& q, PdCrossPlan* pl
     const size_t per = q.ref_batch_pairs > 0 ? (size_t)std::min<int64_t>(q.ref_batch_pairs, (int64_t)n) : n;
     for (size_t start = 0; start < n; start += per) {
       const size_t nb_pairs = std::min(per, n - start);
-      for (size_t i = start + nb_pairs / width * width; i < start + nb_pairs; i++) {
-        const int nb = blocks_for(read_len_of(i), kPdRpl);
-        tail_pair.push_back((int32_t)i);
-        tail_striped.push_back(nb > kLanes ? 1 : 0);
-        tail_steps.push_back(hap_len_of(i) + std::min(nb, kLanes) - 1);
-        tail_lanes.resize(tail_lanes.size() + kLanes, PlanLane{-1, 0});
-        if (nb <= kLanes)
-          for (int b = 0; b < nb; b++) tail_lanes[tail_lanes.size() - kLanes + (size_t)b] = PlanLane{(int32_t)i, b};
-      }
+      for (size_t i = start + nb_pairs / width * width; i < start + nb_pairs; i++)
+        pd_push_tail_job(plan, (int32_t)i, read_len_of(i), hap_len_of(i));
     }
-    n_tail = tail_pair.size();
   }
 }
 
@@ -591,21 +558,125 @@ void pd_plan_cross_routing(gklhip_pdhmm_ctx* c, const PdProblem& q, PdCrossPlan*
   }
 }
 
+// Table launch: a unit of work is (a group of consecutive table haplotypes of ONE region, a chunk of reads) -- the wavefront
+// sets the chunk's rows up once per group (a twelfth of a job's time otherwise).  Groups of up to six while the launch has at
+// least six units per wavefront -- sized by the units of the WHOLE launch: many small regions together fill the device, so
+// they get the full groups a single one would not -- shrinking to single haplotypes over the last part of the launch's list
+// (they run last and even the load out).  n_tab_haps[k]: the table haplotypes of region k (a single call: one count);
+// n_cross_tab: the launch's (haplotype, chunk) jobs.  Fills tab_group_start (`start`, empty before) -- group g = entries
+// [start[g], start[g + 1]) of the launch's haplotype list -- and groups[k], when asked for: the number of region k's groups.
+void pd_size_tab_groups(const size_t* n_tab_haps, int K, int64_t n_cross_tab, std::vector<int32_t>* start, int32_t* groups) {
+  const int64_t per_wave = n_cross_tab / (256 * 8);
+  const size_t group_max = (size_t)std::max<int64_t>(1, std::min<int64_t>(6, per_wave / 6));
+  size_t left = 0, at = 0;
+  for (int k = 0; k < K; k++) left += n_tab_haps[k];
+  for (int k = 0; k < K; k++) {
+    const size_t mine = n_tab_haps[k];
+    int32_t made = 0;
+    for (size_t i = 0; i < mine; made++) {
+      const size_t g = std::max<size_t>(1, std::min(std::min(group_max, left / 7), mine - i));
+      start->push_back((int32_t)(at + i));
+      i += g; left -= g;
+    }
+    at += mine;
+    if (groups) groups[k] = made;
+  }
+  start->push_back((int32_t)at);
+}
+
+// Where the job tables that both launch paths keep in the device buffer `jobs` start (each path lays its own block out).
+struct PdJobOffsets { size_t jl, jp, jn, js, cl, cs, cr, nc, cc, jf, fj, tg; };
+
+// The kernel arguments that a single call and a multi-region call set the same way: the input arrays, the tables, the
+// entry streams, the carry rows and the job tables of PdJobOffsets.  Everything else is 0 / NULL for the caller to set.
+PdArgs pd_common_args(gklhip_pdhmm_ctx* c, const PdInputLayout& in, const PdJobOffsets& o, size_t n_hap_items, int32_t max_hap,
+                      int32_t max_read, int entry_stride, bool table_haps) {
+  unsigned char *d = c->inputs.as<unsigned char>(), *dj = c->jobs.as<unsigned char>();
+  PdArgs a;
+  memset(&a, 0, sizeof a);
+  a.hap_bases = reinterpret_cast<const int8_t*>(d + in.o_hb);
+  a.hap_pdbases = reinterpret_cast<const int8_t*>(d + in.o_hp);
+  a.read_bases = reinterpret_cast<const int8_t*>(d + in.o_rb);
+  a.read_qual = reinterpret_cast<const int8_t*>(d + in.o_rq);
+  a.read_ins = reinterpret_cast<const int8_t*>(d + in.o_ri);
+  a.read_del = reinterpret_cast<const int8_t*>(d + in.o_rd);
+  a.gcp = reinterpret_cast<const int8_t*>(d + in.o_gc);
+  a.hap_len = reinterpret_cast<const int64_t*>(d + in.o_hl);
+  a.read_len = reinterpret_cast<const int64_t*>(d + in.o_rl);
+  a.max_hap = max_hap; a.max_read = max_read;
+  a.n_hap_items = (int32_t)n_hap_items;
+  a.q2err = c->tables.as<double>();
+  a.mm_prob = c->tables.as<double>() + pd_tables().q2err.size();
+  a.entries = c->entries.as<uint32_t>();
+  a.entry_stride = entry_stride;
+  a.next = c->misc.as<int32_t>() + 1;
+  a.carry = c->carry.as<double>();
+  a.carry_len = entry_stride;
+  a.lanes = reinterpret_cast<const LaneSlot*>(dj + o.jl);
+  a.job_pair = reinterpret_cast<const int32_t*>(dj + o.jp);
+  a.job_steps = reinterpret_cast<const int32_t*>(dj + o.jn);
+  a.job_striped = dj + o.js;
+  a.cross_lanes = reinterpret_cast<const LaneSlot*>(dj + o.cl);
+  a.chunk_steps = reinterpret_cast<const int32_t*>(dj + o.cs);
+  a.chunk_rep = reinterpret_cast<const int32_t*>(dj + o.cr);
+  a.hap_ncls = table_haps ? dj + o.nc : nullptr;
+  a.class_codes = reinterpret_cast<const uint32_t*>(dj + o.cc);
+  a.entries_tab = c->entries_tab.as<uint32_t>();
+  a.next_special = table_haps ? reinterpret_cast<int32_t*>(c->entries_tab.as<uint32_t>() + n_hap_items * (size_t)entry_stride) : nullptr;
+  a.tab_group_start = reinterpret_cast<const int32_t*>(dj + o.tg);
+  a.job_flags = dj + o.jf;
+  a.full_jobs = reinterpret_cast<const int32_t*>(dj + o.fj);
+  a.sb_stride = entry_stride / 64; a.ns_stride = entry_stride;
+#ifdef GKL_PD_PROF
+  a.prof = reinterpret_cast<unsigned long long*>(c->misc.as<char>() + 128);
+#endif
+  return a;
+}
+
+// One forward launch of 64-lane blocks in the context's arithmetic: the FMA instantiation of a kernel or its plain twin.
+using PdFwdKernel = void (*)(PdArgs, double);
+void pd_launch_fwd(const gklhip_pdhmm_ctx* c, PdFwdKernel k_fma, PdFwdKernel k_plain, int blocks, hipStream_t s, const PdArgs& a) {
+  const PdFwdKernel k = c->fma_mode ? k_fma : k_plain;
+  hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(64), 0, s, a, pd_tables().initial_condition);
+}
+
+// log10 of the sums with the HOST libm, like the reference (pdhmm.h:846) -- a region's 13 248 pairs are 0.13 ms of it on
+// one thread, three quarters of what the call costs beyond its kernels: four threads from 4096 pairs on (persistent
+// workers: a thread per call would cost more than it saves).  The pairs of K regions (a single call: one) lie behind one
+// another in `sums`, region k from regions[k].pair_base on (regions[K]: the total); its values go to out[k], unless
+// flags[k] says that its inputs were bad: that output stays untouched.
+int pd_finalise(gklhip_pdhmm_ctx* c, const double* sums, const PdRegion* regions, int K, double* const* out, const int32_t* flags) {
+  const double scale_log10 = pd_tables().initial_condition_log10;
+  const std::function<void(int64_t, int64_t)> finalise = [&](int64_t lo, int64_t hi) {
+    for (int k = pd_region_of_pair(regions, K, (int)lo); lo < hi; k++) {   // region by region: the inner loop is a plain one
+      const int64_t base = regions[k].pair_base, end = std::min<int64_t>(hi, regions[k + 1].pair_base);
+      double* const dst = out[k];
+      if (flags[k] == 0)
+        for (int64_t i = lo; i < end; i++) dst[i - base] = std::log10(sums[i]) - scale_log10;
+      lo = end;
+    }
+  };
+  static const int fin_threads = std::max(1, std::min(4, (int)std::thread::hardware_concurrency()));
+  try {
+    c->workers.parallel_for((int64_t)regions[K].pair_base, fin_threads, finalise, 4096);
+  } catch (const std::bad_alloc&) {
+    return fail(GKLHIP_ERR_OOM, "out of memory in the host finalisation");
+  }
+  return GKLHIP_OK;
+}
+
 int pd_run_locked(gklhip_pdhmm_ctx* c, const PdProblem& q, double* out_host) {
   static const bool timing = getenv("GKLHIP_TIMING") != nullptr;
   const auto t_begin = std::chrono::steady_clock::now();
   auto ms_since = [&](std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); };
-  PD_HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipSetDevice(c->device));
   hipStream_t s = c->stream;
   const size_t n = (size_t)q.n_pairs;
   const size_t nh = (size_t)q.n_hap_items, nr = (size_t)q.n_read_items;
-  const size_t hap_bytes = nh * (size_t)q.max_hap_len, read_bytes = nr * (size_t)q.max_read_len;
-  auto up = [](size_t x) { return (x + 255) / 256 * 256; };
-  const size_t o_hb = 0, o_hp = up(hap_bytes), o_rb = o_hp + up(hap_bytes), o_rq = o_rb + up(read_bytes),
-               o_ri = o_rq + up(read_bytes), o_rd = o_ri + up(read_bytes), o_gc = o_rd + up(read_bytes),
-               o_hl = o_gc + up(read_bytes), o_rl = o_hl + up(nh * 8), total = o_rl + up(nr * 8);
+  const PdInputLayout in(nh, nr, (size_t)q.max_hap_len, (size_t)q.max_read_len);
+  const size_t hap_bytes = in.hap_bytes, read_bytes = in.read_bytes;
   int rc;
-  if ((rc = c->inputs.reserve(total))) return rc;
+  if ((rc = c->inputs.reserve(in.total))) return rc;
   unsigned char* d = c->inputs.as<unsigned char>();
   // The nine input copies (the paired layout of a big batch is hundreds of MB of padded [pair][maxLen] arrays: the
   // calls alone -- pinning the caller's pages -- take milliseconds): a helper thread issues them while this one builds
@@ -643,11 +714,11 @@ int pd_run_locked(gklhip_pdhmm_ctx* c, const PdProblem& q, double* out_host) {
       const size_t h0 = n_slices > 1 ? slice_lo[k] : 0, h1 = n_slices > 1 ? slice_lo[k + 1] : nh;
       const size_t r0 = n_slices > 1 ? slice_lo[k] : 0, r1 = n_slices > 1 ? slice_lo[k + 1] : nr;
       const size_t mh = (size_t)q.max_hap_len, mr = (size_t)q.max_read_len;
-      cp(o_hl + h0 * 8, q.hap_lengths + h0, (h1 - h0) * 8); cp(o_rl + r0 * 8, q.read_lengths + r0, (r1 - r0) * 8);
-      cp(o_hb + h0 * mh, q.hap_bases + h0 * mh, (h1 - h0) * mh); cp(o_hp + h0 * mh, q.hap_pdbases + h0 * mh, (h1 - h0) * mh);
-      cp(o_rb + r0 * mr, q.read_bases + r0 * mr, (r1 - r0) * mr); cp(o_rq + r0 * mr, q.read_qual + r0 * mr, (r1 - r0) * mr);
-      cp(o_ri + r0 * mr, q.read_ins_qual + r0 * mr, (r1 - r0) * mr); cp(o_rd + r0 * mr, q.read_del_qual + r0 * mr, (r1 - r0) * mr);
-      cp(o_gc + r0 * mr, q.gcp + r0 * mr, (r1 - r0) * mr);
+      cp(in.o_hl + h0 * 8, q.hap_lengths + h0, (h1 - h0) * 8); cp(in.o_rl + r0 * 8, q.read_lengths + r0, (r1 - r0) * 8);
+      cp(in.o_hb + h0 * mh, q.hap_bases + h0 * mh, (h1 - h0) * mh); cp(in.o_hp + h0 * mh, q.hap_pdbases + h0 * mh, (h1 - h0) * mh);
+      cp(in.o_rb + r0 * mr, q.read_bases + r0 * mr, (r1 - r0) * mr); cp(in.o_rq + r0 * mr, q.read_qual + r0 * mr, (r1 - r0) * mr);
+      cp(in.o_ri + r0 * mr, q.read_ins_qual + r0 * mr, (r1 - r0) * mr); cp(in.o_rd + r0 * mr, q.read_del_qual + r0 * mr, (r1 - r0) * mr);
+      cp(in.o_gc + r0 * mr, q.gcp + r0 * mr, (r1 - r0) * mr);
       if (n_slices > 1) {
         if (up_th.err == hipSuccess) up_th.err = hipEventRecord(c->up_ev[k], us);
         up_th.recorded.store(k + 1, std::memory_order_release);
@@ -656,15 +727,15 @@ int pd_run_locked(gklhip_pdhmm_ctx* c, const PdProblem& q, double* out_host) {
   };
   // A call of the fixture's size (276 reads x 48 haplotypes) spent half its time in two dozen small copies from
   // pageable memory (~10 us each): up to kPdStageBytes the arrays are gathered in a pinned block and travel in ONE copy.
-  const bool staged = total <= kPdStageBytes;
+  const bool staged = in.total <= kPdStageBytes;
   if (staged) {
-    if ((rc = c->stage_in.reserve(total))) return rc;
+    if ((rc = c->stage_in.reserve(in.total))) return rc;
     unsigned char* h = c->stage_in.as<unsigned char>();
-    memcpy(h + o_hb, q.hap_bases, hap_bytes); memcpy(h + o_hp, q.hap_pdbases, hap_bytes);
-    memcpy(h + o_rb, q.read_bases, read_bytes); memcpy(h + o_rq, q.read_qual, read_bytes); memcpy(h + o_ri, q.read_ins_qual, read_bytes);
-    memcpy(h + o_rd, q.read_del_qual, read_bytes); memcpy(h + o_gc, q.gcp, read_bytes);
-    memcpy(h + o_hl, q.hap_lengths, nh * 8); memcpy(h + o_rl, q.read_lengths, nr * 8);
-    PD_HIP_TRY(hipMemcpyAsync(d, h, total, hipMemcpyHostToDevice, s));
+    memcpy(h + in.o_hb, q.hap_bases, hap_bytes); memcpy(h + in.o_hp, q.hap_pdbases, hap_bytes);
+    memcpy(h + in.o_rb, q.read_bases, read_bytes); memcpy(h + in.o_rq, q.read_qual, read_bytes); memcpy(h + in.o_ri, q.read_ins_qual, read_bytes);
+    memcpy(h + in.o_rd, q.read_del_qual, read_bytes); memcpy(h + in.o_gc, q.gcp, read_bytes);
+    memcpy(h + in.o_hl, q.hap_lengths, nh * 8); memcpy(h + in.o_rl, q.read_lengths, nr * 8);
+    HIP_TRY(hipMemcpyAsync(d, h, in.total, hipMemcpyHostToDevice, s));
   } else if (n_slices > 1 || hap_bytes + 5 * read_bytes >= ((size_t)8 << 20)) {
     up_th.th = std::thread(do_uploads);
   } else {
@@ -696,15 +767,7 @@ int pd_run_locked(gklhip_pdhmm_ctx* c, const PdProblem& q, double* out_host) {
     // run by the scalar-arithmetic instantiation of the kernel.
     if (c->tail_mode == 1) n_tail = n % (size_t)(c->fma_mode ? 8 : 4);
     const size_t n_vec = n - n_tail;
-    for (size_t i = n_vec; i < n; i++) {
-      const int nb = blocks_for(read_len_of(i), kPdRpl);
-      tail_pair.push_back((int32_t)i);
-      tail_striped.push_back(nb > kLanes ? 1 : 0);
-      tail_steps.push_back(hap_len_of(i) + std::min(nb, kLanes) - 1);
-      tail_lanes.resize(tail_lanes.size() + kLanes, PlanLane{-1, 0});
-      if (nb <= kLanes)
-        for (int b = 0; b < nb; b++) tail_lanes[tail_lanes.size() - kLanes + (size_t)b] = PlanLane{(int32_t)i, b};
-    }
+    for (size_t i = n_vec; i < n; i++) pd_push_tail_job(&plan, (int32_t)i, read_len_of(i), hap_len_of(i));
     // short pairs, ordered by haplotype length so that wavefront mates finish together, are packed best-fit
     // into 64-lane chunks; a read that needs more than 64 lanes becomes a striped job
     std::vector<int64_t> pair_off(n + 1, 0);  // pack_reads_windowed() addresses reads through offsets
@@ -763,30 +826,16 @@ int pd_run_locked(gklhip_pdhmm_ctx* c, const PdProblem& q, double* out_host) {
   const double ms_routing = ms_since(t_begin);
   const int n_chunks_cross = (int)chunk_steps.size();
   const int64_t n_cross_jobs64 = (int64_t)n_chunks_cross * (int64_t)(cross ? nh : 0);
-  if (n_cross_jobs64 + (int64_t)job_pair.size() > 0x7fffffffLL) return pd_fail(GKLHIP_ERR_INVALID_ARG, "too many jobs");
+  if (n_cross_jobs64 + (int64_t)job_pair.size() > 0x7fffffffLL) return fail(GKLHIP_ERR_INVALID_ARG, "too many jobs");
   const int n_cross_jobs = (int)n_cross_jobs64;
   const int n_cross_tab = cross ? (int)((int64_t)n_chunks_cross * (int64_t)n_tab_haps) : 0;
-  // Table launch: a unit of work is (a group of consecutive table haplotypes, a chunk of reads) -- the wavefront sets the
-  // chunk's rows up once per group (a twelfth of a job's time otherwise).  Groups of up to six while there are at least
-  // six units per wavefront, shrinking to single haplotypes over the last part of the list (they run last and even the load out).
-  std::vector<int32_t> tab_group_start;
-  if (n_cross_tab > 0) {
-    const int64_t per_wave = (int64_t)n_cross_tab / (256 * 8);
-    const int group_max = (int)std::max<int64_t>(1, std::min<int64_t>(6, per_wave / 6));
-    for (size_t k = 0; k < n_tab_haps;) {   // sizes shrink towards the end of the list: the last units are single haplotypes
-      const size_t left = n_tab_haps - k;
-      const size_t g = std::max<size_t>(1, std::min<size_t>((size_t)group_max, left / 7));
-      tab_group_start.push_back((int32_t)k);
-      k += g;
-    }
-    tab_group_start.push_back((int32_t)n_tab_haps);
-  }
+  std::vector<int32_t> tab_group_start;   // (table launch; see pd_size_tab_groups)
+  if (n_cross_tab > 0) pd_size_tab_groups(&n_tab_haps, 1, n_cross_tab, &tab_group_start, nullptr);
   const int n_tab_units = tab_group_start.empty() ? 0 : (int)((int64_t)n_chunks_cross * (int64_t)(tab_group_start.size() - 1));
   const int n_cross_hot = cross ? (int)((int64_t)n_chunks_cross * (int64_t)(n_clean_haps - n_tab_haps)) : 0;
   const int n_general = (int)job_pair.size();
   const int n_jobs = n_cross_jobs + n_general;
   const int entry_stride = (q.max_hap_len + 2 * kLanes + 4 + 63) / 64 * 64;   // 64 idle, the columns, 63 skew + 4 look-ahead
-  const int carry_len = entry_stride;
   const int n_blocks = std::max(1, std::min(std::max(n_jobs, (int)n_tail), 256 * 8));
   // Paired layout through the table kernel (pdhmm_fwd_tab_paired_kernel): classes, special columns and the routing of the
   // jobs are found on the device.  Needs the program's 32-bit entry offsets to reach every item's stream and the step
@@ -795,25 +844,25 @@ int pd_run_locked(gklhip_pdhmm_ctx* c, const PdProblem& q, double* out_host) {
   const bool tab_paired = !cross && c->use_table && n_packed > 0 && nh * (size_t)entry_stride * 4 < ((size_t)1 << 32) && entry_stride <= 12 * 1024;
   const bool tab_paired_asm = tab_paired && c->fma_mode == 1 && GKL_PD_ASM == 2;   // (the C++ step loops ballot on the lanes' own entries)
   const int sb_stride = entry_stride / 64, ns_stride = entry_stride;
-  const size_t x_nc = 0, x_cc = up(nh), x_sb = x_cc + up(nh * 32), x_nt = x_sb + up(nh * (size_t)sb_stride * 8), x_hj = x_nt + up((size_t)n_general),
-               x_ns = x_hj + up((size_t)n_general * 4), x_total = x_ns + (tab_paired_asm ? up((size_t)n_general * (size_t)ns_stride * 4) : 0);
+  const size_t x_nc = 0, x_cc = pd_up(nh), x_sb = x_cc + pd_up(nh * 32), x_nt = x_sb + pd_up(nh * (size_t)sb_stride * 8), x_hj = x_nt + pd_up((size_t)n_general),
+               x_ns = x_hj + pd_up((size_t)n_general * 4), x_total = x_ns + (tab_paired_asm ? pd_up((size_t)n_general * (size_t)ns_stride * 4) : 0);
   if ((rc = c->entries.reserve(nh * (size_t)entry_stride * 4))) return rc;
   if (n_tab_haps && (rc = c->entries_tab.reserve(2 * nh * (size_t)entry_stride * 4))) return rc;   // + the next-special-column table
   if (tab_paired && ((rc = c->entries_tab.reserve(nh * (size_t)entry_stride * 4)) || (rc = c->tabx.reserve(x_total)))) return rc;
   if ((rc = c->sums.reserve(n * 8))) return rc;
   if ((rc = c->misc.reserve(kPdMiscBytes))) return rc;
-  if ((rc = c->carry.reserve((size_t)n_blocks * 2 * (6 * (size_t)carry_len + 64) * 8))) return rc;
-  const size_t o_jl = 0, o_jp = up((size_t)n_general * kLanes * sizeof(PlanLane)), o_jn = o_jp + up((size_t)n_general * 4),
-               o_js = o_jn + up((size_t)n_general * 4), o_cl = o_js + up((size_t)n_general),
-               o_ho = o_cl + up(cross_lanes.size() * sizeof(PlanLane)), o_cs = o_ho + up(hap_order.size() * 4),
-               o_cr = o_cs + up(chunk_steps.size() * 4), o_tl = o_cr + up(chunk_rep.size() * 4),
-               o_tp = o_tl + up(tail_lanes.size() * sizeof(PlanLane)), o_tn = o_tp + up(n_tail * 4), o_ts = o_tn + up(n_tail * 4),
-               o_nc = o_ts + up(n_tail), o_cc = o_nc + up(hap_ncls.size()), o_jf = o_cc + up(class_codes.size() * 4),
-               o_pc = o_jf + up((size_t)n_general), o_pl = o_pc + up(place_chunk.size() * 4), o_cu = o_pl + up(place_lane.size()),
-               o_fj = o_cu + up(chunk_used.size()), o_tg = o_fj + up((size_t)n_general * 4), jobs_total = o_tg + up(tab_group_start.size() * 4);
+  if ((rc = c->carry.reserve((size_t)n_blocks * 2 * (6 * (size_t)entry_stride + 64) * 8))) return rc;   // (carry_len = entry_stride)
+  const size_t o_jl = 0, o_jp = pd_up((size_t)n_general * kLanes * sizeof(PlanLane)), o_jn = o_jp + pd_up((size_t)n_general * 4),
+               o_js = o_jn + pd_up((size_t)n_general * 4), o_cl = o_js + pd_up((size_t)n_general),
+               o_ho = o_cl + pd_up(cross_lanes.size() * sizeof(PlanLane)), o_cs = o_ho + pd_up(hap_order.size() * 4),
+               o_cr = o_cs + pd_up(chunk_steps.size() * 4), o_tl = o_cr + pd_up(chunk_rep.size() * 4),
+               o_tp = o_tl + pd_up(tail_lanes.size() * sizeof(PlanLane)), o_tn = o_tp + pd_up(n_tail * 4), o_ts = o_tn + pd_up(n_tail * 4),
+               o_nc = o_ts + pd_up(n_tail), o_cc = o_nc + pd_up(hap_ncls.size()), o_jf = o_cc + pd_up(class_codes.size() * 4),
+               o_pc = o_jf + pd_up((size_t)n_general), o_pl = o_pc + pd_up(place_chunk.size() * 4), o_cu = o_pl + pd_up(place_lane.size()),
+               o_fj = o_cu + pd_up(chunk_used.size()), o_tg = o_fj + pd_up((size_t)n_general * 4), jobs_total = o_tg + pd_up(tab_group_start.size() * 4);
   if (n_slices == 1) {   // (sliced call: the kernels of slice k wait for slice k's upload event, see below)
     if (up_th.th.joinable()) up_th.th.join();
-    PD_HIP_TRY(up_th.err);
+    HIP_TRY(up_th.err);
   }
   if ((rc = c->jobs.reserve(jobs_total + 256))) return rc;
   unsigned char* dj = c->jobs.as<unsigned char>();
@@ -826,115 +875,78 @@ int pd_run_locked(gklhip_pdhmm_ctx* c, const PdProblem& q, double* out_host) {
     if (staged_jobs) { memcpy(hj + off, src, bytes); staged_hi = std::max(staged_hi, off + bytes); return hipSuccess; }
     return hipMemcpyAsync(dj + off, src, bytes, hipMemcpyHostToDevice, s);
   };
-  PD_HIP_TRY(put(o_jp, job_pair.data(), (size_t)n_general * 4));
-  PD_HIP_TRY(put(o_jn, job_steps.data(), (size_t)n_general * 4));
-  PD_HIP_TRY(put(o_js, job_striped.data(), (size_t)n_general));
-  PD_HIP_TRY(put(o_cl, cross_lanes.data(), cross_lanes.size() * sizeof(PlanLane)));
-  PD_HIP_TRY(put(o_ho, hap_order.data(), hap_order.size() * 4));
-  PD_HIP_TRY(put(o_cs, chunk_steps.data(), chunk_steps.size() * 4));
-  PD_HIP_TRY(put(o_cr, chunk_rep.data(), chunk_rep.size() * 4));
-  PD_HIP_TRY(put(o_tl, tail_lanes.data(), tail_lanes.size() * sizeof(PlanLane)));
-  PD_HIP_TRY(put(o_tp, tail_pair.data(), n_tail * 4));
-  PD_HIP_TRY(put(o_tn, tail_steps.data(), n_tail * 4));
-  PD_HIP_TRY(put(o_ts, tail_striped.data(), n_tail));
-  PD_HIP_TRY(put(o_nc, hap_ncls.data(), hap_ncls.size()));
-  PD_HIP_TRY(put(o_cc, class_codes.data(), class_codes.size() * 4));
-  PD_HIP_TRY(put(o_pc, place_chunk.data(), place_chunk.size() * 4));
-  PD_HIP_TRY(put(o_pl, place_lane.data(), place_lane.size()));
-  PD_HIP_TRY(put(o_cu, chunk_used.data(), chunk_used.size()));
-  PD_HIP_TRY(put(o_tg, tab_group_start.data(), tab_group_start.size() * 4));
+  HIP_TRY(put(o_jp, job_pair.data(), (size_t)n_general * 4));
+  HIP_TRY(put(o_jn, job_steps.data(), (size_t)n_general * 4));
+  HIP_TRY(put(o_js, job_striped.data(), (size_t)n_general));
+  HIP_TRY(put(o_cl, cross_lanes.data(), cross_lanes.size() * sizeof(PlanLane)));
+  HIP_TRY(put(o_ho, hap_order.data(), hap_order.size() * 4));
+  HIP_TRY(put(o_cs, chunk_steps.data(), chunk_steps.size() * 4));
+  HIP_TRY(put(o_cr, chunk_rep.data(), chunk_rep.size() * 4));
+  HIP_TRY(put(o_tl, tail_lanes.data(), tail_lanes.size() * sizeof(PlanLane)));
+  HIP_TRY(put(o_tp, tail_pair.data(), n_tail * 4));
+  HIP_TRY(put(o_tn, tail_steps.data(), n_tail * 4));
+  HIP_TRY(put(o_ts, tail_striped.data(), n_tail));
+  HIP_TRY(put(o_nc, hap_ncls.data(), hap_ncls.size()));
+  HIP_TRY(put(o_cc, class_codes.data(), class_codes.size() * 4));
+  HIP_TRY(put(o_pc, place_chunk.data(), place_chunk.size() * 4));
+  HIP_TRY(put(o_pl, place_lane.data(), place_lane.size()));
+  HIP_TRY(put(o_cu, chunk_used.data(), chunk_used.size()));
+  HIP_TRY(put(o_tg, tab_group_start.data(), tab_group_start.size() * 4));
   if (n_general > 0) {
     if (staged_jobs) { memset(hj + o_jf, 0, (size_t)n_general); staged_hi = std::max(staged_hi, o_jf + (size_t)n_general); }
-    else PD_HIP_TRY(hipMemsetAsync(dj + o_jf, 0, (size_t)n_general, s));
+    else HIP_TRY(hipMemsetAsync(dj + o_jf, 0, (size_t)n_general, s));
   }
   // the full launch's list of listed jobs: the striped ones (the first n_striped in the paired layout, all of them in
   // the cross layout) from here, flagged packed jobs appended by pdhmm_collect_kernel; its length lives in misc[5]
   const int32_t n_striped_listed = cross ? n_general : (int32_t)n_striped;   // (lives, like the vectors, until the stream is drained below)
   std::vector<int32_t> full_first((size_t)n_striped_listed);
   for (int32_t k = 0; k < n_striped_listed; k++) full_first[(size_t)k] = k;
-  PD_HIP_TRY(hipMemsetAsync(c->misc.p, 0, 256, s));
+  HIP_TRY(hipMemsetAsync(c->misc.p, 0, 256, s));
 #ifdef GKL_PD_PROF
-  PD_HIP_TRY(hipMemsetAsync(c->misc.as<char>() + 128 + 13 * 8, 0xff, 8, s));
-  PD_HIP_TRY(hipMemsetAsync(c->misc.as<char>() + 128 + 15 * 8, 0xff, 8, s));
+  HIP_TRY(hipMemsetAsync(c->misc.as<char>() + 128 + 13 * 8, 0xff, 8, s));
+  HIP_TRY(hipMemsetAsync(c->misc.as<char>() + 128 + 15 * 8, 0xff, 8, s));
 #endif
-  PD_HIP_TRY(put(o_fj, full_first.data(), full_first.size() * 4));
-  if (staged_jobs && staged_hi > 0) PD_HIP_TRY(hipMemcpyAsync(dj, hj, staged_hi, hipMemcpyHostToDevice, s));
-  PD_HIP_TRY(hipMemcpyAsync(c->misc.as<int32_t>() + 5, &n_striped_listed, 4, hipMemcpyHostToDevice, s));
+  HIP_TRY(put(o_fj, full_first.data(), full_first.size() * 4));
+  if (staged_jobs && staged_hi > 0) HIP_TRY(hipMemcpyAsync(dj, hj, staged_hi, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(c->misc.as<int32_t>() + 5, &n_striped_listed, 4, hipMemcpyHostToDevice, s));
 
-  const PdTables& t = pd_tables();
-  PdArgs a;
-  a.hap_bases = reinterpret_cast<const int8_t*>(d + o_hb);
-  a.hap_pdbases = reinterpret_cast<const int8_t*>(d + o_hp);
-  a.read_bases = reinterpret_cast<const int8_t*>(d + o_rb);
-  a.read_qual = reinterpret_cast<const int8_t*>(d + o_rq);
-  a.read_ins = reinterpret_cast<const int8_t*>(d + o_ri);
-  a.read_del = reinterpret_cast<const int8_t*>(d + o_rd);
-  a.gcp = reinterpret_cast<const int8_t*>(d + o_gc);
-  a.hap_len = reinterpret_cast<const int64_t*>(d + o_hl);
-  a.read_len = reinterpret_cast<const int64_t*>(d + o_rl);
-  a.batch = (int32_t)n; a.max_hap = q.max_hap_len; a.max_read = q.max_read_len;
-  a.cross_haps = cross; a.n_hap_items = q.n_hap_items;
-  a.q2err = c->tables.as<double>();
-  a.mm_prob = c->tables.as<double>() + t.q2err.size();
-  a.entries = c->entries.as<uint32_t>();
-  a.entry_stride = entry_stride;
+  PdArgs a = pd_common_args(c, in, PdJobOffsets{o_jl, o_jp, o_jn, o_js, o_cl, o_cs, o_cr, o_nc, o_cc, o_jf, o_fj, o_tg}, nh, q.max_hap_len,
+                            q.max_read_len, entry_stride, n_tab_haps != 0);
+  a.batch = (int32_t)n;
+  a.cross_haps = cross;
   a.sums = c->sums.as<double>();
-  // A region-sized call (up to 131 072 pairs = 1 MB of sums): the kernels store the sums -- write-only, one store per pair --
+  // A region-sized call (up to kPdMultiMaxPairs = 1 MB of sums): the kernels store the sums -- write-only, one store per pair --
   // straight into the pinned host block (posted writes over PCIe) instead of a device array that a copy then fetches: one
   // copy launch (~15 us of a 0.28 ms call) less.
-  const bool sums_direct = n <= 131072;
+  const bool sums_direct = n <= kPdMultiMaxPairs;
   if ((rc = c->sums_pin.reserve(n * 8 + 64))) return rc;
   if (sums_direct) {
     void* dp = nullptr;
-    PD_HIP_TRY(hipHostGetDevicePointer(&dp, c->sums_pin.p, 0));
+    HIP_TRY(hipHostGetDevicePointer(&dp, c->sums_pin.p, 0));
     a.sums = static_cast<double*>(dp);
   }
   a.status = c->misc.as<int32_t>();
-  a.next = c->misc.as<int32_t>() + 1;
-  a.carry = c->carry.as<double>();
-  a.carry_len = carry_len;
-  a.lanes = reinterpret_cast<const LaneSlot*>(dj + o_jl);
-  a.job_pair = reinterpret_cast<const int32_t*>(dj + o_jp);
-  a.job_steps = reinterpret_cast<const int32_t*>(dj + o_jn);
-  a.job_striped = dj + o_js;
   a.n_jobs = n_jobs;
   a.n_cross_jobs = n_cross_jobs; a.n_chunks_cross = std::max(n_chunks_cross, 1);
-  a.cross_lanes = reinterpret_cast<const LaneSlot*>(dj + o_cl);
   a.hap_order = reinterpret_cast<const int32_t*>(dj + o_ho);
-  a.chunk_steps = reinterpret_cast<const int32_t*>(dj + o_cs);
-  a.chunk_rep = reinterpret_cast<const int32_t*>(dj + o_cr);
-  a.hap_ncls = n_tab_haps ? dj + o_nc : nullptr;
-  a.class_codes = reinterpret_cast<const uint32_t*>(dj + o_cc);
-  a.entries_tab = c->entries_tab.as<uint32_t>();
-  a.next_special = n_tab_haps ? reinterpret_cast<int32_t*>(c->entries_tab.as<uint32_t>() + nh * (size_t)entry_stride) : nullptr;
-  a.job_flags = dj + o_jf;
-  a.full_jobs = reinterpret_cast<const int32_t*>(dj + o_fj);
   a.full_count = c->misc.as<int32_t>() + 5;
-  a.tab_group_start = reinterpret_cast<const int32_t*>(dj + o_tg);
   unsigned char* dx = c->tabx.as<unsigned char>();
-  a.hap_ncls_out = nullptr; a.class_codes_out = nullptr; a.special_bits = nullptr; a.sb_stride = sb_stride;
-  a.job_notab = nullptr; a.job_ns = nullptr; a.ns_stride = ns_stride;
   if (tab_paired) {
     a.hap_ncls_out = dx + x_nc;
     a.class_codes_out = reinterpret_cast<uint32_t*>(dx + x_cc);
     a.special_bits = tab_paired_asm ? reinterpret_cast<uint64_t*>(dx + x_sb) : nullptr;
     a.job_notab = dx + x_nt;
     a.job_ns = reinterpret_cast<const int32_t*>(dx + x_ns);
-    PD_HIP_TRY(hipMemsetAsync(dx + x_nt, 0, (size_t)n_general, s));
+    HIP_TRY(hipMemsetAsync(dx + x_nt, 0, (size_t)n_general, s));
   }
-#ifdef GKL_PD_PROF
-  a.prof = reinterpret_cast<unsigned long long*>(c->misc.as<char>() + 128);
-#endif
 
-  a.item_base = 0; a.job_base = 0;
-  a.regions = nullptr; a.n_regions = 0; a.multi_launch = 0;
   const bool paired_packed = !cross && !chunk_used.empty();
   if (!paired_packed && n_slices > 1) {
     // A sliced call without one packed chunk (every read striped): nothing below waits slice by slice, and the helper
     // thread may still be sending -- meet ALL the uploads before the first kernel of the other branch reads the arrays.
     if (up_th.th.joinable()) up_th.th.join();
-    PD_HIP_TRY(up_th.err);
-    for (int k = 0; k < n_slices; k++) PD_HIP_TRY(hipStreamWaitEvent(s, c->up_ev[k], 0));
+    HIP_TRY(up_th.err);
+    for (int k = 0; k < n_slices; k++) HIP_TRY(hipStreamWaitEvent(s, c->up_ev[k], 0));
   }
   if (paired_packed) {
     // ---- paired layout: slice by slice (one slice unless the call is big, see above) ----
@@ -955,8 +967,8 @@ int pd_run_locked(gklhip_pdhmm_ctx* c, const PdProblem& q, double* out_host) {
       const int j0 = (int)n_striped + c0, j1 = (int)n_striped + c1;
       if (n_slices > 1) {
         while (up_th.recorded.load(std::memory_order_acquire) <= k) std::this_thread::yield();
-        PD_HIP_TRY(up_th.err);
-        PD_HIP_TRY(hipStreamWaitEvent(s, c->up_ev[k], 0));
+        HIP_TRY(up_th.err);
+        HIP_TRY(hipStreamWaitEvent(s, c->up_ev[k], 0));
       }
       PdArgs ae = a;
       ae.item_base = (int32_t)lo;
@@ -967,8 +979,8 @@ int pd_run_locked(gklhip_pdhmm_ctx* c, const PdProblem& q, double* out_host) {
         hipLaunchKernelGGL(pdhmm_collect_kernel, dim3((unsigned)((j1 - j0 + 255) / 256)), dim3(256), 0, s, dj + o_jf, dj + o_js, j1,
                            reinterpret_cast<int32_t*>(dj + o_fj), c->misc.as<int32_t>() + 5, tab_paired ? dx + x_nt : nullptr,
                            reinterpret_cast<int32_t*>(dx + x_hj), c->misc.as<int32_t>() + 6, j0);
-      PD_HIP_TRY(hipEventRecord(n_slices > 1 ? c->sl_ev0[k] : c->ev0, s));
-      if (j1 <= j0) { if (n_slices > 1) PD_HIP_TRY(hipEventRecord(c->sl_ev1[k], s)); continue; }
+      HIP_TRY(hipEventRecord(n_slices > 1 ? c->sl_ev0[k] : c->ev0, s));
+      if (j1 <= j0) { if (n_slices > 1) HIP_TRY(hipEventRecord(c->sl_ev1[k], s)); continue; }
       if (tab_paired) {
         // table launch: the jobs' next-special-step tables first (part of the timed region: work only this route does),
         // then every listed job of the slice that is clean and whose haplotypes all have at most kPdTabClasses classes
@@ -984,45 +996,40 @@ int pd_run_locked(gklhip_pdhmm_ctx* c, const PdProblem& q, double* out_host) {
         at.n_cross_jobs = 0; at.job_base = j0; at.n_jobs = j1;
         at.class_codes = a.class_codes_out;
         at.next = c->misc.as<int32_t>() + 8 + k;
-        if (c->fma_mode) hipLaunchKernelGGL(pdhmm_fwd_tab_paired_kernel<true>, dim3(std::min(j1 - j0, n_blocks)), dim3(64), 0, s, at, t.initial_condition);
-        else             hipLaunchKernelGGL(pdhmm_fwd_tab_paired_kernel<false>, dim3(std::min(j1 - j0, n_blocks)), dim3(64), 0, s, at, t.initial_condition);
+        pd_launch_fwd(c, pdhmm_fwd_tab_paired_kernel<true>, pdhmm_fwd_tab_paired_kernel<false>, std::min(j1 - j0, n_blocks), s, at);
       } else {
         // predicate launch: walks the slice's listed jobs and skips the flagged ones
         PdArgs ah = a;
         ah.n_cross_jobs = 0; ah.job_base = j0; ah.n_jobs = j1;
         ah.full_jobs = nullptr;
         ah.next = c->misc.as<int32_t>() + 16 + k;
-        if (c->fma_mode) hipLaunchKernelGGL((pdhmm_fwd_kernel<true, false, true>), dim3(std::min(j1 - j0, n_blocks)), dim3(64), 0, s, ah, t.initial_condition);
-        else             hipLaunchKernelGGL((pdhmm_fwd_kernel<false, false, true>), dim3(std::min(j1 - j0, n_blocks)), dim3(64), 0, s, ah, t.initial_condition);
+        pd_launch_fwd(c, pdhmm_fwd_kernel<true, false, true>, pdhmm_fwd_kernel<false, false, true>, std::min(j1 - j0, n_blocks), s, ah);
       }
-      if (n_slices > 1) PD_HIP_TRY(hipEventRecord(c->sl_ev1[k], s));
+      if (n_slices > 1) HIP_TRY(hipEventRecord(c->sl_ev1[k], s));
     }
-    if (n_slices > 1) PD_HIP_TRY(hipEventRecord(c->ev0, s));
+    if (n_slices > 1) HIP_TRY(hipEventRecord(c->ev0, s));
     if (tab_paired) {
       // predicate launch: the (rare) clean packed jobs with an ineligible haplotype, from the list pdhmm_collect_kernel made
       PdArgs ah = a;
       ah.n_cross_jobs = 0; ah.n_jobs = 0;
       ah.full_jobs = reinterpret_cast<const int32_t*>(dx + x_hj);
       ah.full_count = c->misc.as<int32_t>() + 6;
-      if (c->fma_mode) hipLaunchKernelGGL((pdhmm_fwd_kernel<true, false, true>), dim3(std::min((int)n_packed, n_blocks)), dim3(64), 0, s, ah, t.initial_condition);
-      else             hipLaunchKernelGGL((pdhmm_fwd_kernel<false, false, true>), dim3(std::min((int)n_packed, n_blocks)), dim3(64), 0, s, ah, t.initial_condition);
+      pd_launch_fwd(c, pdhmm_fwd_kernel<true, false, true>, pdhmm_fwd_kernel<false, false, true>, std::min((int)n_packed, n_blocks), s, ah);
     }
     PdArgs af = a;   // full launch: striped reads and haplotypes with odd bases (the list: striped jobs from the host, flagged ones from pdhmm_collect_kernel)
     af.n_cross_jobs = 0; af.n_jobs = n_general;
     af.next = c->misc.as<int32_t>() + 3;
-    if (c->fma_mode) hipLaunchKernelGGL(pdhmm_fwd_kernel<true>, dim3(std::min(n_general, n_blocks)), dim3(64), 0, s, af, t.initial_condition);
-    else             hipLaunchKernelGGL(pdhmm_fwd_kernel<false>, dim3(std::min(n_general, n_blocks)), dim3(64), 0, s, af, t.initial_condition);
+    pd_launch_fwd(c, pdhmm_fwd_kernel<true>, pdhmm_fwd_kernel<false>, std::min(n_general, n_blocks), s, af);
   } else {
     // ---- cross layout (and a paired call that holds striped reads only) ----
     hipLaunchKernelGGL(pdhmm_entries_kernel, dim3((unsigned)nh), dim3(kLanes), 0, s, a);   // one wavefront per haplotype item
-    PD_HIP_TRY(hipEventRecord(c->ev0, s));
+    HIP_TRY(hipEventRecord(c->ev0, s));
     // table launch: cross jobs over the haplotypes with few column classes
     if (n_cross_tab > 0) {
       PdArgs at = a;
       at.n_cross_jobs = at.n_jobs = n_tab_units;   // (units: haplotype group x chunk)
       at.next = c->misc.as<int32_t>() + 4;
-      if (c->fma_mode) hipLaunchKernelGGL(pdhmm_fwd_tab_kernel<true>, dim3(std::min(n_tab_units, n_blocks)), dim3(64), 0, s, at, t.initial_condition);
-      else             hipLaunchKernelGGL(pdhmm_fwd_tab_kernel<false>, dim3(std::min(n_tab_units, n_blocks)), dim3(64), 0, s, at, t.initial_condition);
+      pd_launch_fwd(c, pdhmm_fwd_tab_kernel<true>, pdhmm_fwd_tab_kernel<false>, std::min(n_tab_units, n_blocks), s, at);
     }
     // hot launch: cross jobs over the other clean haplotypes + the listed jobs the device routes to it
     PdArgs ah = a;
@@ -1031,8 +1038,7 @@ int pd_run_locked(gklhip_pdhmm_ctx* c, const PdProblem& q, double* out_host) {
     ah.n_jobs = n_cross_hot + (cross ? 0 : n_general);   // (cross layout: the listed jobs are striped reads, all the full kernel's)
     ah.full_jobs = nullptr;   // walks every listed job and skips the flagged ones
     if (ah.n_jobs > 0) {
-      if (c->fma_mode) hipLaunchKernelGGL((pdhmm_fwd_kernel<true, false, true>), dim3(std::min(ah.n_jobs, n_blocks)), dim3(64), 0, s, ah, t.initial_condition);
-      else             hipLaunchKernelGGL((pdhmm_fwd_kernel<false, false, true>), dim3(std::min(ah.n_jobs, n_blocks)), dim3(64), 0, s, ah, t.initial_condition);
+      pd_launch_fwd(c, pdhmm_fwd_kernel<true, false, true>, pdhmm_fwd_kernel<false, false, true>, std::min(ah.n_jobs, n_blocks), s, ah);
     }
     // full launch: cross jobs over the haplotypes with odd bases + the listed jobs with a striped read or an odd haplotype
     PdArgs af = a;
@@ -1041,8 +1047,7 @@ int pd_run_locked(gklhip_pdhmm_ctx* c, const PdProblem& q, double* out_host) {
     af.n_jobs = af.n_cross_jobs + n_general;
     af.next = c->misc.as<int32_t>() + 3;
     if (af.n_jobs > 0) {
-      if (c->fma_mode) hipLaunchKernelGGL(pdhmm_fwd_kernel<true>, dim3(std::min(af.n_jobs, n_blocks)), dim3(64), 0, s, af, t.initial_condition);
-      else             hipLaunchKernelGGL(pdhmm_fwd_kernel<false>, dim3(std::min(af.n_jobs, n_blocks)), dim3(64), 0, s, af, t.initial_condition);
+      pd_launch_fwd(c, pdhmm_fwd_kernel<true>, pdhmm_fwd_kernel<false>, std::min(af.n_jobs, n_blocks), s, af);
     }
   }
   if (n_tail > 0) {
@@ -1056,29 +1061,29 @@ int pd_run_locked(gklhip_pdhmm_ctx* c, const PdProblem& q, double* out_host) {
     at.job_flags = nullptr;   // every tail job is this launch's
     at.full_jobs = nullptr;
     at.next = c->misc.as<int32_t>() + 2;
-    hipLaunchKernelGGL((pdhmm_fwd_kernel<false, true>), dim3((unsigned)std::min<size_t>(n_tail, (size_t)n_blocks)), dim3(64), 0, s, at, t.initial_condition);  // persistent: one carry slab per block
+    hipLaunchKernelGGL((pdhmm_fwd_kernel<false, true>), dim3((unsigned)std::min<size_t>(n_tail, (size_t)n_blocks)), dim3(64), 0, s, at, pd_tables().initial_condition);  // persistent: one carry slab per block
   }
-  PD_HIP_TRY(hipEventRecord(c->ev1, s));
-  PD_HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(c->ev1, s));
+  HIP_TRY(hipGetLastError());
   double* sums = c->sums_pin.as<double>();
   int32_t* status = reinterpret_cast<int32_t*>(sums + n);
-  if (!sums_direct) PD_HIP_TRY(hipMemcpyAsync(sums, c->sums.p, n * 8, hipMemcpyDeviceToHost, s));
-  PD_HIP_TRY(hipMemcpyAsync(status, c->misc.p, 32, hipMemcpyDeviceToHost, s));
+  if (!sums_direct) HIP_TRY(hipMemcpyAsync(sums, c->sums.p, n * 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(status, c->misc.p, 32, hipMemcpyDeviceToHost, s));
   const double ms_launched = ms_since(t_begin);
-  PD_HIP_TRY(hipStreamSynchronize(s));
+  HIP_TRY(hipStreamSynchronize(s));
   if (up_th.th.joinable()) up_th.th.join();   // (a sliced call: the stream has waited for every upload event by now)
-  PD_HIP_TRY(up_th.err);
-  PD_HIP_TRY(hipEventElapsedTime(&c->last_ms, c->ev0, c->ev1));
+  HIP_TRY(up_th.err);
+  HIP_TRY(hipEventElapsedTime(&c->last_ms, c->ev0, c->ev1));
   if (paired_packed && n_slices > 1)   // kernel time of a sliced call: its slices' launches plus the closing ones (the waits for the bus lie between them)
     for (int k = 0; k < n_slices; k++) {
       float ms = 0.f;
-      PD_HIP_TRY(hipEventElapsedTime(&ms, c->sl_ev0[k], c->sl_ev1[k]));
+      HIP_TRY(hipEventElapsedTime(&ms, c->sl_ev0[k], c->sl_ev1[k]));
       c->last_ms += ms;
     }
 #ifdef GKL_PD_PROF
   {  // development build: where the table kernel's wavefronts spent their cycles (s_memtime)
     unsigned long long pr[16];
-    PD_HIP_TRY(hipMemcpy(pr, c->misc.as<char>() + 128, sizeof pr, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(pr, c->misc.as<char>() + 128, sizeof pr, hipMemcpyDeviceToHost));
     const double tot = (double)(pr[0] + pr[1] + pr[2] + pr[3] + pr[4] + pr[5]);
     fprintf(stderr, "[pd prof] setup+table %.3f  asm runs %.3f (%llu steps)  plain x2 loop %.3f (%llu)  plain x1 loop %.3f (%llu)  general %.3f (%llu)  other %.3f  | jobs %llu, total %.3e ticks; first wavefront done at %.3f of the launch, last at 1\n",
             pr[0] / tot, pr[1] / tot, pr[8], pr[2] / tot, pr[9], pr[3] / tot, pr[10], pr[4] / tot, pr[11], pr[5] / tot, pr[12], tot, (double)(pr[13] - pr[15]) / (double)(pr[14] - pr[15]));
@@ -1094,20 +1099,10 @@ int pd_run_locked(gklhip_pdhmm_ctx* c, const PdProblem& q, double* out_host) {
     c->last_routing[2] = n_full_packed;
   }
   if (status[0] != 0)  // PDHMM_INPUT_DATA_ERROR (pdhmm-serial.cc:183-199): negative ins / del / gcp quality
-    return pd_fail(GKLHIP_ERR_INVALID_ARG, "Error while calculating pdhmm. Input arrays aren't valid.");
-  // log10 of the sums with the HOST libm, like the reference (pdhmm.h:846) -- a region's 13 248 pairs are 0.13 ms of it on
-  // one thread, three quarters of what the call costs beyond its kernels: four threads from 4096 pairs on (persistent
-  // workers: a thread per call would cost more than it saves)
-  const std::function<void(int64_t, int64_t)> finalise = [&](int64_t lo, int64_t hi) {
-    for (int64_t i = lo; i < hi; i++) out_host[i] = std::log10(sums[i]) - t.initial_condition_log10;
-  };
-  static const int fin_threads = std::max(1, std::min(4, (int)std::thread::hardware_concurrency()));
-  try {
-    c->workers.parallel_for((int64_t)n, fin_threads, finalise, 4096);
-  } catch (const std::bad_alloc&) {
-    return pd_fail(GKLHIP_ERR_OOM, "out of memory in the host finalisation");
-  }
-  return GKLHIP_OK;
+    return fail(GKLHIP_ERR_INVALID_ARG, "Error while calculating pdhmm. Input arrays aren't valid.");
+  PdRegion one[2] = {};   // the call as ONE region of n pairs
+  one[1].pair_base = (int32_t)n;
+  return pd_finalise(c, sums, one, 1, &out_host, status);   // (status[0] == 0 here)
 }
 
 // ---- several region calls in one set of launches (gklhip_pdhmm_compute_cross_multi) ----
@@ -1119,17 +1114,13 @@ struct PdMultiRegion {
 };
 
 // Bytes of the regions' inputs in the layout of a multi-region call: one common row stride per side.
-size_t pd_input_bytes(size_t nh, size_t nr, size_t mh, size_t mr) {
-  auto up = [](size_t x) { return (x + 255) / 256 * 256; };
-  return 2 * up(nh * mh) + 5 * up(nr * mr) + up(nh * 8) + up(nr * 8);
-}
 size_t pd_multi_input_bytes(const std::vector<PdMultiRegion>& R) {
   size_t nh = 0, nr = 0, mh = 0, mr = 0;
   for (const PdMultiRegion& r : R) {
     nh += (size_t)r.q.n_hap_items; nr += (size_t)r.q.n_read_items;
     mh = std::max(mh, (size_t)r.q.max_hap_len); mr = std::max(mr, (size_t)r.q.max_read_len);
   }
-  return pd_input_bytes(nh, nr, mh, mr);
+  return PdInputLayout(nh, nr, mh, mr).total;
 }
 
 // The regions of R (all valid, same context settings; at most kPdMaxRegions, kPdMultiMaxPairs pairs, kPdStageBytes of
@@ -1139,11 +1130,13 @@ size_t pd_multi_input_bytes(const std::vector<PdMultiRegion>& R) {
 // The return value is the status of the launch set (a HIP failure fails every region); R[k].flag != 0: region k had a
 // negative quality (PDHMM_INPUT_DATA_ERROR), its output is not written.
 int pd_run_multi_locked(gklhip_pdhmm_ctx* c, std::vector<PdMultiRegion>& R) {
-  PD_HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipSetDevice(c->device));
   hipStream_t s = c->stream;
   const int K = (int)R.size();
   std::vector<PdCrossPlan> plans((size_t)K);
   std::vector<PdRegionShape> shapes((size_t)K);
+  std::vector<size_t> tab_haps((size_t)K);
+  std::vector<int32_t> groups((size_t)K);
   size_t NH = 0, NR = 0, NP = 0, mh = 0, mr = 0;
   size_t n_tab_haps = 0, n_hot_haps = 0, n_full_haps = 0, n_chunks = 0, n_general = 0, n_tail = 0;
   int64_t n_cross_tab = 0;   // (haplotype, chunk) jobs of the table launch
@@ -1154,32 +1147,18 @@ int pd_run_multi_locked(gklhip_pdhmm_ctx* c, std::vector<PdMultiRegion>& R) {
     const PdCrossPlan& pl = plans[(size_t)k];
     NH += (size_t)q.n_hap_items; NR += (size_t)q.n_read_items; NP += (size_t)q.n_pairs;
     mh = std::max(mh, (size_t)q.max_hap_len); mr = std::max(mr, (size_t)q.max_read_len);
+    tab_haps[(size_t)k] = pl.n_tab_haps;
     n_tab_haps += pl.n_tab_haps; n_hot_haps += pl.n_clean_haps - pl.n_tab_haps; n_full_haps += (size_t)q.n_hap_items - pl.n_clean_haps;
     n_chunks += pl.chunk_steps.size(); n_general += pl.job_pair.size(); n_tail += pl.n_tail;
     n_cross_tab += (int64_t)pl.chunk_steps.size() * (int64_t)pl.n_tab_haps;
   }
-  // Table launch: groups of consecutive table haplotypes of ONE region (see pd_run_locked), sized by the units of the
-  // whole launch -- many small regions together fill the device, so they get the full groups a single one would not --
-  // and shrinking to single haplotypes over the last part of the launch's list.
   std::vector<int32_t> tab_group_start;
-  {
-    const int64_t per_wave = n_cross_tab / (256 * 8);
-    const size_t group_max = (size_t)std::max<int64_t>(1, std::min<int64_t>(6, per_wave / 6));
-    size_t left = n_tab_haps, at = 0;
-    for (int k = 0; k < K; k++) {
-      const size_t mine = plans[(size_t)k].n_tab_haps;
-      int32_t groups = 0;
-      for (size_t i = 0; i < mine; groups++) {
-        const size_t g = std::max<size_t>(1, std::min(std::min(group_max, left / 7), mine - i));
-        tab_group_start.push_back((int32_t)(at + i));
-        i += g; left -= g;
-      }
-      at += mine;
-      shapes[(size_t)k] = PdRegionShape{R[(size_t)k].q.n_read_items, R[(size_t)k].q.n_hap_items, (int32_t)plans[(size_t)k].chunk_steps.size(),
-                                        {groups, (int32_t)(plans[(size_t)k].n_clean_haps - mine),
-                                         (int32_t)((size_t)R[(size_t)k].q.n_hap_items - plans[(size_t)k].n_clean_haps)}};
-    }
-    tab_group_start.push_back((int32_t)n_tab_haps);
+  pd_size_tab_groups(tab_haps.data(), K, n_cross_tab, &tab_group_start, groups.data());
+  for (int k = 0; k < K; k++) {
+    const PdProblem& q = R[(size_t)k].q;
+    const PdCrossPlan& pl = plans[(size_t)k];
+    shapes[(size_t)k] = PdRegionShape{q.n_read_items, q.n_hap_items, (int32_t)pl.chunk_steps.size(),
+                                      {groups[(size_t)k], (int32_t)(pl.n_clean_haps - pl.n_tab_haps), (int32_t)((size_t)q.n_hap_items - pl.n_clean_haps)}};
   }
   std::vector<PdRegion> regions((size_t)K + 1);
   pd_build_regions(shapes.data(), K, regions.data());
@@ -1187,13 +1166,9 @@ int pd_run_multi_locked(gklhip_pdhmm_ctx* c, std::vector<PdMultiRegion>& R) {
             n_full_units = regions[(size_t)K].unit_start[kPdLaunchFull];
 
   // ---- inputs: one pinned block, every region's rows at the common strides, one copy ----
-  auto up = [](size_t x) { return (x + 255) / 256 * 256; };
-  const size_t hap_bytes = NH * mh, read_bytes = NR * mr;
-  const size_t o_hb = 0, o_hp = up(hap_bytes), o_rb = o_hp + up(hap_bytes), o_rq = o_rb + up(read_bytes),
-               o_ri = o_rq + up(read_bytes), o_rd = o_ri + up(read_bytes), o_gc = o_rd + up(read_bytes),
-               o_hl = o_gc + up(read_bytes), o_rl = o_hl + up(NH * 8), total = o_rl + up(NR * 8);
+  const PdInputLayout in(NH, NR, mh, mr);
   int rc;
-  if ((rc = c->inputs.reserve(total)) || (rc = c->stage_in.reserve(total))) return rc;
+  if ((rc = c->inputs.reserve(in.total)) || (rc = c->stage_in.reserve(in.total))) return rc;
   unsigned char* d = c->inputs.as<unsigned char>();
   {
     unsigned char* h = c->stage_in.as<unsigned char>();
@@ -1205,32 +1180,31 @@ int pd_run_multi_locked(gklhip_pdhmm_ctx* c, std::vector<PdMultiRegion>& R) {
       const PdProblem& q = R[(size_t)k].q;
       const size_t h0 = (size_t)regions[(size_t)k].hap_base, r0 = (size_t)regions[(size_t)k].read_base;
       const size_t nh = (size_t)q.n_hap_items, nr = (size_t)q.n_read_items, qh = (size_t)q.max_hap_len, qr = (size_t)q.max_read_len;
-      rows(h + o_hb + h0 * mh, mh, q.hap_bases, qh, nh); rows(h + o_hp + h0 * mh, mh, q.hap_pdbases, qh, nh);
-      rows(h + o_rb + r0 * mr, mr, q.read_bases, qr, nr); rows(h + o_rq + r0 * mr, mr, q.read_qual, qr, nr);
-      rows(h + o_ri + r0 * mr, mr, q.read_ins_qual, qr, nr); rows(h + o_rd + r0 * mr, mr, q.read_del_qual, qr, nr);
-      rows(h + o_gc + r0 * mr, mr, q.gcp, qr, nr);
-      memcpy(h + o_hl + h0 * 8, q.hap_lengths, nh * 8); memcpy(h + o_rl + r0 * 8, q.read_lengths, nr * 8);
+      rows(h + in.o_hb + h0 * mh, mh, q.hap_bases, qh, nh); rows(h + in.o_hp + h0 * mh, mh, q.hap_pdbases, qh, nh);
+      rows(h + in.o_rb + r0 * mr, mr, q.read_bases, qr, nr); rows(h + in.o_rq + r0 * mr, mr, q.read_qual, qr, nr);
+      rows(h + in.o_ri + r0 * mr, mr, q.read_ins_qual, qr, nr); rows(h + in.o_rd + r0 * mr, mr, q.read_del_qual, qr, nr);
+      rows(h + in.o_gc + r0 * mr, mr, q.gcp, qr, nr);
+      memcpy(h + in.o_hl + h0 * 8, q.hap_lengths, nh * 8); memcpy(h + in.o_rl + r0 * 8, q.read_lengths, nr * 8);
     }
-    PD_HIP_TRY(hipMemcpyAsync(d, h, total, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d, h, in.total, hipMemcpyHostToDevice, s));
   }
 
   // ---- job tables: the regions' plans, shifted to the concatenated indices, in one more pinned block ----
   const int entry_stride = ((int)mh + 2 * kLanes + 4 + 63) / 64 * 64;
-  const int carry_len = entry_stride;
   const int n_jobs_max = std::max(std::max(n_tab_units, n_hot_units), n_full_units + (int)n_general);
   const int n_blocks = std::max(1, std::min(std::max(n_jobs_max, (int)n_tail), 256 * 8));
   if ((rc = c->entries.reserve(NH * (size_t)entry_stride * 4))) return rc;
   if (n_tab_haps && (rc = c->entries_tab.reserve(2 * NH * (size_t)entry_stride * 4))) return rc;
   if ((rc = c->misc.reserve(kPdMiscBytes))) return rc;
-  if ((rc = c->carry.reserve((size_t)n_blocks * 2 * (6 * (size_t)carry_len + 64) * 8))) return rc;
+  if ((rc = c->carry.reserve((size_t)n_blocks * 2 * (6 * (size_t)entry_stride + 64) * 8))) return rc;   // (carry_len = entry_stride)
   if ((rc = c->sums_pin.reserve(NP * 8 + 4 * (64 + (size_t)kPdMaxRegions)))) return rc;
-  const size_t o_rg = 0, o_cl = o_rg + up(((size_t)K + 1) * sizeof(PdRegion)), o_cs = o_cl + up(n_chunks * kLanes * sizeof(PlanLane)),
-               o_cr = o_cs + up(n_chunks * 4), o_ho = o_cr + up(n_chunks * 4), o_tg = o_ho + up(NH * 4),
-               o_nc = o_tg + up(tab_group_start.size() * 4), o_cc = o_nc + up(NH), o_jp = o_cc + up(NH * 32), o_jn = o_jp + up(n_general * 4),
-               o_js = o_jn + up(n_general * 4), o_jf = o_js + up(n_general), o_fj = o_jf + up(n_general), o_fc = o_fj + up(n_general * 4),
-               o_tl = o_fc + 256, o_tp = o_tl + up(n_tail * kLanes * sizeof(PlanLane)), o_tn = o_tp + up(n_tail * 4),
-               o_ts = o_tn + up(n_tail * 4), staged_total = o_ts + up(n_tail),
-               o_jl = staged_total, jobs_total = o_jl + up(n_general * kLanes * sizeof(PlanLane));   // (a striped job's lane row stays unused)
+  const size_t o_rg = 0, o_cl = o_rg + pd_up(((size_t)K + 1) * sizeof(PdRegion)), o_cs = o_cl + pd_up(n_chunks * kLanes * sizeof(PlanLane)),
+               o_cr = o_cs + pd_up(n_chunks * 4), o_ho = o_cr + pd_up(n_chunks * 4), o_tg = o_ho + pd_up(NH * 4),
+               o_nc = o_tg + pd_up(tab_group_start.size() * 4), o_cc = o_nc + pd_up(NH), o_jp = o_cc + pd_up(NH * 32), o_jn = o_jp + pd_up(n_general * 4),
+               o_js = o_jn + pd_up(n_general * 4), o_jf = o_js + pd_up(n_general), o_fj = o_jf + pd_up(n_general), o_fc = o_fj + pd_up(n_general * 4),
+               o_tl = o_fc + 256, o_tp = o_tl + pd_up(n_tail * kLanes * sizeof(PlanLane)), o_tn = o_tp + pd_up(n_tail * 4),
+               o_ts = o_tn + pd_up(n_tail * 4), staged_total = o_ts + pd_up(n_tail),
+               o_jl = staged_total, jobs_total = o_jl + pd_up(n_general * kLanes * sizeof(PlanLane));   // (a striped job's lane row stays unused)
   if ((rc = c->jobs.reserve(jobs_total + 256)) || (rc = c->stage_jobs.reserve(staged_total + 256))) return rc;
   unsigned char* dj = c->jobs.as<unsigned char>();
   {
@@ -1271,72 +1245,35 @@ int pd_run_multi_locked(gklhip_pdhmm_ctx* c, std::vector<PdMultiRegion>& R) {
       for (const int32_t v : pl.tail_steps) *tn++ = v;
       for (const uint8_t v : pl.tail_striped) *ts++ = v;
     }
-    PD_HIP_TRY(hipMemcpyAsync(dj, hj, staged_total, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(dj, hj, staged_total, hipMemcpyHostToDevice, s));
   }
-  PD_HIP_TRY(hipMemsetAsync(c->misc.p, 0, kPdMiscBytes, s));
+  HIP_TRY(hipMemsetAsync(c->misc.p, 0, kPdMiscBytes, s));
 
-  const PdTables& t = pd_tables();
-  PdArgs a;
-  memset(&a, 0, sizeof a);
-  a.hap_bases = reinterpret_cast<const int8_t*>(d + o_hb);
-  a.hap_pdbases = reinterpret_cast<const int8_t*>(d + o_hp);
-  a.read_bases = reinterpret_cast<const int8_t*>(d + o_rb);
-  a.read_qual = reinterpret_cast<const int8_t*>(d + o_rq);
-  a.read_ins = reinterpret_cast<const int8_t*>(d + o_ri);
-  a.read_del = reinterpret_cast<const int8_t*>(d + o_rd);
-  a.gcp = reinterpret_cast<const int8_t*>(d + o_gc);
-  a.hap_len = reinterpret_cast<const int64_t*>(d + o_hl);
-  a.read_len = reinterpret_cast<const int64_t*>(d + o_rl);
-  a.batch = (int32_t)NP; a.max_hap = (int32_t)mh; a.max_read = (int32_t)mr;
+  PdArgs a = pd_common_args(c, in, PdJobOffsets{o_jl, o_jp, o_jn, o_js, o_cl, o_cs, o_cr, o_nc, o_cc, o_jf, o_fj, o_tg}, NH, (int32_t)mh,
+                            (int32_t)mr, entry_stride, n_tab_haps != 0);
+  a.batch = (int32_t)NP;
   a.cross_haps = 1;   // (cross layout; the pair index comes from the region table)
-  a.n_hap_items = (int32_t)NH;
-  a.q2err = c->tables.as<double>();
-  a.mm_prob = c->tables.as<double>() + t.q2err.size();
-  a.entries = c->entries.as<uint32_t>();
-  a.entry_stride = entry_stride;
   {
     void* dp = nullptr;
-    PD_HIP_TRY(hipHostGetDevicePointer(&dp, c->sums_pin.p, 0));
+    HIP_TRY(hipHostGetDevicePointer(&dp, c->sums_pin.p, 0));
     a.sums = static_cast<double*>(dp);
   }
   a.status = c->misc.as<int32_t>() + 64;   // one flag per region
-  a.next = c->misc.as<int32_t>() + 1;
-  a.carry = c->carry.as<double>();
-  a.carry_len = carry_len;
-  a.lanes = reinterpret_cast<const LaneSlot*>(dj + o_jl);
-  a.job_pair = reinterpret_cast<const int32_t*>(dj + o_jp);
-  a.job_steps = reinterpret_cast<const int32_t*>(dj + o_jn);
-  a.job_striped = dj + o_js;
   a.n_chunks_cross = 1;
-  a.cross_lanes = reinterpret_cast<const LaneSlot*>(dj + o_cl);
-  a.chunk_steps = reinterpret_cast<const int32_t*>(dj + o_cs);
-  a.chunk_rep = reinterpret_cast<const int32_t*>(dj + o_cr);
-  a.hap_ncls = n_tab_haps ? dj + o_nc : nullptr;
-  a.class_codes = reinterpret_cast<const uint32_t*>(dj + o_cc);
-  a.entries_tab = c->entries_tab.as<uint32_t>();
-  a.next_special = n_tab_haps ? reinterpret_cast<int32_t*>(c->entries_tab.as<uint32_t>() + NH * (size_t)entry_stride) : nullptr;
-  a.tab_group_start = reinterpret_cast<const int32_t*>(dj + o_tg);
-  a.job_flags = dj + o_jf;
-  a.full_jobs = reinterpret_cast<const int32_t*>(dj + o_fj);
   a.full_count = reinterpret_cast<const int32_t*>(dj + o_fc);
-  a.sb_stride = entry_stride / 64; a.ns_stride = entry_stride;
   a.regions = reinterpret_cast<const PdRegion*>(dj + o_rg);
   a.n_regions = K;
-#ifdef GKL_PD_PROF
-  a.prof = reinterpret_cast<unsigned long long*>(c->misc.as<char>() + 128);
-#endif
   const int32_t* d_ho = reinterpret_cast<const int32_t*>(dj + o_ho);
 
   hipLaunchKernelGGL(pdhmm_entries_kernel, dim3((unsigned)NH), dim3(kLanes), 0, s, a);   // one wavefront per haplotype item
-  PD_HIP_TRY(hipEventRecord(c->ev0, s));
+  HIP_TRY(hipEventRecord(c->ev0, s));
   if (n_tab_units > 0) {
     PdArgs at = a;
     at.hap_order = d_ho;
     at.n_cross_jobs = at.n_jobs = n_tab_units;
     at.multi_launch = kPdLaunchTab;
     at.next = c->misc.as<int32_t>() + 4;
-    if (c->fma_mode) hipLaunchKernelGGL((pdhmm_fwd_tab_kernel<true, true>), dim3(std::min(n_tab_units, n_blocks)), dim3(64), 0, s, at, t.initial_condition);
-    else             hipLaunchKernelGGL((pdhmm_fwd_tab_kernel<false, true>), dim3(std::min(n_tab_units, n_blocks)), dim3(64), 0, s, at, t.initial_condition);
+    pd_launch_fwd(c, pdhmm_fwd_tab_kernel<true, true>, pdhmm_fwd_tab_kernel<false, true>, std::min(n_tab_units, n_blocks), s, at);
   }
   if (n_hot_units > 0) {
     PdArgs ah = a;
@@ -1344,8 +1281,7 @@ int pd_run_multi_locked(gklhip_pdhmm_ctx* c, std::vector<PdMultiRegion>& R) {
     ah.n_cross_jobs = ah.n_jobs = n_hot_units;
     ah.multi_launch = kPdLaunchHot;
     ah.full_jobs = nullptr;
-    if (c->fma_mode) hipLaunchKernelGGL((pdhmm_fwd_kernel<true, false, true, true>), dim3(std::min(n_hot_units, n_blocks)), dim3(64), 0, s, ah, t.initial_condition);
-    else             hipLaunchKernelGGL((pdhmm_fwd_kernel<false, false, true, true>), dim3(std::min(n_hot_units, n_blocks)), dim3(64), 0, s, ah, t.initial_condition);
+    pd_launch_fwd(c, pdhmm_fwd_kernel<true, false, true, true>, pdhmm_fwd_kernel<false, false, true, true>, std::min(n_hot_units, n_blocks), s, ah);
   }
   if (n_full_units + (int)n_general > 0) {   // the listed jobs: the striped reads, all from the host's list
     PdArgs af = a;
@@ -1354,8 +1290,7 @@ int pd_run_multi_locked(gklhip_pdhmm_ctx* c, std::vector<PdMultiRegion>& R) {
     af.n_jobs = n_full_units + (int)n_general;
     af.multi_launch = kPdLaunchFull;
     af.next = c->misc.as<int32_t>() + 3;
-    if (c->fma_mode) hipLaunchKernelGGL((pdhmm_fwd_kernel<true, false, false, true>), dim3(std::min(af.n_jobs, n_blocks)), dim3(64), 0, s, af, t.initial_condition);
-    else             hipLaunchKernelGGL((pdhmm_fwd_kernel<false, false, false, true>), dim3(std::min(af.n_jobs, n_blocks)), dim3(64), 0, s, af, t.initial_condition);
+    pd_launch_fwd(c, pdhmm_fwd_kernel<true, false, false, true>, pdhmm_fwd_kernel<false, false, false, true>, std::min(af.n_jobs, n_blocks), s, af);
   }
   if (n_tail > 0) {   // every region's tail pairs, scalar-engine arithmetic (same stream: the carry rows are free again)
     PdArgs at = a;
@@ -1368,15 +1303,15 @@ int pd_run_multi_locked(gklhip_pdhmm_ctx* c, std::vector<PdMultiRegion>& R) {
     at.job_flags = nullptr;
     at.full_jobs = nullptr;
     at.next = c->misc.as<int32_t>() + 2;
-    hipLaunchKernelGGL((pdhmm_fwd_kernel<false, true, false, true>), dim3((unsigned)std::min<size_t>(n_tail, (size_t)n_blocks)), dim3(64), 0, s, at, t.initial_condition);
+    hipLaunchKernelGGL((pdhmm_fwd_kernel<false, true, false, true>), dim3((unsigned)std::min<size_t>(n_tail, (size_t)n_blocks)), dim3(64), 0, s, at, pd_tables().initial_condition);
   }
-  PD_HIP_TRY(hipEventRecord(c->ev1, s));
-  PD_HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(c->ev1, s));
+  HIP_TRY(hipGetLastError());
   double* sums = c->sums_pin.as<double>();
   int32_t* status = reinterpret_cast<int32_t*>(sums + NP);
-  PD_HIP_TRY(hipMemcpyAsync(status, c->misc.p, 4 * (64 + (size_t)K), hipMemcpyDeviceToHost, s));
-  PD_HIP_TRY(hipStreamSynchronize(s));
-  PD_HIP_TRY(hipEventElapsedTime(&c->last_ms, c->ev0, c->ev1));
+  HIP_TRY(hipMemcpyAsync(status, c->misc.p, 4 * (64 + (size_t)K), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  HIP_TRY(hipEventElapsedTime(&c->last_ms, c->ev0, c->ev1));
   c->last_routing[0] = (int32_t)n_tab_haps; c->last_routing[1] = (int32_t)n_hot_haps; c->last_routing[2] = (int32_t)n_full_haps;
   for (int k = 0; k < K; k++) {
     PdMultiRegion& r = R[(size_t)k];
@@ -1384,21 +1319,10 @@ int pd_run_multi_locked(gklhip_pdhmm_ctx* c, std::vector<PdMultiRegion>& R) {
     r.routing[0] = (int32_t)plans[(size_t)k].n_tab_haps; r.routing[1] = (int32_t)(plans[(size_t)k].n_clean_haps - plans[(size_t)k].n_tab_haps);
     r.routing[2] = (int32_t)((size_t)r.q.n_hap_items - plans[(size_t)k].n_clean_haps);
   }
-  // one finalisation over all pairs (log10 with the host libm, see pd_run_locked); a region with an input error keeps its output untouched
-  const std::function<void(int64_t, int64_t)> finalise = [&](int64_t lo, int64_t hi) {
-    int k = pd_region_of_pair(regions.data(), K, (int)lo);
-    for (int64_t i = lo; i < hi; i++) {
-      while (i >= regions[(size_t)k + 1].pair_base) k++;
-      if (status[64 + k] == 0) R[(size_t)k].out[i - regions[(size_t)k].pair_base] = std::log10(sums[i]) - t.initial_condition_log10;
-    }
-  };
-  static const int fin_threads = std::max(1, std::min(4, (int)std::thread::hardware_concurrency()));
-  try {
-    c->workers.parallel_for((int64_t)NP, fin_threads, finalise, 4096);
-  } catch (const std::bad_alloc&) {
-    return pd_fail(GKLHIP_ERR_OOM, "out of memory in the host finalisation");
-  }
-  return GKLHIP_OK;
+  // one finalisation over all pairs; a region with an input error keeps its output untouched
+  double* out[kPdMaxRegions];
+  for (int k = 0; k < K; k++) out[k] = R[(size_t)k].out;
+  return pd_finalise(c, sums, regions.data(), K, out, status + 64);
 }
 
 // process-wide, per device (gklhip_pdhmm_combine_counts): region calls computed, region calls that shared a launch set
@@ -1412,26 +1336,10 @@ void pd_count(int device, int64_t calls, int64_t shared, int64_t sets) {
 
 constexpr const char* kPdInputErrorText = "Error while calculating pdhmm. Input arrays aren't valid.";
 
-// pd_run_multi_locked behind the same fence as pd_run_locked: no C++ exception leaves, a failed launch set is drained.
-int pd_run_multi_guarded(gklhip_pdhmm_ctx* c, std::vector<PdMultiRegion>& R) {
-  int rc;
-  try { rc = pd_run_multi_locked(c, R); }
-  catch (const std::bad_alloc&) { rc = pd_fail(GKLHIP_ERR_OOM, "host memory allocation failed"); }
-  catch (const std::exception& e) { rc = pd_fail(GKLHIP_ERR_HIP, "%s", e.what()); }
-  catch (...) { rc = pd_fail(GKLHIP_ERR_HIP, "unexpected C++ exception"); }
-  if (rc != GKLHIP_OK) {
-    const std::string keep = g_pd_err;
-    if (c->stream) (void)hipStreamSynchronize(c->stream);
-    (void)hipGetLastError();
-    g_pd_err = keep;
-  }
-  return rc;
-}
-
 // Does the cross call fit a multi-region launch set on its own?
 bool pd_fits_multi(const PdProblem& q) {
   return q.cross_haps && (size_t)q.n_pairs <= kPdMultiMaxPairs &&
-         pd_input_bytes((size_t)q.n_hap_items, (size_t)q.n_read_items, (size_t)q.max_hap_len, (size_t)q.max_read_len) <= kPdStageBytes;
+         PdInputLayout((size_t)q.n_hap_items, (size_t)q.n_read_items, (size_t)q.max_hap_len, (size_t)q.max_read_len).total <= kPdStageBytes;
 }
 
 // ---- concurrent cross calls share launches (GKL_HIP_PDHMM_COMBINE=1; off by default) ----
@@ -1471,7 +1379,7 @@ const PdCombineConfig* pd_combine_config() {
   return &cfg;
 }
 
-// c->mu is held.  The call's own result: status (and g_pd_err), c->last_ms, c->last_routing.
+// c->mu is held.  The call's own result: status (and g_err), c->last_ms, c->last_routing.
 int pd_run_combined(gklhip_pdhmm_ctx* c, const PdProblem& q, double* out_host) {
   const PdCombineConfig& cfg = *pd_combine_config();
   PdCombiner& cb = g_pd_combiners[c->device];
@@ -1501,7 +1409,7 @@ int pd_run_combined(gklhip_pdhmm_ctx* c, const PdProblem& q, double* out_host) {
       auto fits_with = [&](const PdTicket* t) {
         const size_t p2 = pairs + (size_t)t->q.n_pairs, nh2 = nh + (size_t)t->q.n_hap_items, nr2 = nr + (size_t)t->q.n_read_items,
                      mh2 = std::max(mh, (size_t)t->q.max_hap_len), mr2 = std::max(mr, (size_t)t->q.max_read_len);
-        return p2 <= kPdMultiMaxPairs && pd_input_bytes(nh2, nr2, mh2, mr2) <= kPdStageBytes;
+        return p2 <= kPdMultiMaxPairs && PdInputLayout(nh2, nr2, mh2, mr2).total <= kPdStageBytes;
       };
       auto take = [&](PdTicket* t) {
         pairs += (size_t)t->q.n_pairs; nh += (size_t)t->q.n_hap_items; nr += (size_t)t->q.n_read_items;
@@ -1532,8 +1440,8 @@ int pd_run_combined(gklhip_pdhmm_ctx* c, const PdProblem& q, double* out_host) {
     try {
       std::vector<PdMultiRegion> R((size_t)n_taken);
       for (int k = 0; k < n_taken; k++) { R[(size_t)k].q = taken[k]->q; R[(size_t)k].out = taken[k]->out; }
-      rc = pd_run_multi_guarded(c, R);
-      if (rc != GKLHIP_OK) err = g_pd_err;
+      rc = pd_fenced(c, [&] { return pd_run_multi_locked(c, R); });
+      if (rc != GKLHIP_OK) err = g_err;
       for (int k = 0; k < n_taken; k++) {
         PdTicket* t = taken[k];
         t->rc = rc != GKLHIP_OK ? rc : (R[(size_t)k].flag != 0 ? GKLHIP_ERR_INVALID_ARG : GKLHIP_OK);
@@ -1552,7 +1460,7 @@ int pd_run_combined(gklhip_pdhmm_ctx* c, const PdProblem& q, double* out_host) {
   }
   c->last_ms = me.ms;
   for (int i = 0; i < 3; i++) c->last_routing[i] = me.routing[i];
-  return me.rc == GKLHIP_OK ? GKLHIP_OK : pd_fail(me.rc, "%s", me.err);
+  return me.rc == GKLHIP_OK ? GKLHIP_OK : fail(me.rc, "%s", me.err);
 }
 
 // a cross call on a context of this process, counted (gklhip_pdhmm_combine_counts); with the combiner on, through it
@@ -1567,10 +1475,10 @@ int pd_run_cross(gklhip_pdhmm_ctx* c, const PdProblem& q, double* out_host) {
 }  // namespace
 
 int gklhip_pdhmm_compute(gklhip_pdhmm_ctx* c, const gklhip_pdhmm_batch* b, double* out_host) {
-  if (!c) return pd_fail(GKLHIP_ERR_INVALID_ARG, "context is NULL (initNative not called)");
-  if (!b) return pd_fail(GKLHIP_ERR_INVALID_ARG, "batch is NULL");
+  if (!c) return fail(GKLHIP_ERR_INVALID_ARG, "context is NULL (initNative not called)");
+  if (!b) return fail(GKLHIP_ERR_INVALID_ARG, "batch is NULL");
   // IntelPDHMM.java:163-173
-  if (b->batch <= 0) return pd_fail(GKLHIP_ERR_INVALID_ARG, "batchSize must be greater than 0");
+  if (b->batch <= 0) return fail(GKLHIP_ERR_INVALID_ARG, "batchSize must be greater than 0");
   PdProblem q{b->batch, b->batch, b->batch, 0, b->max_hap_len, b->max_read_len, b->hap_bases, b->hap_pdbases,
               b->read_bases, b->read_qual, b->read_ins_qual, b->read_del_qual, b->gcp, b->hap_lengths, b->read_lengths, 0};
   const int rc = pd_validate(q, out_host);
@@ -1599,27 +1507,22 @@ int64_t gklhip_pdhmm_reference_batch_pairs(int32_t max_memory_mb, int32_t max_re
 }
 
 int gklhip_pdhmm_compute_cross_batched(gklhip_pdhmm_ctx* c, const gklhip_pdhmm_cross* x, int64_t ref_batch_pairs, double* out_host) {
-  if (!c) return pd_fail(GKLHIP_ERR_INVALID_ARG, "context is NULL (initNative not called)");
-  if (ref_batch_pairs < 0) return pd_fail(GKLHIP_ERR_INVALID_ARG, "ref_batch_pairs must not be negative");
-  if (!x) return pd_fail(GKLHIP_ERR_INVALID_ARG, "batch is NULL");
-  if (x->n_reads <= 0 || x->n_haps <= 0) return pd_fail(GKLHIP_ERR_INVALID_ARG, "no pairs to process");
-  PdProblem q{(int64_t)x->n_reads * x->n_haps, x->n_reads, x->n_haps, x->n_haps, x->max_hap_len, x->max_read_len,
-              x->hap_bases, x->hap_pdbases, x->read_bases, x->read_qual, x->read_ins_qual, x->read_del_qual, x->gcp,
-              x->hap_lengths, x->read_lengths, ref_batch_pairs};
-  const int rc = pd_validate(q, out_host);
+  if (!c) return fail(GKLHIP_ERR_INVALID_ARG, "context is NULL (initNative not called)");
+  PdProblem q;
+  const int rc = pd_cross_problem(x, ref_batch_pairs, out_host, &q);
   return rc ? rc : pd_run_cross(c, q, out_host);
 }
 
 int gklhip_pdhmm_compute_cross_multi(gklhip_pdhmm_ctx* c, int32_t n_regions, const gklhip_pdhmm_cross* regions, const int64_t* ref_batch_pairs,
                                      double* const* out_host, int32_t* status_out) {
-  if (!c) return pd_fail(GKLHIP_ERR_INVALID_ARG, "context is NULL (initNative not called)");
-  if (n_regions <= 0) return pd_fail(GKLHIP_ERR_INVALID_ARG, "no regions to process");
-  if (!regions || !out_host) return pd_fail(GKLHIP_ERR_INVALID_ARG, "regions / out_host is NULL");
+  if (!c) return fail(GKLHIP_ERR_INVALID_ARG, "context is NULL (initNative not called)");
+  if (n_regions <= 0) return fail(GKLHIP_ERR_INVALID_ARG, "no regions to process");
+  if (!regions || !out_host) return fail(GKLHIP_ERR_INVALID_ARG, "regions / out_host is NULL");
   int first_rc = GKLHIP_OK, first_k = n_regions;   // the failing region with the lowest index
   std::string first_err;
-  auto note = [&](int k, int rc) {   // (g_pd_err holds region k's message)
+  auto note = [&](int k, int rc) {   // (g_err holds region k's message)
     if (status_out) status_out[k] = rc;
-    if (rc != GKLHIP_OK && k < first_k) { first_k = k; first_rc = rc; first_err = g_pd_err; }
+    if (rc != GKLHIP_OK && k < first_k) { first_k = k; first_rc = rc; first_err = g_err; }
   };
   try {
     // the argument checks of gklhip_pdhmm_compute_cross_batched, region by region, before anything touches the device
@@ -1627,23 +1530,13 @@ int gklhip_pdhmm_compute_cross_multi(gklhip_pdhmm_ctx* c, int32_t n_regions, con
     std::vector<int32_t> index;
     R.reserve((size_t)n_regions);
     for (int32_t k = 0; k < n_regions; k++) {
-      const gklhip_pdhmm_cross* x = &regions[k];
-      const int64_t rb = ref_batch_pairs ? ref_batch_pairs[k] : 0;
-      int rc = GKLHIP_OK;
-      if (rb < 0) rc = pd_fail(GKLHIP_ERR_INVALID_ARG, "ref_batch_pairs must not be negative");
-      else if (x->n_reads <= 0 || x->n_haps <= 0) rc = pd_fail(GKLHIP_ERR_INVALID_ARG, "no pairs to process");
       PdMultiRegion r;
-      if (rc == GKLHIP_OK) {
-        r.q = PdProblem{(int64_t)x->n_reads * x->n_haps, x->n_reads, x->n_haps, x->n_haps, x->max_hap_len, x->max_read_len,
-                        x->hap_bases, x->hap_pdbases, x->read_bases, x->read_qual, x->read_ins_qual, x->read_del_qual, x->gcp,
-                        x->hap_lengths, x->read_lengths, rb};
-        r.out = out_host[k];
-        rc = pd_validate(r.q, r.out);
-      }
+      r.out = out_host[k];
+      const int rc = pd_cross_problem(&regions[k], ref_batch_pairs ? ref_batch_pairs[k] : 0, r.out, &r.q);
       note(k, rc);
       if (rc == GKLHIP_OK) { R.push_back(r); index.push_back(k); }
     }
-    if (R.empty()) return pd_fail(first_rc, "%s", first_err.c_str());
+    if (R.empty()) return fail(first_rc, "%s", first_err.c_str());
     size_t pairs = 0;
     for (const PdMultiRegion& r : R) pairs += (size_t)r.q.n_pairs;
     const bool fits = !c->remote && R.size() <= (size_t)kPdMaxRegions && pairs <= kPdMultiMaxPairs && pd_multi_input_bytes(R) <= kPdStageBytes;
@@ -1664,24 +1557,24 @@ int gklhip_pdhmm_compute_cross_multi(gklhip_pdhmm_ctx* c, int32_t n_regions, con
       for (int j = 0; j < 3; j++) c->last_routing[j] = routing[j];
     } else {
       std::lock_guard<std::mutex> lock(c->mu);
-      const int rc = pd_run_multi_guarded(c, R);
+      const int rc = pd_fenced(c, [&] { return pd_run_multi_locked(c, R); });
       pd_count(c->device, (int64_t)R.size(), R.size() > 1 ? (int64_t)R.size() : 0, 1);
       for (size_t i = 0; i < R.size(); i++) {
-        if (rc != GKLHIP_OK) { note(index[i], rc); continue; }   // (g_pd_err: the launch set's message)
-        note(index[i], R[i].flag != 0 ? pd_fail(GKLHIP_ERR_INVALID_ARG, "%s", kPdInputErrorText) : GKLHIP_OK);
+        if (rc != GKLHIP_OK) { note(index[i], rc); continue; }   // (g_err: the launch set's message)
+        note(index[i], R[i].flag != 0 ? fail(GKLHIP_ERR_INVALID_ARG, "%s", kPdInputErrorText) : GKLHIP_OK);
       }
     }
   } catch (const std::bad_alloc&) {
-    return pd_fail(GKLHIP_ERR_OOM, "host memory allocation failed");
+    return fail(GKLHIP_ERR_OOM, "host memory allocation failed");
   } catch (...) {
-    return pd_fail(GKLHIP_ERR_HIP, "unexpected C++ exception");
+    return fail(GKLHIP_ERR_HIP, "unexpected C++ exception");
   }
-  return first_rc == GKLHIP_OK ? GKLHIP_OK : pd_fail(first_rc, "%s", first_err.c_str());
+  return first_rc == GKLHIP_OK ? GKLHIP_OK : fail(first_rc, "%s", first_err.c_str());
 }
 
 int gklhip_pdhmm_combine_counts(int device, int64_t out[3], int reset) {
-  if (!out) return pd_fail(GKLHIP_ERR_INVALID_ARG, "NULL argument");
-  if (device >= kPdCountDevices) return pd_fail(GKLHIP_ERR_INVALID_ARG, "device %d", device);
+  if (!out) return fail(GKLHIP_ERR_INVALID_ARG, "NULL argument");
+  if (device >= kPdCountDevices) return fail(GKLHIP_ERR_INVALID_ARG, "device %d", device);
   out[0] = out[1] = out[2] = 0;
   for (int d = device < 0 ? 0 : device; d < (device < 0 ? kPdCountDevices : device + 1); d++)
     for (int i = 0; i < 3; i++) out[i] += reset ? g_pd_counts[d][i].exchange(0) : g_pd_counts[d][i].load();
