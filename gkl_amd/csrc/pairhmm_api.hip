@@ -177,6 +177,11 @@ int gklhip_release_idle(gklhip_ctx* c, int32_t* streams_released) {
     }
   }
   for (DevCtx* d : c->dev) n += trim_streams(d);
+  // the staging lanes of multi calls (no streams: nothing to count; their buffers are what an idle context gives back --
+  // nothing of theirs is in flight outside a call, and this thread holds the context's lock)
+  for (DevCtx* d : c->lanes) dev_done(d);
+  c->lanes.clear();
+  for (auto& r : c->multi_last) r.first = -1;
   // the process's small-call combiner on these devices: its flight streams, when no host call is inside the library and
   // no set has been launched for a second
   if (g_host_calls_in_flight.load() == 0)
@@ -295,6 +300,7 @@ static int compute_device_impl(gklhip_ctx* c, const gklhip_batch* dev_batch, dou
   if (mode != GKLHIP_FINALIZE_DEVICE_F64 && mode != GKLHIP_FINALIZE_DEVICE_REF32) mode = GKLHIP_FINALIZE_DEVICE_F64;
   hipStream_t s = static_cast<hipStream_t>(hip_stream);  // NULL = HIP's default stream
   c->last_reads = dev_batch->n_reads; c->last_haps = dev_batch->n_haps;
+  c->after_multi = false;
   // which engine set: the one that served this stream last; a call on a NEW stream while the other set is busy with
   // another stream's work takes (first: creates) the second set
   int set = 0;
@@ -362,24 +368,16 @@ static bool fault_due() {
   return nth >= from && nth < from + g_fault_count.load();
 }
 
-static int compute_impl(gklhip_ctx* c, const gklhip_batch* hb, double* out_host) {
-  if (!c) return fail(GKLHIP_ERR_INVALID_ARG, "context is NULL (initNative not called)");
-  int rc = validate(hb);
-  if (rc) return rc;
+// One checked host-buffer call (at least one pair, an output array) on a context whose lock the caller holds.
+static int compute_locked(gklhip_ctx* c, const gklhip_batch* hb, double* out_host) {
+  int rc;
   const int64_t n_pairs = (int64_t)hb->n_reads * hb->n_haps;
-  if (n_pairs == 0) return GKLHIP_OK;
-  if (!out_host) return fail(GKLHIP_ERR_INVALID_ARG, "output array is NULL");
   if (c->remote) {
-    std::lock_guard<std::mutex> lock(c->mu);
     std::string err;
     rc = gklhip_remote::compute(c->remote, hb, out_host, &c->stats, &err);
     return rc == GKLHIP_OK ? rc : fail(rc, "%s", err.c_str());
   }
-  if (fault_due()) {
-    for (int64_t i = 0; i < n_pairs; i++) out_host[i] = std::numeric_limits<double>::quiet_NaN();
-    return fail(GKLHIP_ERR_HIP, "injected fault (GKLHIP_FAULT_INJECT)");
-  }
-  std::lock_guard<std::mutex> lock(c->mu);
+  c->after_multi = false;
   c->last_reads = hb->n_reads; c->last_haps = hb->n_haps;
   if (c->dev.size() == 1 && c->host_shards > 1 && n_pairs >= kHostShardPairs && hb->n_reads >= 2 * c->host_shards) {
     // a big call on one device: two (GKL_HIP_HOST_SHARDS) half-batches on twin engines
@@ -402,6 +400,80 @@ static int compute_impl(gklhip_ctx* c, const gklhip_batch* hb, double* out_host)
     return rc;
   }
   return multi_compute_host(c, c->dev, hb, out_host);
+}
+
+static int compute_impl(gklhip_ctx* c, const gklhip_batch* hb, double* out_host) {
+  if (!c) return fail(GKLHIP_ERR_INVALID_ARG, "context is NULL (initNative not called)");
+  int rc = validate(hb);
+  if (rc) return rc;
+  const int64_t n_pairs = (int64_t)hb->n_reads * hb->n_haps;
+  if (n_pairs == 0) return GKLHIP_OK;
+  if (!out_host) return fail(GKLHIP_ERR_INVALID_ARG, "output array is NULL");
+  if (!c->remote && fault_due()) {
+    for (int64_t i = 0; i < n_pairs; i++) out_host[i] = std::numeric_limits<double>::quiet_NaN();
+    return fail(GKLHIP_ERR_HIP, "injected fault (GKLHIP_FAULT_INJECT)");
+  }
+  std::lock_guard<std::mutex> lock(c->mu);
+  return compute_locked(c, hb, out_host);
+}
+
+// Several region calls, the ones the single call would defer in shared sets of launches (dev_compute_host_multi); see the
+// header for the contract.
+static int compute_multi_impl(gklhip_ctx* c, int32_t n_regions, const gklhip_batch* regions, double* const* out_host, int32_t* status_out) {
+  if (!c) return fail(GKLHIP_ERR_INVALID_ARG, "context is NULL (initNative not called)");
+  if (n_regions <= 0) return fail(GKLHIP_ERR_INVALID_ARG, "no regions to process");
+  if (!regions || !out_host) return fail(GKLHIP_ERR_INVALID_ARG, "regions / out_host is NULL");
+  int first_rc = GKLHIP_OK, first_k = n_regions;   // the failing region with the lowest index
+  std::string first_err;
+  auto note = [&](int k, int rc) {   // (g_err holds region k's message)
+    if (status_out) status_out[k] = rc;
+    if (rc != GKLHIP_OK && k < first_k) { first_k = k; first_rc = rc; first_err = g_err; }
+  };
+  // the argument checks of gklhip_compute, region by region, before anything touches the device
+  std::vector<MultiRegion> R;
+  for (int32_t k = 0; k < n_regions; k++) {
+    int rc = validate(&regions[k]);
+    const int64_t n_pairs = rc ? 0 : (int64_t)regions[k].n_reads * regions[k].n_haps;
+    if (rc == GKLHIP_OK && n_pairs > 0 && !out_host[k]) rc = fail(GKLHIP_ERR_INVALID_ARG, "output array is NULL");
+    note(k, rc);
+    if (rc != GKLHIP_OK || n_pairs == 0) continue;
+    MultiRegion r;
+    r.hb = &regions[k]; r.out = out_host[k]; r.index = k;
+    R.push_back(r);
+  }
+  std::lock_guard<std::mutex> lock(c->mu);
+  gklhip_stats sum;
+  memset(&sum, 0, sizeof sum);
+  auto add_stats = [&](const gklhip_stats& s) {
+    sum.n_pairs += s.n_pairs; sum.cells += s.cells; sum.cells_fp64 += s.cells_fp64;
+    if (s.n_fallback < 0 || sum.n_fallback < 0) sum.n_fallback = -1; else sum.n_fallback += s.n_fallback;
+  };
+  // shared sets: one device, whose engine stages the regions that qualify on its lanes; a client context, several
+  // devices: every region through the single-call path
+  const bool sets = !c->remote && c->dev.size() == 1;
+  if (sets) {
+    const int rc = dev_compute_host_multi(c->dev[0], c->lanes, R);
+    if (rc != GKLHIP_OK) return rc;
+  }
+  for (MultiRegion& r : R) {
+    if (!sets || r.alone) {
+      r.lane = -1;
+      r.rc = compute_locked(c, r.hb, r.out);
+      r.stats = c->stats;
+    } else {
+      g_err = r.err;
+    }
+    note(r.index, r.rc);
+    if (r.rc == GKLHIP_OK) add_stats(r.stats);
+  }
+  c->stats = sum;
+  if (!c->remote) {
+    c->multi_last.assign((size_t)n_regions, std::make_pair(-1, (int64_t)0));
+    for (const MultiRegion& r : R)
+      if (r.rc == GKLHIP_OK) c->multi_last[(size_t)r.index] = std::make_pair(r.lane, r.stats.n_pairs);
+    c->after_multi = true;
+  }
+  return first_rc == GKLHIP_OK ? GKLHIP_OK : fail(first_rc, "%s", first_err.c_str());
 }
 
 // A client process (GKL_HIP_SERVER set; decided once per process) makes no HIP call: its "page-locked" buffers are plain
@@ -457,6 +529,7 @@ static int get_raw_impl(gklhip_ctx* ctx, float* raw32, double* raw64, uint8_t* u
   if (!ctx) return fail(GKLHIP_ERR_INVALID_ARG, "context is NULL");
   if (ctx->remote) return fail(GKLHIP_ERR_UNSUPPORTED, "gklhip_get_raw: the raw sums stay on the PairHMM server (client context)");
   std::lock_guard<std::mutex> lock(ctx->mu);
+  if (ctx->after_multi) return fail(GKLHIP_ERR_INVALID_ARG, "no completed call to read back (the last call was gklhip_compute_multi: gklhip_get_raw_region)");
   int64_t n_fallback = 0;
   bool any = false;
   const std::vector<DevCtx*>& list = ctx->last ? *ctx->last : ctx->dev;
@@ -481,6 +554,26 @@ static int get_raw_impl(gklhip_ctx* ctx, float* raw32, double* raw64, uint8_t* u
   if (!any) return fail(GKLHIP_ERR_INVALID_ARG, "no completed call to read back");
   ctx->stats.n_fallback = n_fallback;
   HIP_TRY(hipSetDevice(ctx->dev[0]->device));
+  return GKLHIP_OK;
+}
+
+static int get_raw_region_impl(gklhip_ctx* ctx, int32_t region, float* raw32, double* raw64, uint8_t* used64) {
+  if (!ctx) return fail(GKLHIP_ERR_INVALID_ARG, "context is NULL");
+  if (ctx->remote) return fail(GKLHIP_ERR_UNSUPPORTED, "gklhip_get_raw_region: the raw sums stay on the PairHMM server (client context)");
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  if (!ctx->after_multi) return fail(GKLHIP_ERR_INVALID_ARG, "no completed multi call to read back");
+  if (region < 0 || (size_t)region >= ctx->multi_last.size()) return fail(GKLHIP_ERR_INVALID_ARG, "region %d of %zu", region, ctx->multi_last.size());
+  const int lane = ctx->multi_last[(size_t)region].first;
+  const size_t n = (size_t)ctx->multi_last[(size_t)region].second;
+  if (lane < 0)
+    return fail(GKLHIP_ERR_UNSUPPORTED, "region %d: its raw sums were not kept (it failed, was empty, ran alone, or a later set of the call took its staging lane)", region);
+  DevCtx* c = ctx->lanes[(size_t)lane];
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t s = ctx->dev[0]->stream;   // (the region's set has ended: any stream will do)
+  if (raw32) HIP_TRY(hipMemcpyAsync(raw32, c->raw32.p, n * 4, hipMemcpyDeviceToHost, s));
+  if (raw64) HIP_TRY(hipMemcpyAsync(raw64, c->raw64.p, n * 8, hipMemcpyDeviceToHost, s));
+  if (used64) HIP_TRY(hipMemcpyAsync(used64, c->used64.p, n, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
   return GKLHIP_OK;
 }
 
@@ -522,6 +615,8 @@ int gklhip_init_devices(const gklhip_config* cfg, const int32_t* devices, int32_
 int gklhip_compute_device(gklhip_ctx* c, const gklhip_batch* dev_batch, double* out_dev, void* hip_stream) { return guarded([&] { return compute_device_impl(c, dev_batch, out_dev, hip_stream); }); }
 int gklhip_compute(gklhip_ctx* c, const gklhip_batch* hb, double* out_host) { return guarded([&] { return compute_impl(c, hb, out_host); }); }
 int gklhip_get_raw(gklhip_ctx* ctx, float* raw32, double* raw64, uint8_t* used64) { return guarded([&] { return get_raw_impl(ctx, raw32, raw64, used64); }); }
+int gklhip_compute_multi(gklhip_ctx* c, int32_t n_regions, const gklhip_batch* regions, double* const* out_host, int32_t* status_out) { return guarded([&] { return compute_multi_impl(c, n_regions, regions, out_host, status_out); }); }
+int gklhip_get_raw_region(gklhip_ctx* ctx, int32_t region, float* raw32, double* raw64, uint8_t* used64) { return guarded([&] { return get_raw_region_impl(ctx, region, raw32, raw64, used64); }); }
 int gklhip_get_step_times(gklhip_ctx* ctx, int32_t steps_back, float* ms_main, float* ms_fallback, float* ms_total) { return guarded([&] { return get_step_times_impl(ctx, steps_back, ms_main, ms_fallback, ms_total); }); }
 int gklhip_rccl_selftest(int32_t device) { return guarded([&] { return rccl_selftest_impl(device); }); }
 int gklhip_init(const gklhip_config* cfg, gklhip_ctx** out_ctx) { return guarded([&] { return init_impl(cfg, out_ctx); }); }

@@ -8,6 +8,7 @@
 
 #include "../../include/gkl_hip_pairhmm.h"
 #include "pairhmm_fwd_kernel.h"
+#include "pairhmm_multi_sets.h"
 
 namespace gklhip {
 
@@ -115,22 +116,23 @@ struct SmallCall {
   int32_t fused;  // the whole pair in one wavefront (pair_fused_block) instead of the packed fp32 pass + per-pair policy
   int32_t speculate;  // host side only: the context asked for the fp64 pass beside the fp32 one when the call runs alone
 };
-constexpr int kMultiMax = 16;
+// A set holds up to kMultiMax (64) calls, all in the kernel arguments (776 bytes; pairhmm_multi_sets.h: the limits, the
+// prefix sums and the lookup, shared with the host).
 struct MultiArgs {
   const SmallCall* call[kMultiMax];  // prep: the descriptors in the pinned staging blocks; later kernels: the device copies
   int32_t begin[kMultiMax + 1];      // first block of each call in this launch
   int32_t n;
 };
+static_assert(sizeof(MultiArgs) == 776, "the set's table travels in the kernel arguments");
+// (the block index and begin[] are wavefront-uniform: a scalar binary search over the kernel arguments)
 __device__ __forceinline__ int multi_find(const MultiArgs& m, int block) {
-  int r = 0;
-  for (int i = 1; i < m.n; i++) r += block >= m.begin[i] ? 1 : 0;
-  return __builtin_amdgcn_readfirstlane(r);
+  return __builtin_amdgcn_readfirstlane(multi_find(m.begin, m.n, block));
 }
 __global__ __launch_bounds__(kPrepBlock) void prep_multi_kernel(MultiArgs m) {
   const int r = multi_find(m, (int)blockIdx.x);
   const SmallCall* c = m.call[r];
   const PrepArgs a = c->prep;
-  prep_block(a, (int)blockIdx.x - m.begin[r], c->prep_grid);
+  prep_block(a, multi_local(m.begin, r, (int)blockIdx.x), c->prep_grid);
 }
 template <bool FMA, int kRplF32>  // kRplF32: the widest fp32 variant (2, 4 or this many rows per lane)
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void fwd_stream_multi_kernel(MultiArgs m) {
@@ -139,7 +141,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void fw
   __shared__ __attribute__((aligned(16))) unsigned char lds[kLds];
   const int r = multi_find(m, (int)blockIdx.x);
   const SmallCall* c = m.call[r];
-  const int block = (int)blockIdx.x - m.begin[r];
+  const int block = multi_local(m.begin, r, (int)blockIdx.x);
   const FwdArgs<float> a = c->f;
   const int rpl = c->rpl_main;
   if (rpl == 2)      fwd_stream_block<float, 2, FMA>(a, block, lds);
@@ -153,7 +155,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) void pa
                 WaveJob<double, 4, FMA>::kLdsBytes <= WaveJob<double, kRplF64, FMA>::kLdsBytes, "LDS of the widest job");
   const int r = multi_find(m, (int)blockIdx.x);
   const SmallCall* c = m.call[r];
-  const int64_t p = (int)blockIdx.x - m.begin[r];
+  const int64_t p = multi_local(m.begin, r, (int)blockIdx.x);
   const FwdArgs<double> d = c->d;
   const PairPolicyArgs q = c->q;
   pair_policy_block<kRplF64, FMA>(d, q, p, lds);  // (rows per lane by the pair's own read)
@@ -164,7 +166,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kRplF64 <= 4
   __shared__ __attribute__((aligned(16))) unsigned char lds[PairFusedLds<kRplF64, FMA>::bytes];
   const int r = multi_find(m, (int)blockIdx.x);
   const SmallCall* c = m.call[r];
-  const int64_t p = (int)blockIdx.x - m.begin[r];
+  const int64_t p = multi_local(m.begin, r, (int)blockIdx.x);
   const FwdArgs<float> f = c->f;
   const FwdArgs<double> d = c->d;
   const PairPolicyArgs q = c->q;

@@ -179,4 +179,38 @@ int dev_init(const gklhip_config& cfg, int dev, int ndev, DevCtx** out) {
   return GKLHIP_OK;
 }
 
+// A staging lane of `parent` (gklhip_compute_multi: a set of n regions needs n staged calls alive at once).  A lane is a
+// DevCtx used for its per-call staging state only -- plan slots, pinned result words, raw sums and flags, the prep
+// kernel's outputs -- over the PARENT's device tables; it has no stream and no event ring of its own (every stream is a
+// hardware queue: docs/NOTES.md 48).  Its calls are only ever staged (run_device with defer->only) and leave through the
+// combiner, on the parent's stream or a flight stream; the set they ride in has ended before the multi call returns, so
+// the slot events below are never recorded again -- they exist because run_device waits for them before it writes a slot.
+// dev_done takes a lane as it takes an engine.
+int lane_init(DevCtx* parent, DevCtx** out) {
+  *out = nullptr;
+  HIP_TRY(hipSetDevice(parent->device));
+  DevCtx* c = new (std::nothrow) DevCtx();
+  if (!c) return fail(GKLHIP_ERR_OOM, "context allocation failed");
+  c->cfg = parent->cfg;
+  c->device = parent->device;
+  c->n_cus = parent->n_cus;
+  c->n_xcds = parent->n_xcds;
+  c->asm_general = parent->asm_general;
+  c->speculate_fp64 = parent->speculate_fp64;
+  c->lds_oob_zero = parent->lds_oob_zero;
+  c->dt32 = parent->dt32;   // (the parent's tab32 / tab64 own the memory)
+  c->dt64 = parent->dt64;
+  memset(&c->stats, 0, sizeof c->stats);
+  for (int k = 0; k < 2; k++)
+    if (hipEventCreateWithFlags(&c->stage_free_slot[k], hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&c->plan_unused_slot[k], hipEventDisableTiming) != hipSuccess ||
+        hipEventRecord(c->stage_free_slot[k], parent->stream) != hipSuccess || hipEventRecord(c->plan_unused_slot[k], parent->stream) != hipSuccess) {
+      (void)hipGetLastError();
+      dev_done(c);
+      return fail(GKLHIP_ERR_HIP, "hipEventCreate failed (staging lane)");
+    }
+  *out = c;
+  return GKLHIP_OK;
+}
+
 }  // namespace

@@ -180,6 +180,9 @@ void launch_long_jobs(const FwdArgs<T>& a, int fma, int n_blocks, int max_read_l
 // A small host-buffer call, planned and staged but not launched: SmallCombiner decides how it reaches the device (on
 // its own, or in one set of launches with the calls of other threads).
 struct SmallLaunch {
+  bool only = false;    // in: a call that cannot be deferred is not run at all (run_device returns before it touches the device)
+  bool probe = false;   // in, with `only`: nothing is staged either -- `qualifies` and call.fused are the answer
+  bool qualifies = false;
   bool filled = false;
   SmallCall call;                          // the descriptor
   const SmallCall* desc_pinned = nullptr;  // ... as the device sees it in the pinned staging block (the prep kernel reads this one)
@@ -304,6 +307,25 @@ void launch_pair_fused(const FwdArgs<float>& f, const FwdArgs<double>& d, const 
   else     hipLaunchKernelGGL((pairhmm_pair_fused_kernel<kRplF64, false>), grid, block, 0, s, f, d, q);
 }
 
+// A small plan (GATK-sized call) is PULLED from the pinned staging block by the prep kernel itself: no copy-engine hop at all.
+bool plan_pulled(size_t plan_bytes) { return plan_bytes < (1u << 20); }  // (256 KB .. 2 MB measure within 2 % on calls of 4k-50k pairs, 1 MB best)
+// Policy + fp64 recomputation of one pair per wavefront (the kernel holds at most 64 x kRplF64 - 1 rows).
+bool per_pair_policy_call(const DevCtx* c, int64_t n_pairs, int n_long64, int max_read_len) {
+  return !c->cfg.use_double && n_pairs <= kDirectPairs && n_long64 == 0 && max_read_len <= kLanes * kRplF64 - 1;
+}
+// Which host-buffer calls are deferred -- planned and staged by run_device, launched by the small-call combiner, alone or
+// in one set of launches with others (concurrent callers' calls, the regions of one gklhip_compute_multi): inputs inline
+// (<= kSmallBatchBytes), not switched off (GKL_HIP_COMBINE=0), and -- once the call is planned -- plan block pulled,
+// per-pair call, no long read, host-exact packed finalisation, no event recording, at most kTwoStepFrom pairs.
+// Without a plan: what a host call knows before run_device has planned it (whether to offer deferral at all).
+bool small_call_defers(const DevCtx* c, bool inline_host, int finalize_mode = kModePacked, int64_t n_pairs = 0, const Plan* plan = nullptr,
+                       size_t plan_bytes = 0, int n_long64 = 0) {
+  if (!g_env.combine || !inline_host) return false;
+  if (!plan) return true;
+  return plan_pulled(plan_bytes) && c->cfg.record_events == 0 && per_pair_policy_call(c, n_pairs, n_long64, plan->max_read_len) &&
+         plan->long_reads.empty() && finalize_mode == kModePacked && plan->n_chunks > 0 && n_pairs <= kTwoStepFrom;
+}
+
 // The whole device-side pipeline on stream `s`: 7 launches in the policy mode (prep, fp32 forward, the three launches of
 // policy + planning of the fp64 pass, fp64 forward over the job list, log10 / packed words of the recomputed pairs; + the
 // log10 of the kept pairs on a side stream in the device finalisation modes), 3-4 for calls of up to 65 536 pairs (prep,
@@ -313,6 +335,8 @@ void launch_pair_fused(const FwdArgs<float>& f, const FwdArgs<double>& d, const 
 // copy for plan and inputs).
 // `defer` (host-buffer calls on an idle context only): a call that takes the small-call path -- pulled plan block,
 // per-pair policy -- is planned and staged but NOT launched; its descriptor is returned in *defer (filled = true).
+// With defer->only, a call that does not qualify is not run at all (the regions of a multi call are staged on lanes that
+// have no stream of their own); with defer->probe on top, the call is only planned and asked whether it qualifies.
 int run_device(DevCtx* c, const gklhip_batch* db, double* out_dev, int finalize_mode, hipStream_t s, bool inline_host,
                SmallLaunch* defer = nullptr) {
   const int n_reads = db->n_reads, n_haps = db->n_haps;
@@ -364,6 +388,18 @@ int run_device(DevCtx* c, const gklhip_batch* db, double* out_dev, int finalize_
   carry_len = (carry_len + 63) / 64 * 64;
   const size_t rl = (size_t)db->read_off[n_reads], hl = (size_t)db->hap_off[n_haps];
   const PlanLayout L = layout_for(plan, n_reads, n_haps, long_lanes.size(), long_jobs.size(), inline_host ? rl : 0, inline_host ? hl : 0);
+  const bool pull = plan_pulled(L.total);
+  const bool per_pair_call = per_pair_policy_call(c, n_pairs, n_long64, plan.max_read_len);
+  // ... the tiny ones (one GATK active region) with the fp32 recurrence in the same wavefront and launch as the policy
+  const bool fused_env = g_env.fused_pairs;
+  const int64_t fused_max = g_env.fused_max >= 0 ? g_env.fused_max : (int64_t)kTwoStepFrom;
+  const bool fused_call = per_pair_call && fused_env && n_pairs <= fused_max && n_long_main == 0 && c->cfg.rows_per_lane == 0;
+  const bool deferred_launch = defer && small_call_defers(c, inline_host, finalize_mode, n_pairs, &plan, L.total, n_long64);
+  if (defer && defer->only) {
+    defer->qualifies = deferred_launch;
+    defer->call.fused = fused_call ? 1 : 0;
+    if (!deferred_launch || defer->probe) return GKLHIP_OK;   // (nothing staged, nothing launched)
+  }
 
   // ---- stage + upload plan ----
   int rc;
@@ -440,15 +476,6 @@ int run_device(DevCtx* c, const gklhip_batch* db, double* out_dev, int finalize_
   if (c->have_call_done && c->last_stream != s) HIP_TRY(hipStreamWaitEvent(s, c->call_done, 0));
   // Big plans ride the upload stream (the copy overlaps the previous call's kernels); a small plan (GATK-sized
   // call) is PULLED from the pinned staging block by the prep kernel itself: no copy-engine hop at all.
-  const bool pull = L.total < (1u << 20);  // (256 KB .. 2 MB measure within 2 % on calls of 4k-50k pairs, 1 MB best)
-  // (the one-pair-per-wavefront policy kernel holds at most 64 x kRplF64 - 1 rows)
-  const bool per_pair_call = !use_double && n_pairs <= kDirectPairs && n_long64 == 0 && plan.max_read_len <= kLanes * kRplF64 - 1;
-  // ... the tiny ones (one GATK active region) with the fp32 recurrence in the same wavefront and launch as the policy
-  const bool fused_env = g_env.fused_pairs;
-  const int64_t fused_max = g_env.fused_max >= 0 ? g_env.fused_max : (int64_t)kTwoStepFrom;
-  const bool fused_call = per_pair_call && fused_env && n_pairs <= fused_max && n_long_main == 0 && c->cfg.rows_per_lane == 0;
-  const bool deferred_launch = defer && pull && inline_host && c->cfg.record_events == 0 && per_pair_call && n_long_main == 0 &&
-                               finalize_mode == kModePacked && plan.n_chunks > 0 && n_pairs <= kTwoStepFrom;
   const unsigned char* hs_dev = nullptr;  // the staging block as the device sees it
   if (pull) {
     void* p = nullptr;

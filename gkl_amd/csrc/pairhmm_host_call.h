@@ -1,5 +1,5 @@
-// The host-buffer call of one device (dev_compute_host: H2D, device pass, reference-exact host log10) and the small-call combiner that launches
-// the GATK-sized calls of several threads together.
+// The host-buffer call of one device (dev_compute_host: H2D, device pass, reference-exact host log10), the small-call combiner that launches
+// the GATK-sized calls of several threads together, and the multi-region call that hands it whole sets (dev_compute_host_multi).
 // Part of the ONE translation unit gkl_amd/csrc/pairhmm_api.hip (included there, in this order: pairhmm_ctx.h, pairhmm_device_pass.h,
 // pairhmm_ctx_lifecycle.h, pairhmm_host_call.h, pairhmm_multi_device.h, pairhmm_diagnostics.h); not a stand-alone header.
 #pragma once
@@ -117,20 +117,22 @@ struct SmallCombiner {
     HIP_TRY(hipGetLastError());
     return GKLHIP_OK;
   }
-  int launch_multi(Ticket* const* batch, int n, int fma, Slot& sl) {
+  int launch_multi(const SmallLaunch* const* calls, int n, int fma, Slot& sl) {
     MultiArgs mp{}, mf{}, mq{};
     mp.n = mf.n = mq.n = n;
+    int32_t prep_blocks[kMultiMax], main_blocks[kMultiMax], pair_blocks[kMultiMax];
     for (int i = 0; i < n; i++) {
-      const SmallLaunch& L = *batch[i]->sl;
+      const SmallLaunch& L = *calls[i];
       mp.call[i] = L.desc_pinned; mf.call[i] = L.desc_dev; mq.call[i] = L.desc_dev;
-      mp.begin[i + 1] = mp.begin[i] + L.call.prep_grid;
-      mf.begin[i + 1] = mf.begin[i] + L.call.main_blocks;
-      mq.begin[i + 1] = mq.begin[i] + L.call.n_pairs;
+      prep_blocks[i] = L.call.prep_grid; main_blocks[i] = L.call.main_blocks; pair_blocks[i] = L.call.n_pairs;
     }
+    multi_begin(prep_blocks, n, mp.begin);
+    multi_begin(main_blocks, n, mf.begin);
+    multi_begin(pair_blocks, n, mq.begin);
     hipLaunchKernelGGL(prep_multi_kernel, dim3((unsigned)mp.begin[n]), dim3(kPrepBlock), 0, sl.stream, mp);
-    if (batch[0]->sl->call.fused) {  // (every call of a set is of one kind: the leader only takes calls like its own)
+    if (calls[0]->call.fused) {  // (every call of a set is of one kind: a leader only takes calls like its own, a multi call cuts its sets by kind)
       bool narrow = true;   // reads of at most 255 bases in every call of the set: the four-wavefronts-per-SIMD variant
-      for (int i = 0; i < n; i++) narrow = narrow && batch[i]->sl->call.rows <= 4;
+      for (int i = 0; i < n; i++) narrow = narrow && calls[i]->call.rows <= 4;
       const dim3 grid((unsigned)mq.begin[n]), block(64);
       if (narrow && fma)  hipLaunchKernelGGL((pair_fused_multi_kernel<true, 4>), grid, block, 0, sl.stream, mq);
       else if (narrow)    hipLaunchKernelGGL((pair_fused_multi_kernel<false, 4>), grid, block, 0, sl.stream, mq);
@@ -146,6 +148,72 @@ struct SmallCombiner {
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(sl.ev, sl.stream));
     return GKLHIP_OK;
+  }
+
+  // One set into the air and back: takes a free flight slot (the caller holds the lock and has found flights < max_flights),
+  // launches calls[0 .. n) -- one call on the caller's own stream exactly as a lone call always went, several in one set of
+  // launches on the slot's stream --, reports the launch to the owners of calls[1 ..] (`others`; NULL: all n are the
+  // caller's own, the regions of a multi call) and waits for the end.  Returns with the lock released.
+  int fly(std::unique_lock<std::mutex>& l, const SmallLaunch* const* calls, int n, hipStream_t own_stream, Ticket* const* others, int64_t t_lead) {
+    int si = 0;
+    while (slot[si].busy) si++;
+    Slot& sl = slot[si];
+    sl.busy = true;
+    const bool alone = flights == 0 && queue.empty() && n == 1;   // no other small call on the device or waiting for it
+    flights++;
+    n_launch_sets++;
+    if (n > 1) n_combined += n;
+    int rc = GKLHIP_OK;
+    if (n > 1) make_streams();
+    if (n > 1 && !sl.stream) rc = fail(GKLHIP_ERR_HIP, "no stream for combined small calls");
+    l.unlock();
+    if (rc == GKLHIP_OK) rc = n == 1 ? launch_single(calls[0]->call, own_stream, alone) : launch_multi(calls, n, calls[0]->call.fma, sl);
+    const std::string err = rc == GKLHIP_OK ? std::string() : g_err;
+    const int64_t t_launched = now_ns();
+    // a launch that failed part-way may have left kernels on the stream that still read the calls' staging blocks and
+    // write their result buffers: drain it BEFORE any of the calls is told about the failure (and returns to a caller
+    // that is free to reuse those buffers)
+    if (rc != GKLHIP_OK) { (void)(n == 1 ? hipStreamSynchronize(own_stream) : hipStreamSynchronize(sl.stream)); (void)hipGetLastError(); }
+    if (n > 1 && others) {
+      l.lock();
+      // (the others wait on the set's event themselves; letting them sleep until this thread has seen the end
+      //  measured the same)
+      for (int i = 1; i < n; i++) {
+        Ticket* o = others[i - 1];
+        o->rc = rc; o->err = err; o->ev = sl.ev;
+        o->state = rc == GKLHIP_OK ? 1 : 2;
+      }
+      cv.notify_all();
+      l.unlock();
+    }
+    hipError_t e = hipSuccess;
+    if (rc == GKLHIP_OK) e = n == 1 ? hipStreamSynchronize(own_stream) : hipEventSynchronize(sl.ev);
+    l.lock();
+    {
+      const int64_t t_end = now_ns();
+      ns_launch += t_launched - t_lead; ns_sync += t_end - t_launched;
+    }
+    sl.busy = false;  // (the event is recorded again only from here on: a late waiter of this flight then waits a little longer)
+    flights--;
+    cv.notify_all();
+    l.unlock();
+    if (rc != GKLHIP_OK) { g_err = err; return rc; }
+    if (e != hipSuccess) return fail(GKLHIP_ERR_HIP, "%s (combined small calls)", hipGetErrorString(e));
+    return GKLHIP_OK;
+  }
+
+  // The staged regions of one gklhip_compute_multi call that share a set (at most kMultiMax, of one kind and arithmetic
+  // mode), to completion: the set waits for a flight slot like any leader and leaves through the same launches, but it is
+  // the caller's own from end to end -- it never enters the queue, so no other leader sees its regions, it takes nobody
+  // else's tickets, and it never waits for company.  One region alone goes out on `own_stream` as a lone call does.
+  int run_set(const SmallLaunch* const* calls, int n, hipStream_t own_stream) {
+    const int64_t t_in = now_ns();
+    std::unique_lock<std::mutex> l(mu);
+    n_calls += n;
+    cv.wait(l, [&] { return flights < max_flights; });
+    const int64_t t_lead = now_ns();
+    ns_queued += (t_lead - t_in) * n;
+    return fly(l, calls, n, own_stream, nullptr, t_lead);
   }
 
   // Runs one staged call to completion (its packed words are in the caller's pinned result buffer on return).
@@ -174,64 +242,23 @@ struct SmallCombiner {
       // lead: this call first, then the waiting calls of the same arithmetic mode
       const int64_t t_lead = now_ns();
       ns_queued += t_lead - t_in;
-      Ticket* batch[kMultiMax];
+      const SmallLaunch* calls[kCombineMax];
+      Ticket* others[kCombineMax];   // the owners of calls[1 ..]
       int n = 0;
-      batch[n++] = &t;
+      calls[n++] = &mine;
       for (auto it = queue.begin(); it != queue.end();) {
         if (*it == &t) { it = queue.erase(it); continue; }
-        if (n < kMultiMax && (*it)->sl->call.fma == mine.call.fma && (*it)->sl->call.fused == mine.call.fused) {
+        if (n < kCombineMax && (*it)->sl->call.fma == mine.call.fma && (*it)->sl->call.fused == mine.call.fused) {
           (*it)->state = 4;  // taken: its owner keeps sleeping until this thread reports the launch (or the end)
           ns_queued += t_lead - (*it)->t_in;
-          batch[n++] = *it;
+          others[n - 1] = *it;
+          calls[n++] = (*it)->sl;
           it = queue.erase(it);
           continue;
         }
         ++it;
       }
-      int si = 0;
-      while (slot[si].busy) si++;
-      Slot& sl = slot[si];
-      sl.busy = true;
-      const bool alone = flights == 0 && queue.empty() && n == 1;   // no other small call on the device or waiting for it
-      flights++;
-      n_launch_sets++;
-      if (n > 1) n_combined += n;
-      int rc = GKLHIP_OK;
-      if (n > 1) make_streams();
-      if (n > 1 && !sl.stream) rc = fail(GKLHIP_ERR_HIP, "no stream for combined small calls");
-      l.unlock();
-      if (rc == GKLHIP_OK) rc = n == 1 ? launch_single(mine.call, own_stream, alone) : launch_multi(batch, n, mine.call.fma, sl);
-      const std::string err = rc == GKLHIP_OK ? std::string() : g_err;
-      const int64_t t_launched = now_ns();
-      // a launch that failed part-way may have left kernels on the stream that still read the calls' staging blocks and
-      // write their result buffers: drain it BEFORE any of the calls is told about the failure (and returns to a caller
-      // that is free to reuse those buffers)
-      if (rc != GKLHIP_OK) { (void)(n == 1 ? hipStreamSynchronize(own_stream) : hipStreamSynchronize(sl.stream)); (void)hipGetLastError(); }
-      if (n > 1) {
-        l.lock();
-        // (the others wait on the set's event themselves; letting them sleep until this thread has seen the end
-        //  measured the same)
-        for (int i = 1; i < n; i++) {
-          batch[i]->rc = rc; batch[i]->err = err; batch[i]->ev = sl.ev;
-          batch[i]->state = rc == GKLHIP_OK ? 1 : 2;
-        }
-        cv.notify_all();
-        l.unlock();
-      }
-      hipError_t e = hipSuccess;
-      if (rc == GKLHIP_OK) e = n == 1 ? hipStreamSynchronize(own_stream) : hipEventSynchronize(sl.ev);
-      l.lock();
-      {
-        const int64_t t_end = now_ns();
-        ns_launch += t_launched - t_lead; ns_sync += t_end - t_launched;
-      }
-      sl.busy = false;  // (the event is recorded again only from here on: a late waiter of this flight then waits a little longer)
-      flights--;
-      cv.notify_all();
-      l.unlock();
-      if (rc != GKLHIP_OK) { g_err = err; return rc; }
-      if (e != hipSuccess) return fail(GKLHIP_ERR_HIP, "%s (combined small calls)", hipGetErrorString(e));
-      return GKLHIP_OK;
+      return fly(l, calls, n, own_stream, others, t_lead);
     }
     l.unlock();
     if (t.state == 2) { g_err = t.err; return t.rc; }
@@ -249,15 +276,11 @@ SmallCombiner* small_combiner(int device) {
     k->device = device;   // (its flight streams: SmallCombiner::make_streams, when two calls first meet)
     if (const char* v = getenv("GKL_HIP_EAGER_STREAMS")) if (atoi(v) >= 7) k->make_streams();   // A/B: the r04 arrangement
     if (const char* v = getenv("GKL_HIP_COMBINE_FLIGHTS")) all[(size_t)device]->max_flights = std::max(1, std::min(kFlightSlots, atoi(v)));
-    if (const char* v = getenv("GKL_HIP_COMBINE_MIN")) all[(size_t)device]->min_batch = std::max(0, std::min(kMultiMax, atoi(v)));
+    if (const char* v = getenv("GKL_HIP_COMBINE_MIN")) all[(size_t)device]->min_batch = std::max(0, std::min(kCombineMax, atoi(v)));
     if (const char* v = getenv("GKL_HIP_COMBINE_WAIT_US")) all[(size_t)device]->batch_wait_ns = (int64_t)std::max(0, atoi(v)) * 1000;
   }
   return all[(size_t)device];
 }
-bool combine_enabled() {
-  return g_env.combine;
-}
-
 int dev_compute_host_impl(DevCtx* c, const gklhip_batch* hb, double* out_host) {
   const int64_t n_pairs = (int64_t)hb->n_reads * hb->n_haps;
   HIP_TRY(hipSetDevice(c->device));
@@ -311,7 +334,7 @@ int dev_compute_host_impl(DevCtx* c, const gklhip_batch* hb, double* out_host) {
   HostFinalizer fin;
   // (a context with an asynchronous device-resident call still in flight keeps the stream-ordered path)
   SmallLaunch small;
-  const bool may_defer = inline_inputs && combine_enabled() && (!c->have_call_done || hipEventQuery(c->call_done) == hipSuccess);
+  const bool may_defer = small_call_defers(c, inline_inputs) && (!c->have_call_done || hipEventQuery(c->call_done) == hipSuccess);
   (void)hipGetLastError();  // (hipErrorNotReady of the query)
   const int64_t t_call = SmallCombiner::now_ns();
   if ((rc = run_device(c, &db, pin_out, kModePacked, s, inline_inputs, may_defer ? &small : nullptr))) return rc;  // records policy_done
@@ -364,6 +387,103 @@ int dev_compute_host(DevCtx* c, const gklhip_batch* hb, double* out_host) {
     g_err = keep;
   }
   return rc;
+}
+
+// ---- several region calls in one set of launches (gklhip_compute_multi) ----
+// A region of a multi call: checked by the caller (validate, at least one pair, an output array).
+struct MultiRegion {
+  const gklhip_batch* hb = nullptr;
+  double* out = nullptr;
+  int index = 0;            // its place in the caller's arrays
+  int rc = GKLHIP_OK;
+  std::string err;
+  bool alone = false;       // does not qualify for a shared set: the caller runs it through the single-call path
+  int lane = -1;            // the staging lane that holds its raw sums after the call (-1: none)
+  gklhip_stats stats;
+};
+
+// The regions that the single-call path would defer are staged on the context's lanes -- by run_device, exactly as a single
+// call stages itself --, cut into sets (multi_cut_sets) and leave set by set through the combiner's launches; each region's
+// packed words are then finalised on the host as a single call's are.  Every other region comes back marked `alone`.
+// Up to kMultiMax regions are staged first and cut afterwards; a longer list is planned twice: once to learn which regions
+// qualify (the cut needs that of the whole list), once more when the region's set is staged.
+// A failure is the region's own (`rc`, `err`), a failed set's the failure of every region in it; the return value is for
+// what stops the whole call before any region is touched.
+int dev_compute_host_multi(DevCtx* c, std::vector<DevCtx*>& lanes, std::vector<MultiRegion>& R) {
+  HIP_TRY(hipSetDevice(c->device));
+  const HostCallInFlight in_flight;
+  const int threads = finalize_threads(c, in_flight.share);
+  const int64_t one_pass_min = g_env.finalize_min > 0 ? g_env.finalize_min : 8192;
+  const int mode = c->cfg.finalize;
+  const bool on_device = (mode == GKLHIP_FINALIZE_DEVICE_F64 || mode == GKLHIP_FINALIZE_DEVICE_REF32);
+  SmallCombiner* k = small_combiner(c->device);
+  const int n = (int)R.size();
+  const bool stage_first = n <= kMultiMax;
+  std::vector<SmallLaunch> staged((size_t)kMultiMax);   // by lane
+  std::vector<int> owner((size_t)kMultiMax, -1);        // by lane: the region whose raw sums it holds
+  auto fail_region = [](MultiRegion& r, int rc) { r.rc = rc; r.err = g_err; };
+  // Plans region i on lane `li` and stages it there (probe: only asks whether it would be).  False: no set for this region
+  // (it does not qualify: r.alone; it failed: r.rc).
+  auto stage = [&](int i, int li, bool probe) {
+    MultiRegion& r = R[(size_t)i];
+    const gklhip_batch* hb = r.hb;
+    const size_t rl = (size_t)hb->read_off[hb->n_reads], hl = (size_t)hb->hap_off[hb->n_haps];
+    const bool inline_inputs = 5 * align_up(rl) + align_up(hl) <= kSmallBatchBytes;
+    if (on_device || !small_call_defers(c, inline_inputs)) { r.alone = true; return false; }
+    while ((int)lanes.size() <= li) {   // lanes are made on first use
+      DevCtx* ln = nullptr;
+      const int rc = lane_init(c, &ln);
+      if (rc != GKLHIP_OK) { fail_region(r, rc); return false; }
+      lanes.push_back(ln);
+    }
+    DevCtx* ln = lanes[(size_t)li];
+    SmallLaunch& sl = staged[(size_t)li];
+    sl = SmallLaunch();
+    sl.only = true;
+    sl.probe = probe;
+    int rc = GKLHIP_OK;
+    void* pin_out = nullptr;
+    if (!probe) {
+      if (owner[(size_t)li] >= 0) R[(size_t)owner[(size_t)li]].lane = -1;   // an earlier set's region: its raw sums go now
+      owner[(size_t)li] = -1;
+      rc = ln->res_pin.reserve((size_t)hb->n_reads * (size_t)hb->n_haps * 8);
+      if (rc == GKLHIP_OK && hipHostGetDevicePointer(&pin_out, ln->res_pin.p, 0) != hipSuccess) { (void)hipGetLastError(); rc = fail(GKLHIP_ERR_HIP, "hipHostGetDevicePointer failed"); }
+    }
+    if (rc == GKLHIP_OK) rc = run_device(ln, hb, static_cast<double*>(pin_out), kModePacked, c->stream, true, &sl);
+    if (rc != GKLHIP_OK) { fail_region(r, rc); return false; }
+    if (!sl.qualifies) { r.alone = true; return false; }
+    if (!probe) { owner[(size_t)li] = i; r.lane = li; }
+    return true;
+  };
+  std::vector<uint8_t> qualifies((size_t)n), kind((size_t)n);
+  for (int i = 0; i < n; i++) {
+    const int li = stage_first ? i : 0;
+    qualifies[(size_t)i] = stage(i, li, !stage_first) ? 1 : 0;
+    kind[(size_t)i] = qualifies[(size_t)i] ? (uint8_t)staged[(size_t)li].call.fused : 0;
+  }
+  std::vector<int32_t> set_of((size_t)n);
+  const int n_sets = multi_cut_sets(qualifies.data(), kind.data(), n, set_of.data());
+  for (int s = 0, i = 0; s < n_sets; s++) {
+    const SmallLaunch* calls[kMultiMax];
+    int members[kMultiMax], m = 0;
+    for (; i < n && set_of[(size_t)i] <= s; i++) {
+      if (set_of[(size_t)i] != s) continue;
+      if (!stage_first && !stage(i, m, false)) continue;   // (planned under another load, it no longer qualifies: alone after all)
+      calls[m] = &staged[(size_t)R[(size_t)i].lane];
+      members[m++] = i;
+    }
+    if (m == 0) continue;
+    const int rc = k->run_set(calls, m, c->stream);
+    for (int j = 0; j < m; j++) {
+      MultiRegion& r = R[(size_t)members[j]];
+      DevCtx* ln = lanes[(size_t)r.lane];
+      if (rc != GKLHIP_OK) { fail_region(r, rc); owner[(size_t)r.lane] = -1; r.lane = -1; continue; }
+      const HostFinalizer fin;
+      ln->stats.n_fallback = fin.all(&c->workers, ln->res_pin.as<uint64_t>(), r.out, ln->stats.n_pairs, threads, one_pass_min);
+      r.stats = ln->stats;
+    }
+  }
+  return GKLHIP_OK;
 }
 
 }  // namespace

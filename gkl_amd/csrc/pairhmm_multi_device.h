@@ -147,6 +147,12 @@ struct gklhip_ctx {
   int last_set = 0;
   gklhip_stats stats;
   int32_t last_reads = 0, last_haps = 0;
+  // gklhip_compute_multi: the staging lanes of dev[0] (up to kMultiMax, made on first use, given back by
+  // gklhip_release_idle) and, per region of the last multi call, the lane that still holds its raw sums (-1: none) and
+  // its pairs (gklhip_get_raw_region).  `after_multi`: the last call was a multi call -- gklhip_get_raw has no one call to read.
+  std::vector<DevCtx*> lanes;
+  std::vector<std::pair<int, int64_t>> multi_last;
+  bool after_multi = false;
   // A client context (gklhip_connect): every call goes to the PairHMM server; nothing above is used, and no HIP call is made.
   gklhip_remote::Client* remote = nullptr;
   ~gklhip_ctx() {
@@ -160,6 +166,7 @@ struct gklhip_ctx {
       if (shard_done_alt[d]) { (void)hipSetDevice(dev[d]->device); (void)hipEventDestroy(shard_done_alt[d]); }
     if (inputs_ready) { (void)hipSetDevice(dev[0]->device); (void)hipEventDestroy(inputs_ready); }
     if (inputs_ready_alt) { (void)hipSetDevice(dev[0]->device); (void)hipEventDestroy(inputs_ready_alt); }
+    for (DevCtx* d : lanes) dev_done(d);   // (before their parent: a lane's last stream is the parent's)
     for (DevCtx* d : dev_alt) dev_done(d);
     for (DevCtx* d : dev) dev_done(d);
     for (DevCtx* d : twins) dev_done(d);

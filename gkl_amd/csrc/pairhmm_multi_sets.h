@@ -1,0 +1,69 @@
+// Several small PairHMM calls in one set of launches: which calls share a set, where each call's blocks begin in a
+// launch, and how a block finds its call -- for the host (SmallCombiner, gklhip_compute_multi) and the kernels
+// (pairhmm_aux_kernels.h: the *_multi_kernel families).
+//
+// A launch of a set runs the blocks of its n calls back to back: call k owns blocks [begin[k], begin[k + 1]) and runs
+// local block (block - begin[k]) exactly as its single-call kernel would.  begin[] is a prefix sum of n + 1 values, so a
+// block finds its call by a binary search over it -- uniform over the wavefront, once per block.
+//
+// Plain C++ (tests/native/pairhmm_multi_sets_check.cpp compiles it for the host alone, under the sanitizers).
+#pragma once
+#include <stdint.h>
+
+#if defined(__HIPCC__)
+#define GKL_MS_HD __host__ __device__ __forceinline__
+#else
+#define GKL_MS_HD inline
+#endif
+
+namespace gklhip {
+
+constexpr int kMultiMax = 64;     // calls per set of launches (what MultiArgs holds: a set of gklhip_compute_multi)
+constexpr int kCombineMax = 16;   // ... of which a leader of concurrent callers takes at most this many (SmallCombiner::run)
+
+// The set-cutting rule of gklhip_compute_multi.  The regions that qualify for a shared set (the single call would defer
+// them: small_call_defers) form runs in input order: a run ends where the next qualifying region is of the other kind
+// (fused per-pair kernel or not); regions that do not qualify run alone and do not interrupt a run.  A run of m regions
+// is cut into ceil(m / kMultiMax) sets of consecutive regions whose sizes differ by at most one -- 65 regions leave as
+// 33 + 32, not as 64 and one region that pays a set of launches alone.
+// set_of[k]: the set of region k, numbered from 0 in input order, or -1 for a region that does not qualify.  Returns the
+// number of sets.
+inline int multi_cut_sets(const uint8_t* qualifies, const uint8_t* kind, int n, int32_t* set_of) {
+  int n_sets = 0;
+  for (int k = 0; k < n;) {
+    if (!qualifies[k]) { set_of[k++] = -1; continue; }
+    int m = 0, end = k;
+    for (; end < n && (!qualifies[end] || kind[end] == kind[k]); end++) m += qualifies[end] ? 1 : 0;
+    const int sets = (m + kMultiMax - 1) / kMultiMax;
+    for (int j = k, i = 0; j < end; j++) {
+      if (!qualifies[j]) { set_of[j] = -1; continue; }
+      set_of[j] = n_sets + (int)((int64_t)i * sets / m);
+      i++;
+    }
+    n_sets += sets;
+    k = end;
+  }
+  return n_sets;
+}
+
+// begin[0 .. n]: first block of each call in a launch of `blocks[k]` blocks per call (begin[n] = the grid).
+inline void multi_begin(const int32_t* blocks, int n, int32_t* begin) {
+  begin[0] = 0;
+  for (int k = 0; k < n; k++) begin[k + 1] = begin[k] + blocks[k];
+}
+
+// The call of block `block`, 0 <= block < begin[n], n >= 1: the LAST k with begin[k] <= block (a call without blocks in
+// this launch shares its start with the next one).
+GKL_MS_HD int multi_find(const int32_t* __restrict__ begin, int n, int block) {
+  int lo = 0, hi = n;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (block >= begin[mid]) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+// ... and its index inside that call, and back.
+GKL_MS_HD int multi_local(const int32_t* __restrict__ begin, int call, int block) { return block - begin[call]; }
+GKL_MS_HD int multi_block(const int32_t* __restrict__ begin, int call, int local) { return begin[call] + local; }
+
+}  // namespace gklhip

@@ -128,6 +128,10 @@ def load_library(path: Optional[str] = None):
     lib.gklhip_get_stats.restype = C.c_int
     lib.gklhip_get_raw.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.gklhip_get_raw.restype = C.c_int
+    lib.gklhip_compute_multi.argtypes = [C.c_void_p, C.c_int32, C.POINTER(CBatch), C.POINTER(C.c_void_p), C.POINTER(C.c_int32)]
+    lib.gklhip_compute_multi.restype = C.c_int
+    lib.gklhip_get_raw_region.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.gklhip_get_raw_region.restype = C.c_int
     lib.gklhip_get_table_f32.argtypes = [C.c_int, C.c_void_p, C.c_int64]
     lib.gklhip_get_table_f32.restype = C.c_int64
     lib.gklhip_get_table_f64.argtypes = [C.c_int, C.c_void_p, C.c_int64]
@@ -145,13 +149,28 @@ def load_library(path: Optional[str] = None):
     return lib
 
 
+def _exception(lib, status: int, msg: str):
+    if status == ERR_INVALID_ARG:
+        return IllegalArgumentException(msg)
+    if status == ERR_OOM:
+        return OutOfMemoryError(msg)
+    return RuntimeException(f"{lib.gklhip_strerror(status).decode()}: {msg}")
+
+
 def _raise(lib, status: int):
     msg = (lib.gklhip_last_error() or b"").decode() or lib.gklhip_strerror(status).decode()
-    if status == ERR_INVALID_ARG:
-        raise IllegalArgumentException(msg)
-    if status == ERR_OOM:
-        raise OutOfMemoryError(msg)
-    raise RuntimeException(f"{lib.gklhip_strerror(status).decode()}: {msg}")
+    raise _exception(lib, status, msg)
+
+
+class PairHmmMultiError(Exception):
+    """compute_multi: some regions failed.  results[k] is region k's array or None, statuses[k] its status code,
+    errors[k] the exception a single call would have raised (None for a region that succeeded); status is what
+    gklhip_compute_multi returned (the first failing region's status)."""
+
+    def __init__(self, results, statuses, errors, status):
+        first = next(e for e in errors if e is not None)
+        super().__init__(f"{sum(e is not None for e in errors)} of {len(errors)} regions failed; the first: {first}")
+        self.results, self.statuses, self.errors, self.status = results, statuses, errors, int(status)
 
 
 def host_table(which: int, dtype) -> np.ndarray:
@@ -363,6 +382,34 @@ class PairHmmContext:
             _raise(self.lib, st)
         return out
 
+    def compute_multi(self, batches) -> list:
+        """Several region calls, the GATK-sized ones in one set of launches (gklhip_compute_multi): batches is a list of
+        FlatBatch; returns the list of their likelihood arrays, each byte for byte what compute() returns for it alone.
+        When regions fail, the others are still computed: PairHmmMultiError carries their arrays and every region's
+        status and exception."""
+        n = len(batches)
+        keep, cbs, outs = [], (CBatch * max(n, 1))(), []
+        for k, b in enumerate(batches):
+            arrs = [np.ascontiguousarray(a, np.uint8) for a in (b.read_bases, b.read_quals, b.ins_gop, b.del_gop, b.gcp, b.hap_bases)]
+            ro = np.ascontiguousarray(b.read_off, np.int64)
+            ho = np.ascontiguousarray(b.hap_off, np.int64)
+            keep.append((arrs, ro, ho))
+            cbs[k] = CBatch(b.n_reads, b.n_haps, ro.ctypes.data_as(_i64p), ho.ctypes.data_as(_i64p), *[a.ctypes.data for a in arrs])
+            outs.append(np.empty(max(b.n_reads * b.n_haps, 0), np.float64))
+        out_ptrs = (C.c_void_p * max(n, 1))(*[o.ctypes.data for o in outs])
+        status = (C.c_int32 * max(n, 1))()
+        st = self.lib.gklhip_compute_multi(self.handle, n, cbs, out_ptrs, status)
+        if st == OK:
+            return outs
+        if n <= 0 or all(status[k] == OK for k in range(n)):
+            _raise(self.lib, st)   # the call itself was refused
+        # the library keeps the first failing region's message; the others get their status's text
+        msg = (self.lib.gklhip_last_error() or b"").decode()
+        first = next(k for k in range(n) if status[k] != OK)
+        errors = [None if status[k] == OK else _exception(self.lib, status[k], msg if k == first else f"region {k} failed with status {status[k]}")
+                  for k in range(n)]
+        raise PairHmmMultiError([o if status[k] == OK else None for k, o in enumerate(outs)], [int(status[k]) for k in range(n)], errors, st)
+
     # -- everything resident in HBM; `out` is a torch float64 CUDA tensor --
     def compute_device(self, dbatch: DeviceBatch, out=None, stream=None):
         import torch
@@ -398,6 +445,16 @@ class PairHmmContext:
         r64 = np.zeros(n_pairs, np.float64)
         u = np.zeros(n_pairs, np.uint8)
         st = self.lib.gklhip_get_raw(self.handle, r32.ctypes.data, r64.ctypes.data, u.ctypes.data)
+        if st != OK:
+            _raise(self.lib, st)
+        return r32, r64, u
+
+    def raw_region(self, k: int, n_pairs: int):
+        """Raw scaled sums of region k of the last compute_multi call: (raw32, raw64, used64)."""
+        r32 = np.zeros(n_pairs, np.float32)
+        r64 = np.zeros(n_pairs, np.float64)
+        u = np.zeros(n_pairs, np.uint8)
+        st = self.lib.gklhip_get_raw_region(self.handle, int(k), r32.ctypes.data, r64.ctypes.data, u.ctypes.data)
         if st != OK:
             _raise(self.lib, st)
         return r32, r64, u

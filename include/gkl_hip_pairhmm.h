@@ -151,6 +151,30 @@ int gklhip_rccl_selftest(int32_t device);
  * 8-byte word per pair through pinned memory owned by the context. */
 int gklhip_compute(gklhip_ctx* ctx, const gklhip_batch* host_batch, double* out_host);
 
+/* Several region calls, the GATK-sized ones in ONE set of launches: region k's output is, byte for byte, what
+ * gklhip_compute(ctx, &regions[k], out_host[k]) writes on the same context -- whichever other regions ride along, in
+ * whatever order, in both fma modes.  out_host: [n_regions] pointers, region k's n_reads * n_haps doubles.  status_out:
+ * [n_regions] or NULL.
+ * Returns GKLHIP_OK when every region succeeded, else the status of the first failing region (gklhip_last_error: its
+ * message); the per-region statuses are in status_out and the regions that succeeded have valid results.  The argument
+ * checks of the single call run per region before anything touches the device: a region that fails them is left out and
+ * the rest still run.  A region with n_reads * n_haps == 0 succeeds and writes nothing.  A HIP failure of a shared set of
+ * launches fails every region in that set (after its stream has been drained).
+ * Which regions share a set: those the single call hands to the small-call combiner (inputs of at most 1 MB, at most
+ * 2048 pairs, no read of 384 bases or more, host finalisation, no use_double, no record_events).  In input order they
+ * are cut into sets of one kind (with rows_per_lane == 0: the fused per-pair kernel) of at most 64 regions; each region
+ * is planned and staged exactly as a single call is, on one of up to 64 staging lanes of the context (made on first
+ * use, given back by gklhip_release_idle), and a set leaves through the combiner's launches: it waits for a flight slot
+ * like the set of any concurrent callers, but takes nobody else's calls and waits for no company.  Every other region --
+ * and every region of a multi-device context, of a process with GKL_HIP_COMBINE=0 and of a client context, whose wire
+ * protocol has no multi request -- is computed afterwards through the single-call path, in input order.
+ * gklhip_small_call_counts: a set of n regions adds n to the calls, n to the combined calls when n > 1, and 1 to the
+ * sets; a region that ran alone counts as a single call does.  Afterwards gklhip_get_stats holds the sums over the
+ * regions of n_pairs, n_fallback, cells and cells_fp64 (the other fields are 0), gklhip_get_raw fails ("no completed call
+ * to read back": it has no one call to read) and gklhip_get_raw_region reads one region. */
+int gklhip_compute_multi(gklhip_ctx* ctx, int32_t n_regions, const gklhip_batch* regions, double* const* out_host,
+                         int32_t* status_out);
+
 /* Page-locked host memory for a binder's marshalling buffers (replaces the per-array
  * Get<T>ArrayElements pins of JavaData.h:135-154 with one flat, DMA-able staging area that is
  * reused across calls).  NULL on failure.  Not tied to a context.  In a process with GKL_HIP_SERVER set (client mode,
@@ -174,6 +198,11 @@ int gklhip_get_step_times(gklhip_ctx* ctx, int32_t steps_back, float* ms_main, f
 /* Raw sums of the last call, copied to host arrays of n_pairs entries (any may be NULL).
  * raw64 is meaningful where used64 != 0. Synchronises the stream. */
 int gklhip_get_raw(gklhip_ctx* ctx, float* raw32, double* raw64, uint8_t* used64);
+/* gklhip_get_raw for region `region` of the last gklhip_compute_multi call (arrays of that region's n_pairs entries).
+ * The raw sums of a region that shared a set stay on its staging lane until a later set of the same call, the next
+ * multi call or gklhip_release_idle takes the lane; a region that failed, was empty or ran alone through the
+ * single-call path has none (GKLHIP_ERR_UNSUPPORTED). */
+int gklhip_get_raw_region(gklhip_ctx* ctx, int32_t region, float* raw32, double* raw64, uint8_t* used64);
 /* Host-built lookup tables exactly as uploaded: which = 0 ph2pr[128],
  * 1 matchToMatch triangle for quals 0..127 [8256], 2 ph2pr/3 [128]. Returns count. */
 int64_t gklhip_get_table_f32(int which, float* dst, int64_t cap);
@@ -220,8 +249,8 @@ int gklhip_fault_inject(const char* spec);
  * was started without --devices) and runs every call through its gklhip_compute, so the calls of many client
  * processes meet in one process's small-call combiner.  A client process makes no HIP call: batches travel through a
  * shared-memory arena (memfd) the server maps.  gklhip_init with GKL_HIP_SERVER=PATH in the environment is
- * gklhip_connect(PATH, cfg, out_ctx).  On a remote context gklhip_compute, gklhip_get_stats, gklhip_release_idle (no-op)
- * and gklhip_done work; gklhip_compute_device, gklhip_get_raw, gklhip_get_step_times and gklhip_measure_issue_ceiling
+ * gklhip_connect(PATH, cfg, out_ctx).  On a remote context gklhip_compute, gklhip_compute_multi (region by region), gklhip_get_stats, gklhip_release_idle (no-op)
+ * and gklhip_done work; gklhip_compute_device, gklhip_get_raw, gklhip_get_raw_region, gklhip_get_step_times and gklhip_measure_issue_ceiling
  * return GKLHIP_ERR_UNSUPPORTED, and so does gklhip_fault_inject in a process with GKL_HIP_SERVER set.  A server that
  * has gone away fails the call with GKLHIP_ERR_HIP and a message that names the socket. */
 #define GKLHIP_SERVER_PROTOCOL 1

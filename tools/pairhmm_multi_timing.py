@@ -1,0 +1,90 @@
+#!/usr/bin/env python3
+"""K distinct seeded `hc` regions of 100 reads x 10 haplotypes as ONE gklhip_compute_multi call against K consecutive
+gklhip_compute calls on the same context: median host-to-host time of each, K in --counts, the two arms alternating in one
+process.  Both arms are made on prebuilt arguments: nothing but the C ABI is timed.  Checks that both give the same bytes
+and reports how many sets of launches the multi call took (gklhip_small_call_counts).
+
+usage: tools/pairhmm_multi_timing.py [--counts 1,2,4,8,16,64] [--reps 30] [--warmup 10] [--out FILE]"""
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--counts", default="1,2,4,8,16,64")
+    ap.add_argument("--reps", type=int, default=30)
+    ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--out", default="")
+    a = ap.parse_args()
+    if a.reps < 30:
+        raise SystemExit("at least 30 repetitions")
+    from gkl_amd import native
+    from gkl_amd.synth import make_batch
+    ctx = native.PairHmmContext(device=0)
+    lib, h = ctx.lib, ctx.handle
+    result = {"region": "hc 100 x 10", "reps": a.reps, "warmup": a.warmup, "rows": []}
+    for K in (int(x) for x in a.counts.split(",")):
+        batches = [make_batch("hc", 100, 10, seed=1000 + k) for k in range(K)]
+        keep, cbs = [], (native.CBatch * K)()
+        for k, b in enumerate(batches):
+            arrs = [np.ascontiguousarray(x, np.uint8) for x in (b.read_bases, b.read_quals, b.ins_gop, b.del_gop, b.gcp, b.hap_bases)]
+            ro, ho = np.ascontiguousarray(b.read_off, np.int64), np.ascontiguousarray(b.hap_off, np.int64)
+            keep.append((arrs, ro, ho))
+            cbs[k] = native.CBatch(b.n_reads, b.n_haps, ro.ctypes.data_as(native._i64p), ho.ctypes.data_as(native._i64p),
+                                   *[x.ctypes.data for x in arrs])
+        cells = sum(int(b.read_off[-1]) * int(b.hap_off[-1]) for b in batches)
+        outs_m = [np.empty(b.n_pairs) for b in batches]
+        outs_s = [np.empty(b.n_pairs) for b in batches]
+        ptrs = (C.c_void_p * K)(*[o.ctypes.data for o in outs_m])
+        single_args = [(C.byref(cbs[k]), outs_s[k].ctypes.data) for k in range(K)]
+
+        def multi():
+            if lib.gklhip_compute_multi(h, K, cbs, ptrs, None) != 0:
+                raise SystemExit("multi call failed: " + lib.gklhip_last_error().decode())
+
+        def singles():
+            for cb, out in single_args:
+                if lib.gklhip_compute(h, cb, out) != 0:
+                    raise SystemExit("single call failed: " + lib.gklhip_last_error().decode())
+
+        for _ in range(a.warmup):
+            multi()
+            singles()
+        native.small_call_counts(0, reset=True)
+        multi()
+        counts = native.small_call_counts(0)
+        t = {"multi": [], "singles": []}
+        for _ in range(a.reps):
+            for name, fn in (("multi", multi), ("singles", singles)):
+                t0 = time.perf_counter()
+                fn()
+                t[name].append((time.perf_counter() - t0) * 1e3)
+        same = all(m.tobytes() == s.tobytes() for m, s in zip(outs_m, outs_s))
+        row = {"K": K, "multi_call_counts": list(counts), "same_bytes": bool(same)}
+        for name in ("multi", "singles"):
+            p50 = float(np.median(t[name]))
+            row[name] = {"host_ms_p50": round(p50, 4), "host_ms_p10": round(float(np.percentile(t[name], 10)), 4),
+                         "host_ms_p90": round(float(np.percentile(t[name], 90)), 4), "gcups_host": round(cells / (p50 * 1e-3) / 1e9, 1)}
+        row["host_speedup"] = round(row["singles"]["host_ms_p50"] / row["multi"]["host_ms_p50"], 3)
+        result["rows"].append(row)
+        print(json.dumps(row), flush=True)
+        if not same:
+            raise SystemExit("the multi call and the single calls differ")
+    ctx.close()
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(result, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
