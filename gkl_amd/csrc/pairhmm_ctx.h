@@ -1,7 +1,6 @@
 // Process-wide switches and DevCtx: one device's engine state (error plumbing and the grow-and-trim device / pinned
 // buffers: hip_host_common.h, shared with the PDHMM and Smith-Waterman libraries).
-// Part of the ONE translation unit gkl_amd/csrc/pairhmm_api.hip (included there, in this order: pairhmm_ctx.h, pairhmm_device_pass.h,
-// pairhmm_ctx_lifecycle.h, pairhmm_host_call.h, pairhmm_multi_device.h, pairhmm_diagnostics.h); not a stand-alone header.
+// Part of the ONE translation unit gkl_amd/csrc/pairhmm_api.hip, which includes it in the order it needs; not a stand-alone header.
 #pragma once
 
 using namespace gklhip;
@@ -95,6 +94,5 @@ struct DevCtx {
   Plan plan;
   std::vector<PlanLane> long_lanes;
   std::vector<FwdJob> long_jobs;
-  std::vector<int64_t> sub_read_off;  // multi-device: this device's read range, offsets rebased to 0
   DevBuf carry;
 };

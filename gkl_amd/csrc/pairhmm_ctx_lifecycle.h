@@ -1,6 +1,5 @@
 // A device engine's lifecycle: dev_init (streams, self-tests, tables), dev_done, trim_streams.
-// Part of the ONE translation unit gkl_amd/csrc/pairhmm_api.hip (included there, in this order: pairhmm_ctx.h, pairhmm_device_pass.h,
-// pairhmm_ctx_lifecycle.h, pairhmm_host_call.h, pairhmm_multi_device.h, pairhmm_diagnostics.h); not a stand-alone header.
+// Part of the ONE translation unit gkl_amd/csrc/pairhmm_api.hip, which includes it in the order it needs; not a stand-alone header.
 #pragma once
 
 namespace {
@@ -182,9 +181,9 @@ int dev_init(const gklhip_config& cfg, int dev, int ndev, DevCtx** out) {
 // A staging lane of `parent` (gklhip_compute_multi: a set of n regions needs n staged calls alive at once).  A lane is a
 // DevCtx used for its per-call staging state only -- plan slots, pinned result words, raw sums and flags, the prep
 // kernel's outputs -- over the PARENT's device tables; it has no stream and no event ring of its own (every stream is a
-// hardware queue: docs/NOTES.md 48).  Its calls are only ever staged (run_device with defer->only) and leave through the
+// hardware queue: docs/NOTES.md 48).  Its calls are only ever planned, staged and described (plan_call, stage_call, describe_small_call) and leave through the
 // combiner, on the parent's stream or a flight stream; the set they ride in has ended before the multi call returns, so
-// the slot events below are never recorded again -- they exist because run_device waits for them before it writes a slot.
+// the slot events below are never recorded again -- they exist because stage_call waits for them before it writes a slot.
 // dev_done takes a lane as it takes an engine.
 int lane_init(DevCtx* parent, DevCtx** out) {
   *out = nullptr;

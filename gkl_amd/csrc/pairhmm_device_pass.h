@@ -1,7 +1,8 @@
-// One pass of the hot path on one device: table upload, plan block layout, kernel launch helpers, run_device (prep -> fp32 forward -> policy +
-// device-side planning -> fp64 recomputation -> finalisation).
-// Part of the ONE translation unit gkl_amd/csrc/pairhmm_api.hip (included there, in this order: pairhmm_ctx.h, pairhmm_device_pass.h,
-// pairhmm_ctx_lifecycle.h, pairhmm_host_call.h, pairhmm_multi_device.h, pairhmm_diagnostics.h); not a stand-alone header.
+// One pass of the hot path on one device: table upload, plan block layout, kernel launch helpers, and the pass in steps -- plan_call (host
+// only), stage_call (the block and its way to the device), the kernels' argument builders, one launch function per shape of call (prep ->
+// fp32 forward -> policy + device-side planning -> fp64 recomputation -> finalisation), describe_small_call (the deferred exit) -- which
+// run_device and the host-buffer calls (pairhmm_host_call.h) compose.
+// Part of the ONE translation unit gkl_amd/csrc/pairhmm_api.hip, which includes it in the order it needs; not a stand-alone header.
 #pragma once
 
 namespace {
@@ -177,13 +178,9 @@ void launch_long_jobs(const FwdArgs<T>& a, int fma, int n_blocks, int max_read_l
   }
 }
 
-// A small host-buffer call, planned and staged but not launched: SmallCombiner decides how it reaches the device (on
-// its own, or in one set of launches with the calls of other threads).
+// A small host-buffer call, planned and staged but not launched (describe_small_call): SmallCombiner decides how it
+// reaches the device (on its own, or in one set of launches with the calls of other threads).
 struct SmallLaunch {
-  bool only = false;    // in: a call that cannot be deferred is not run at all (run_device returns before it touches the device)
-  bool probe = false;   // in, with `only`: nothing is staged either -- `qualifies` and call.fused are the answer
-  bool qualifies = false;
-  bool filled = false;
   SmallCall call;                          // the descriptor
   const SmallCall* desc_pinned = nullptr;  // ... as the device sees it in the pinned staging block (the prep kernel reads this one)
   const SmallCall* desc_dev = nullptr;     // ... in the device copy of the plan block (which the prep kernel pulls)
@@ -309,108 +306,170 @@ void launch_pair_fused(const FwdArgs<float>& f, const FwdArgs<double>& d, const 
 
 // A small plan (GATK-sized call) is PULLED from the pinned staging block by the prep kernel itself: no copy-engine hop at all.
 bool plan_pulled(size_t plan_bytes) { return plan_bytes < (1u << 20); }  // (256 KB .. 2 MB measure within 2 % on calls of 4k-50k pairs, 1 MB best)
-// Policy + fp64 recomputation of one pair per wavefront (the kernel holds at most 64 x kRplF64 - 1 rows).
-bool per_pair_policy_call(const DevCtx* c, int64_t n_pairs, int n_long64, int max_read_len) {
-  return !c->cfg.use_double && n_pairs <= kDirectPairs && n_long64 == 0 && max_read_len <= kLanes * kRplF64 - 1;
+bool finalizes_on_device(int mode) { return mode == GKLHIP_FINALIZE_DEVICE_F64 || mode == GKLHIP_FINALIZE_DEVICE_REF32; }
+
+// The six byte arrays of a batch in ONE buffer: the five read arrays `stride` apart, then the haplotype bases.
+size_t six_arrays_bytes(const gklhip_batch* b) { return 5 * align_up((size_t)b->read_off[b->n_reads]) + align_up((size_t)b->hap_off[b->n_haps]); }
+// a GATK-sized host call: the six arrays travel inside the plan block (ONE copy or pull for plan + inputs)
+bool inputs_inline(const gklhip_batch* hb) { return six_arrays_bytes(hb) <= kSmallBatchBytes; }
+// ... `b` with its array pointers into such a buffer at `base`
+gklhip_batch batch_at(const gklhip_batch& b, const unsigned char* base, size_t stride) {
+  gklhip_batch v = b;
+  v.read_bases = base; v.read_quals = base + stride; v.ins_gop = base + 2 * stride;
+  v.del_gop = base + 3 * stride; v.gcp = base + 4 * stride; v.hap_bases = base + 5 * stride;
+  return v;
 }
-// Which host-buffer calls are deferred -- planned and staged by run_device, launched by the small-call combiner, alone or
-// in one set of launches with others (concurrent callers' calls, the regions of one gklhip_compute_multi): inputs inline
-// (<= kSmallBatchBytes), not switched off (GKL_HIP_COMBINE=0), and -- once the call is planned -- plan block pulled,
-// per-pair call, no long read, host-exact packed finalisation, no event recording, at most kTwoStepFrom pairs.
-// Without a plan: what a host call knows before run_device has planned it (whether to offer deferral at all).
-bool small_call_defers(const DevCtx* c, bool inline_host, int finalize_mode = kModePacked, int64_t n_pairs = 0, const Plan* plan = nullptr,
-                       size_t plan_bytes = 0, int n_long64 = 0) {
-  if (!g_env.combine || !inline_host) return false;
-  if (!plan) return true;
-  return plan_pulled(plan_bytes) && c->cfg.record_events == 0 && per_pair_policy_call(c, n_pairs, n_long64, plan->max_read_len) &&
-         plan->long_reads.empty() && finalize_mode == kModePacked && plan->n_chunks > 0 && n_pairs <= kTwoStepFrom;
+// ... and the arrays of `b` on their way there: put(offset in the buffer, source, bytes) is the copy (memcpy, H2D, peer)
+template <typename F>
+int copy_six_arrays(const gklhip_batch& b, size_t stride, F put) {
+  const size_t rl = (size_t)b.read_off[b.n_reads], hl = (size_t)b.hap_off[b.n_haps];
+  const uint8_t* srcs[5] = {b.read_bases, b.read_quals, b.ins_gop, b.del_gop, b.gcp};
+  for (int i = 0; i < 5; i++)
+    if (int rc = put(i * stride, srcs[i], rl)) return rc;
+  return put(5 * stride, b.hap_bases, hl);
 }
 
-// The whole device-side pipeline on stream `s`: 7 launches in the policy mode (prep, fp32 forward, the three launches of
-// policy + planning of the fp64 pass, fp64 forward over the job list, log10 / packed words of the recomputed pairs; + the
-// log10 of the kept pairs on a side stream in the device finalisation modes), 3-4 for calls of up to 65 536 pairs (prep,
-// fp32 forward, per-pair policy in one or two launches), 2 for up to 2048 (prep, the fused per-pair kernel); no host
-// synchronisation.  `db` holds host offsets and DEVICE byte
-// arrays -- or, with `inline_host`, HOST byte arrays that travel inside the plan block (small host-buffer calls: one
-// copy for plan and inputs).
-// `defer` (host-buffer calls on an idle context only): a call that takes the small-call path -- pulled plan block,
-// per-pair policy -- is planned and staged but NOT launched; its descriptor is returned in *defer (filled = true).
-// With defer->only, a call that does not qualify is not run at all (the regions of a multi call are staged on lanes that
-// have no stream of their own); with defer->probe on top, the call is only planned and asked whether it qualifies.
-int run_device(DevCtx* c, const gklhip_batch* db, double* out_dev, int finalize_mode, hipStream_t s, bool inline_host,
-               SmallLaunch* defer = nullptr) {
-  const int n_reads = db->n_reads, n_haps = db->n_haps;
-  const int64_t n_pairs = (int64_t)n_reads * n_haps;
+// ---- step 1: the plan.  Everything a call decides before it touches the device, on the caller's stack. ----
+struct CallPlan {
+  int n_reads, n_haps;
+  int64_t n_pairs;               // 0: an empty call -- nothing else is set, and nothing is staged or launched
+  size_t rl, hl;                 // read / haplotype bases
+  int finalize_mode, fma, rpl_main, carry_len;
+  bool inline_host, use_double;  // inline_host: the batch's byte arrays are HOST arrays that travel inside the plan block
+  int n_long_main, n_long64;     // reads too long for a chunk of the main pass / of the packed fp64 pass
+  PlanLayout L;
+  bool pull;                     // the prep kernel pulls the block from pinned memory (plan_pulled)
+  bool per_pair, fused;          // policy + fp64 of one pair per wavefront; ... with the fp32 recurrence in the same wavefront and launch
+  int rows;                      // rows per lane of the per-pair kernels, by the longest read
+  bool defers;                   // planned and staged, then handed to the small-call combiner (small_call_defers)
+  int n_hist, chunk_stride, n_main_blocks, n_long_waves;   // grids and sizes that follow from the plan
+  size_t striped_carry_bytes;
+  int64_t xsteps;                // steps of a super-stripe carry row (0: no read needs super-stripes)
+  std::chrono::steady_clock::time_point t0;   // (GKLHIP_TIMING)
+};
+
+// Which host-buffer calls are deferred -- planned and staged, then launched by the small-call combiner, alone or in one
+// set of launches with others (concurrent callers' calls, the regions of one gklhip_compute_multi).  What a host call
+// knows before it is planned (whether to offer deferral at all): inputs inline, not switched off (GKL_HIP_COMBINE=0) ...
+bool deferral_offered(bool inline_host) { return g_env.combine && inline_host; }
+// ... and of a planned call that was offered it (plan_call, nowhere else): plan block pulled, per-pair call, no long
+// read, host-exact packed finalisation, no event recording, at most kTwoStepFrom pairs.
+bool small_call_defers(const DevCtx* c, const CallPlan& P) {
+  return deferral_offered(P.inline_host) && P.pull && c->cfg.record_events == 0 && P.per_pair && c->plan.long_reads.empty() &&
+         P.finalize_mode == kModePacked && c->plan.n_chunks > 0 && P.n_pairs <= kTwoStepFrom;
+}
+// `load` of pick_f32_rpl: 1 for a call that is not offered deferral.  (About half of the calls inside the library are on
+// the device at any moment, the others are being staged or finalised: 16 callers of 100 x 10 regions keep the 4-row
+// kernel -- the 8-row one needs three wavefronts per SIMD to pay, tools/small_scaling.py -- and 32 callers get the 8-row one.)
+int call_load(bool deferral) {
+  return !deferral ? 1 : g_env.combine_load > 0 ? g_env.combine_load : std::max(1, g_host_calls_in_flight.load(std::memory_order_relaxed) / 2);
+}
+
+// Host only: no HIP call, no stream.  Fills c->plan, c->long_lanes, c->long_jobs and the statistics a plan decides.
+// `db` holds host offsets; the byte arrays are not read.
+void plan_call(DevCtx* c, const gklhip_batch* db, int finalize_mode, bool inline_host, bool deferral, int load, CallPlan* out) {
+  CallPlan& P = *out;
+  const int n_reads = P.n_reads = db->n_reads, n_haps = P.n_haps = db->n_haps;
+  P.n_pairs = (int64_t)n_reads * n_haps;
+  P.defers = false;
   gklhip_stats& st = c->stats;
   memset(&st, 0, sizeof st);
-  st.n_pairs = n_pairs;
+  st.n_pairs = P.n_pairs;
   c->have_last = false;
-  if (n_pairs == 0) return GKLHIP_OK;
-  const bool use_double = c->cfg.use_double != 0;
-  const int fma = c->cfg.fma_mode != 0;
-
-  // ---- plan (host) ----
-  const auto t_plan0 = std::chrono::steady_clock::now();
+  if (P.n_pairs == 0) return;
+  P.finalize_mode = finalize_mode;
+  P.inline_host = inline_host;
+  P.use_double = c->cfg.use_double != 0;
+  P.fma = c->cfg.fma_mode != 0;
+  P.t0 = std::chrono::steady_clock::now();
   Plan& plan = c->plan;
-  const int rpl64 = kRplF64Jobs;
-  const int load_env = g_env.combine_load;
-  // (about half of the calls inside the library are on the device at any moment, the others are being staged or
-  //  finalised: 16 callers of 100 x 10 regions keep the 4-row kernel -- the 8-row one needs three wavefronts per SIMD
-  //  to pay, tools/small_scaling.py -- and 32 callers get the 8-row one)
-  const int load = !defer ? 1 : load_env > 0 ? load_env : std::max(1, g_host_calls_in_flight.load(std::memory_order_relaxed) / 2);
-  const int rpl_main = use_double ? rpl64 : pick_f32_rpl(c->cfg.rows_per_lane, n_reads, n_haps, db->read_off, db->hap_off, load);
-  const int target_cols_env = g_env.target_cols;
-  build_plan(n_reads, n_haps, db->read_off, db->hap_off, rpl_main, target_cols_env > 0 ? target_cols_env : kTargetCols, &plan);
+  P.rpl_main = P.use_double ? kRplF64Jobs : pick_f32_rpl(c->cfg.rows_per_lane, n_reads, n_haps, db->read_off, db->hap_off, load);
+  build_plan(n_reads, n_haps, db->read_off, db->hap_off, P.rpl_main, g_env.target_cols > 0 ? g_env.target_cols : kTargetCols, &plan);
   // Long reads: pseudo-chunks (lane 0 names the read) + one striped job per (read, stream group)
   // for the main pass; for the fp64 fallback the same pseudo-chunks feed the run detection.
   std::vector<PlanLane>& long_lanes = c->long_lanes;
   std::vector<FwdJob>& long_jobs = c->long_jobs;
   long_lanes.clear(); long_jobs.clear();
-  const std::vector<int32_t>& long_main = plan.long_reads;
-  const int n_long_main = (int)long_main.size();
+  P.n_long_main = (int)plan.long_reads.size();
   // pseudo-chunk index space: [0, n_long_main) main-pass reads, then [n_long_main, +n_long64) fp64-pass reads
-  for (int32_t r : long_main) { long_lanes.resize(long_lanes.size() + kLanes, PlanLane{-1, 0}); long_lanes[long_lanes.size() - kLanes] = PlanLane{r, 0}; }
-  int n_long64 = 0;  // reads too long for the packed fp64 pass
-  if (!use_double && plan.max_read_len > kLanes * kRplF64Jobs - 1)
+  auto pseudo_chunk = [&](int32_t r) { long_lanes.resize(long_lanes.size() + kLanes, PlanLane{-1, 0}); long_lanes[long_lanes.size() - kLanes] = PlanLane{r, 0}; };
+  for (int32_t r : plan.long_reads) pseudo_chunk(r);
+  P.n_long64 = 0;  // reads too long for the packed fp64 pass
+  if (!P.use_double && plan.max_read_len > kLanes * kRplF64Jobs - 1)
     for (int r = 0; r < n_reads; r++)
-      if (blocks_for((int)(db->read_off[r + 1] - db->read_off[r]), kRplF64Jobs) > kLanes) {
-        long_lanes.resize(long_lanes.size() + kLanes, PlanLane{-1, 0});
-        long_lanes[long_lanes.size() - kLanes] = PlanLane{r, 0};
-        n_long64++;
-      }
-  for (int i = 0; i < n_long_main; i++)
+      if (blocks_for((int)(db->read_off[r + 1] - db->read_off[r]), kRplF64Jobs) > kLanes) { pseudo_chunk(r); P.n_long64++; }
+  for (int i = 0; i < P.n_long_main; i++)
     for (const PlanGroup& g : plan.groups) long_jobs.push_back(FwdJob{i, g.hap_begin, g.hap_end, 0});
   int carry_len = 0;
   for (const PlanGroup& g : plan.groups) {
     const int last = g.hap_end - 1;
     carry_len = std::max(carry_len, plan.hap_pos[last] + plan.hap_len[last] - plan.hap_pos[g.hap_begin] + 3 * kLanes);
   }
-  carry_len = (carry_len + 63) / 64 * 64;
-  const size_t rl = (size_t)db->read_off[n_reads], hl = (size_t)db->hap_off[n_haps];
-  const PlanLayout L = layout_for(plan, n_reads, n_haps, long_lanes.size(), long_jobs.size(), inline_host ? rl : 0, inline_host ? hl : 0);
-  const bool pull = plan_pulled(L.total);
-  const bool per_pair_call = per_pair_policy_call(c, n_pairs, n_long64, plan.max_read_len);
+  P.carry_len = (carry_len + 63) / 64 * 64;
+  P.rl = (size_t)db->read_off[n_reads]; P.hl = (size_t)db->hap_off[n_haps];
+  P.L = layout_for(plan, n_reads, n_haps, long_lanes.size(), long_jobs.size(), inline_host ? P.rl : 0, inline_host ? P.hl : 0);
+  P.pull = plan_pulled(P.L.total);
+  // policy + fp64 recomputation of one pair per wavefront (the kernel holds at most 64 x kRplF64 - 1 rows)
+  P.per_pair = !P.use_double && P.n_pairs <= kDirectPairs && P.n_long64 == 0 && plan.max_read_len <= kLanes * kRplF64 - 1;
   // ... the tiny ones (one GATK active region) with the fp32 recurrence in the same wavefront and launch as the policy
-  const bool fused_env = g_env.fused_pairs;
   const int64_t fused_max = g_env.fused_max >= 0 ? g_env.fused_max : (int64_t)kTwoStepFrom;
-  const bool fused_call = per_pair_call && fused_env && n_pairs <= fused_max && n_long_main == 0 && c->cfg.rows_per_lane == 0;
-  const bool deferred_launch = defer && small_call_defers(c, inline_host, finalize_mode, n_pairs, &plan, L.total, n_long64);
-  if (defer && defer->only) {
-    defer->qualifies = deferred_launch;
-    defer->call.fused = fused_call ? 1 : 0;
-    if (!deferred_launch || defer->probe) return GKLHIP_OK;   // (nothing staged, nothing launched)
-  }
+  P.fused = P.per_pair && g_env.fused_pairs && P.n_pairs <= fused_max && P.n_long_main == 0 && c->cfg.rows_per_lane == 0;
+  P.rows = plan.max_read_len <= 2 * kLanes - 1 ? 2 : plan.max_read_len <= 4 * kLanes - 1 ? 4 : kRplF64;
+  P.defers = deferral && small_call_defers(c, P);
 
-  // ---- stage + upload plan ----
-  int rc;
-  const int slot = c->plan_slot ^= 1;
-  PinBuf& stage = c->stage_slot[slot];
-  DevBuf& plan_dev = c->plan_dev_slot[slot];
-  HIP_TRY(hipEventSynchronize(c->stage_free_slot[slot]));
-  if (L.total > stage.cap || L.total > plan_dev.cap) HIP_TRY(hipEventSynchronize(c->plan_unused_slot[slot]));  // about to reallocate
-  if ((rc = stage.reserve(L.total))) return rc;
-  if ((rc = plan_dev.reserve(L.total))) return rc;
-  unsigned char* hs = stage.as<unsigned char>();
+  P.n_hist = P.use_double ? 0 : 2 * (n_haps + 2);
+  // XCD-aware grid of the streaming kernels (fwd_stream_block): a chunk's jobs all land on one XCD
+  // (c->n_xcds: what the device reports -- 8 on an MI355X in SPX mode; a partitioned device shows fewer and gets no padding it cannot use)
+  const int xq = c->n_xcds;
+  P.chunk_stride = (g_env.xcd_aware && xq > 1 && plan.n_chunks >= 64) ? (plan.n_chunks + xq - 1) / xq * xq : plan.n_chunks;
+  P.n_main_blocks = P.chunk_stride * (int)plan.groups.size();
+  // persistent wavefronts of the striped long-read kernel: one per job up to two per SIMD (each owns two carry rows of
+  // the longest stream group: ~110 KB)
+  P.n_long_waves = (int)std::min<size_t>(2048, std::max<size_t>(512, std::max(long_jobs.size(), (size_t)P.n_long64 * plan.groups.size())));
+  // ... and, when a read needs more wavefronts than a wide workgroup holds, the super-stripe kernel's carry rows behind them
+  P.striped_carry_bytes = (size_t)P.n_long_waves * 2 * (3 * (size_t)P.carry_len + 64) * sizeof(double);
+  const bool super_long = (blocks_for(plan.max_read_len, kRplF32) + kLanes - 1) / kLanes > kWideWavesMax;
+  P.xsteps = super_long ? super_steps(P.carry_len, plan.max_read_len, kRplF32) : 0;   // (fp32 and fp64 both run the long reads at 8 rows per lane)
+  static_assert(kRplF32 == kRplF64Wide, "one array depth for the long reads of both precisions");
+
+  st.n_long_pairs = (int32_t)std::min<int64_t>((int64_t)P.n_long_main * n_haps, 0x7fffffff);
+  st.n_chunks = plan.n_chunks;
+  st.n_hap_groups = (int)plan.groups.size();
+  st.rows_per_lane = P.rpl_main;
+  st.lane_fill = plan.n_chunks ? (float)((double)plan.useful_rows / ((double)plan.n_chunks * 64 * P.rpl_main)) : 0.f;
+  st.cells = (int64_t)P.rl * (int64_t)P.hl;
+}
+
+// ---- step 2: the plan block and its way to the device ----
+// the haplotype streams and 'N' flags of a host call (what prep_kernel builds on the device for resident batches)
+void build_host_streams(unsigned char* hs, const PlanLayout& L, const Plan& plan, const uint8_t* hap_bases, int n_haps) {
+  uint32_t* sg = reinterpret_cast<uint32_t*>(hs + L.stream);
+  uint32_t* sf = reinterpret_cast<uint32_t*>(hs + L.stream_flat);
+  uint8_t* hn = hs + L.has_n;
+  for (int k = 0; k < n_haps; k++) {
+    const uint8_t* src = hap_bases + plan.hap_src[k];
+    const int len = plan.hap_len[k], pg = plan.hap_pos[k], pf = plan.hap_pos_flat[k];
+    bool has_n = false;
+    for (int col = 0; col < len; col++) {
+      const uint8_t bb = src[col];  // pairhmm_common.h:57-61: A0 C1 T2 G3 N4, anything else 0
+      const uint32_t e = bb == 'C' ? 1u : bb == 'T' ? 2u : bb == 'G' ? 3u : bb == 'N' ? 4u : 0u;
+      sg[pg + col] = e; sf[pf + col] = e;
+      has_n |= bb == 'N';
+    }
+    sg[pg + len] = kEntSep | (uint32_t)k;
+    sf[pf + len] = kEntSep | (uint32_t)k;
+    hn[k] = has_n ? 1 : 0;
+    if (k + 1 == n_haps || plan.hap_group[k + 1] != plan.hap_group[k])
+      for (int i = 0; i < kLanes; i++) sg[pg + len + 1 + i] = kEntIdle;
+    if (k + 1 == n_haps)
+      for (int i = 0; i < kLanes; i++) sf[pf + len + 1 + i] = kEntIdle;
+  }
+}
+// Writes the block at `hs` (P.L.total bytes of plain memory; no HIP object is touched).
+void fill_plan_block(unsigned char* hs, const CallPlan& P, const Plan& plan, const std::vector<PlanLane>& long_lanes,
+                     const std::vector<FwdJob>& long_jobs, const gklhip_batch* db) {
+  const PlanLayout& L = P.L;
+  const int n_reads = P.n_reads, n_haps = P.n_haps;
   memcpy(hs + L.place_chunk, plan.place_chunk.data(), (size_t)n_reads * 4);
   memcpy(hs + L.place_lane, plan.place_lane.data(), (size_t)n_reads);
   memcpy(hs + L.chunk_used, plan.chunk_used.data(), (size_t)plan.n_chunks);
@@ -437,51 +496,57 @@ int run_device(DevCtx* c, const gklhip_batch* db, double* out_dev, int finalize_
   if (!long_lanes.empty()) memcpy(hs + L.long_lanes, long_lanes.data(), long_lanes.size() * sizeof(PlanLane));
   if (!long_jobs.empty()) memcpy(hs + L.long_jobs, long_jobs.data(), long_jobs.size() * sizeof(FwdJob));
   {
-    int32_t lc[4] = {(int32_t)long_jobs.size(), n_long_main, n_long64, 0};
+    int32_t lc[4] = {(int32_t)long_jobs.size(), P.n_long_main, P.n_long64, 0};
     memcpy(hs + L.long_count, lc, sizeof lc);
   }
-  unsigned char* dp = plan_dev.as<unsigned char>();
-  gklhip_batch dbi = *db;  // device pointers of the six byte arrays
-  if (inline_host) {
-    const uint8_t* srcs[5] = {db->read_bases, db->read_quals, db->ins_gop, db->del_gop, db->gcp};
-    for (int i = 0; i < 5; i++) memcpy(hs + L.batch + i * L.batch_stride, srcs[i], rl);
-    memcpy(hs + L.batch + 5 * L.batch_stride, db->hap_bases, hl);
-    unsigned char* d = dp + L.batch;
-    dbi.read_bases = d; dbi.read_quals = d + L.batch_stride; dbi.ins_gop = d + 2 * L.batch_stride;
-    dbi.del_gop = d + 3 * L.batch_stride; dbi.gcp = d + 4 * L.batch_stride; dbi.hap_bases = d + 5 * L.batch_stride;
-    // the haplotype streams (what prep_kernel builds on the device for resident batches)
-    uint32_t* sg = reinterpret_cast<uint32_t*>(hs + L.stream);
-    uint32_t* sf = reinterpret_cast<uint32_t*>(hs + L.stream_flat);
-    uint8_t* hn = hs + L.has_n;
-    for (int k = 0; k < n_haps; k++) {
-      const uint8_t* src = db->hap_bases + plan.hap_src[k];
-      const int len = plan.hap_len[k], pg = plan.hap_pos[k], pf = plan.hap_pos_flat[k];
-      bool has_n = false;
-      for (int col = 0; col < len; col++) {
-        const uint8_t bb = src[col];  // pairhmm_common.h:57-61: A0 C1 T2 G3 N4, anything else 0
-        const uint32_t e = bb == 'C' ? 1u : bb == 'T' ? 2u : bb == 'G' ? 3u : bb == 'N' ? 4u : 0u;
-        sg[pg + col] = e; sf[pf + col] = e;
-        has_n |= bb == 'N';
-      }
-      sg[pg + len] = kEntSep | (uint32_t)k;
-      sf[pf + len] = kEntSep | (uint32_t)k;
-      hn[k] = has_n ? 1 : 0;
-      if (k + 1 == n_haps || plan.hap_group[k + 1] != plan.hap_group[k])
-        for (int i = 0; i < kLanes; i++) sg[pg + len + 1 + i] = kEntIdle;
-      if (k + 1 == n_haps)
-        for (int i = 0; i < kLanes; i++) sf[pf + len + 1 + i] = kEntIdle;
-    }
+  if (P.inline_host) {
+    unsigned char* dst = hs + L.batch;
+    copy_six_arrays(*db, L.batch_stride, [dst](size_t at, const uint8_t* src, size_t n) { memcpy(dst + at, src, n); return 0; });
+    build_host_streams(hs, L, plan, db->hap_bases, n_haps);
   }
+}
+
+// A call whose block is on its way to the device and whose scratch is reserved: what the argument builders point at.
+struct StagedCall {
+  hipStream_t s;
+  double* out;
+  int slot;
+  unsigned char* hs;            // the pinned staging block
+  const unsigned char* hs_dev;  // ... as the device sees it (pulled plans only)
+  unsigned char* dp;            // the device copy of the block
+  DevBatch b;                   // the batch as the forward kernels see it
+  const uint8_t* hap_bases;     // ... and its haplotype bases as the prep kernel does
+  uint32_t *stream_grouped, *stream_flat;
+  uint8_t *hap_has_n, *xcarry;  // xcarry: carry rows of the super-stripe kernel (reserve_carry)
+};
+
+// `db` holds host offsets and DEVICE byte arrays -- or, with P.inline_host, HOST byte arrays that travel inside the plan
+// block (small host-buffer calls: one copy for plan and inputs).  Flips c->plan_slot.
+int stage_call(DevCtx* c, const gklhip_batch* db, const CallPlan& P, double* out_dev, hipStream_t s, StagedCall* out) {
+  const PlanLayout& L = P.L;
+  const Plan& plan = c->plan;
+  StagedCall& S = *out;
+  int rc;
+  const int slot = c->plan_slot ^= 1;
+  PinBuf& stage = c->stage_slot[slot];
+  DevBuf& plan_dev = c->plan_dev_slot[slot];
+  HIP_TRY(hipEventSynchronize(c->stage_free_slot[slot]));
+  if (L.total > stage.cap || L.total > plan_dev.cap) HIP_TRY(hipEventSynchronize(c->plan_unused_slot[slot]));  // about to reallocate
+  if ((rc = stage.reserve(L.total))) return rc;
+  if ((rc = plan_dev.reserve(L.total))) return rc;
+  unsigned char* hs = stage.as<unsigned char>();
+  fill_plan_block(hs, P, plan, c->long_lanes, c->long_jobs, db);
+  unsigned char* dp = plan_dev.as<unsigned char>();
   // scratch is shared by the calls of a context: one on another stream than the last one waits for that one's end
   if (c->have_call_done && c->last_stream != s) HIP_TRY(hipStreamWaitEvent(s, c->call_done, 0));
-  // Big plans ride the upload stream (the copy overlaps the previous call's kernels); a small plan (GATK-sized
-  // call) is PULLED from the pinned staging block by the prep kernel itself: no copy-engine hop at all.
-  const unsigned char* hs_dev = nullptr;  // the staging block as the device sees it
-  if (pull) {
+  // Big plans ride the upload stream (the copy overlaps the previous call's kernels); a small one is pulled (plan_pulled).
+  S.hs_dev = nullptr;
+  if (P.pull) {
     void* p = nullptr;
     HIP_TRY(hipHostGetDevicePointer(&p, hs, 0));
-    hs_dev = static_cast<const unsigned char*>(p);
-    if (!deferred_launch) HIP_TRY(hipStreamWaitEvent(s, c->plan_unused_slot[slot], 0));
+    S.hs_dev = static_cast<const unsigned char*>(p);
+    // (a deferred call is launched by the combiner, maybe on another stream: a lane's slot events are never recorded)
+    if (!P.defers) HIP_TRY(hipStreamWaitEvent(s, c->plan_unused_slot[slot], 0));
   } else {
     if ((rc = aux_streams(c))) return rc;
     HIP_TRY(hipStreamWaitEvent(c->upload_stream, c->plan_unused_slot[slot], 0));  // readers of the old contents are done
@@ -489,337 +554,339 @@ int run_device(DevCtx* c, const gklhip_batch* db, double* out_dev, int finalize_
     HIP_TRY(hipEventRecord(c->stage_free_slot[slot], c->upload_stream));
     HIP_TRY(hipStreamWaitEvent(s, c->stage_free_slot[slot], 0));                    // kernels below read the new plan
   }
-  const bool timing = g_env.timing;
-  if (timing)
+  if (g_env.timing)
     fprintf(stderr, "[gklhip] host plan + staging: %.3f ms (%d chunks, %d stream entries, %zu plan bytes)\n",
-            std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_plan0).count(),
+            std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - P.t0).count(),
             plan.n_chunks, plan.n_stream, L.total);
 
   // ---- scratch ----
-  if ((rc = c->raw32.reserve((size_t)n_pairs * 4))) return rc;
-  if ((rc = c->raw64.reserve((size_t)n_pairs * 8))) return rc;
-  if ((rc = c->used64.reserve((size_t)n_pairs))) return rc;
+  if ((rc = c->raw32.reserve((size_t)P.n_pairs * 4))) return rc;
+  if ((rc = c->raw64.reserve((size_t)P.n_pairs * 8))) return rc;
+  if ((rc = c->used64.reserve((size_t)P.n_pairs))) return rc;
   if ((rc = c->counters.reserve(128))) return rc;
-  if ((rc = c->read_fail.reserve((size_t)n_reads * 4))) return rc;
+  if ((rc = c->read_fail.reserve((size_t)P.n_reads * 4))) return rc;
   if ((rc = c->stream_buf.reserve(((size_t)plan.n_stream + (size_t)plan.n_stream_flat) * 4))) return rc;
-  const int n_hist = use_double ? 0 : 2 * (n_haps + 2);
-  if (!use_double && (rc = c->fail_hist.reserve((size_t)n_hist * 4))) return rc;
-  if ((rc = c->hap_flags.reserve((size_t)n_haps))) return rc;
+  if (!P.use_double && (rc = c->fail_hist.reserve((size_t)P.n_hist * 4))) return rc;
+  if ((rc = c->hap_flags.reserve((size_t)P.n_haps))) return rc;
   if ((rc = c->lanes_main.reserve((size_t)std::max(plan.n_chunks, 1) * kLanes * sizeof(LaneSlot)))) return rc;
 
-  const bool ev = c->cfg.record_events != 0;
-  const bool deferred = c->cfg.record_events == 2;
-  if (ev) {
-    c->ev = c->ev_ring[deferred ? c->calls % DevCtx::kEventRing : 0];
-    c->ring_double[deferred ? c->calls % DevCtx::kEventRing : 0] = use_double;
-    c->calls++;
-  }
-  if (ev) HIP_TRY(hipEventRecord(c->ev[0], s));
+  S.s = s; S.out = out_dev; S.slot = slot; S.hs = hs; S.dp = dp; S.xcarry = nullptr;
+  // the six byte arrays as the device reads them: inside the block, or where the caller put them
+  const gklhip_batch dbi = P.inline_host ? batch_at(*db, dp + L.batch, L.batch_stride) : *db;
+  S.b = DevBatch{dbi.read_bases, dbi.read_quals, dbi.ins_gop, dbi.del_gop, dbi.gcp, reinterpret_cast<const int64_t*>(dp + L.read_off), P.n_reads, P.n_haps};
+  // (pulling: the prep kernel reads the HOST copy of the block)
+  S.hap_bases = (P.pull && P.inline_host) ? batch_at(*db, S.hs_dev + L.batch, L.batch_stride).hap_bases : dbi.hap_bases;
+  // (host-built streams arrive with the block; the prep kernel then only pulls and clears)
+  S.stream_grouped = P.inline_host ? reinterpret_cast<uint32_t*>(dp + L.stream) : c->stream_buf.as<uint32_t>();
+  S.stream_flat = P.inline_host ? reinterpret_cast<uint32_t*>(dp + L.stream_flat) : c->stream_buf.as<uint32_t>() + plan.n_stream;
+  S.hap_has_n = P.inline_host ? dp + L.has_n : c->hap_flags.as<uint8_t>();
+  return GKLHIP_OK;
+}
 
-  // ---- haplotype streams + clears: one launch ----
-  uint32_t *stream_grouped = nullptr, *stream_flat = nullptr;
-  uint8_t* hap_has_n = nullptr;
-  {
-    PrepArgs pa;
-    const unsigned char* pb = pull ? hs_dev : dp;  // pulling: this kernel reads the HOST copy of the plan
-    pa.hap_bases = (pull && inline_host) ? pb + L.batch + 5 * L.batch_stride : dbi.hap_bases;
-    pa.hap_src = reinterpret_cast<const int32_t*>(pb + L.hap_src);
-    pa.hap_len = reinterpret_cast<const int32_t*>(pb + L.hap_len);
-    pa.hap_pos = reinterpret_cast<const int32_t*>(pb + L.hap_pos);
-    pa.hap_group = reinterpret_cast<const int32_t*>(pb + L.hap_group);
-    // (host-built streams: they arrive with the pulled block; this kernel then only pulls and clears)
-    const bool host_streams = inline_host;
-    stream_grouped = host_streams ? reinterpret_cast<uint32_t*>(dp + L.stream) : c->stream_buf.as<uint32_t>();
-    stream_flat = host_streams ? reinterpret_cast<uint32_t*>(dp + L.stream_flat) : c->stream_buf.as<uint32_t>() + plan.n_stream;
-    hap_has_n = host_streams ? dp + L.has_n : c->hap_flags.as<uint8_t>();
-    pa.stream = stream_grouped;
-    // the flat stream (no gaps between groups): the fp64 recomputation's jobs are arbitrary runs of it
-    pa.hap_pos_flat = use_double ? nullptr : reinterpret_cast<const int32_t*>(pb + L.hap_pos_flat);
-    pa.stream_flat = stream_flat;
-    pa.hap_has_n = hap_has_n;
-    pa.n_haps = host_streams ? 0 : n_haps;
-    pa.clear_a = c->counters.as<int32_t>(); pa.n_a = 32;
-    pa.clear_b = c->read_fail.as<int32_t>(); pa.n_b = use_double ? 0 : n_reads;
-    pa.clear_c = c->fail_hist.as<int32_t>(); pa.n_c = n_hist;
-    pa.place_chunk = reinterpret_cast<const int32_t*>(pb + L.place_chunk);
-    pa.place_lane = pb + L.place_lane;
-    pa.chunk_used = pb + L.chunk_used;
-    pa.read_off = reinterpret_cast<const int64_t*>(pb + L.read_off);
-    pa.lanes_out = c->lanes_main.as<LaneSlot>();
-    pa.n_reads = n_reads; pa.n_chunks = plan.n_chunks; pa.rpl = rpl_main;
-    const int threads_needed = std::max({pa.n_haps * 64, 32, pa.n_b, pa.n_c, n_reads});
-    pa.hap_blocks = (threads_needed + kPrepBlock - 1) / kPrepBlock;
-    pa.pull_src = reinterpret_cast<const uint4*>(hs_dev);
-    pa.pull_dst = reinterpret_cast<uint4*>(dp);
-    pa.pull_n16 = pull ? (int32_t)(L.total / 16) : 0;
-    const int pull_blocks = pull ? (int)std::min<size_t>(64, (L.total / 16 + kPrepBlock * 4 - 1) / (kPrepBlock * 4)) : 0;
-    if (deferred_launch) {
-      defer->call.prep = pa;
-      defer->call.prep_grid = pa.hap_blocks + pull_blocks;
-    } else {
-      hipLaunchKernelGGL(prep_kernel, dim3((unsigned)(pa.hap_blocks + pull_blocks)), dim3(kPrepBlock), 0, s, pa);
-      if (pull) HIP_TRY(hipEventRecord(c->stage_free_slot[slot], s));
-    }
-  }
+// ---- step 3: the kernels' arguments, each a function of (context, plan, staged call) ----
+// haplotype streams + clears + the pull of the block: one launch
+PrepArgs prep_args(const DevCtx* c, const CallPlan& P, const StagedCall& S) {
+  const PlanLayout& L = P.L;
+  PrepArgs pa;
+  const unsigned char* pb = P.pull ? S.hs_dev : S.dp;  // pulling: this kernel reads the HOST copy of the plan
+  pa.hap_bases = S.hap_bases;
+  pa.hap_src = reinterpret_cast<const int32_t*>(pb + L.hap_src);
+  pa.hap_len = reinterpret_cast<const int32_t*>(pb + L.hap_len);
+  pa.hap_pos = reinterpret_cast<const int32_t*>(pb + L.hap_pos);
+  pa.hap_group = reinterpret_cast<const int32_t*>(pb + L.hap_group);
+  pa.stream = S.stream_grouped;
+  // the flat stream (no gaps between groups): the fp64 recomputation's jobs are arbitrary runs of it
+  pa.hap_pos_flat = P.use_double ? nullptr : reinterpret_cast<const int32_t*>(pb + L.hap_pos_flat);
+  pa.stream_flat = S.stream_flat;
+  pa.hap_has_n = S.hap_has_n;
+  pa.n_haps = P.inline_host ? 0 : P.n_haps;   // (host-built streams)
+  pa.clear_a = c->counters.as<int32_t>(); pa.n_a = 32;
+  pa.clear_b = c->read_fail.as<int32_t>(); pa.n_b = P.use_double ? 0 : P.n_reads;
+  pa.clear_c = c->fail_hist.as<int32_t>(); pa.n_c = P.n_hist;
+  pa.place_chunk = reinterpret_cast<const int32_t*>(pb + L.place_chunk);
+  pa.place_lane = pb + L.place_lane;
+  pa.chunk_used = pb + L.chunk_used;
+  pa.read_off = reinterpret_cast<const int64_t*>(pb + L.read_off);
+  pa.lanes_out = c->lanes_main.as<LaneSlot>();
+  pa.n_reads = P.n_reads; pa.n_chunks = c->plan.n_chunks; pa.rpl = P.rpl_main;
+  const int threads_needed = std::max({pa.n_haps * 64, 32, pa.n_b, pa.n_c, P.n_reads});
+  pa.hap_blocks = (threads_needed + kPrepBlock - 1) / kPrepBlock;
+  pa.pull_src = reinterpret_cast<const uint4*>(S.hs_dev);
+  pa.pull_dst = reinterpret_cast<uint4*>(S.dp);
+  pa.pull_n16 = P.pull ? (int32_t)(L.total / 16) : 0;
+  return pa;
+}
+int prep_grid(const PrepArgs& pa, const CallPlan& P) {
+  return pa.hap_blocks + (P.pull ? (int)std::min<size_t>(64, (P.L.total / 16 + kPrepBlock * 4 - 1) / (kPrepBlock * 4)) : 0);
+}
 
-  DevBatch b;
-  b.read_bases = dbi.read_bases; b.read_quals = dbi.read_quals; b.ins = dbi.ins_gop;
-  b.del = dbi.del_gop; b.gcp = dbi.gcp;
-  b.read_off = reinterpret_cast<const int64_t*>(dp + L.read_off);
-  b.n_reads = n_reads; b.n_haps = n_haps;
-
-  // XCD-aware grid of the streaming kernels (fwd_stream_block): a chunk's jobs all land on one XCD
-  const bool xcd_env = g_env.xcd_aware;
-  // (c->n_xcds: what the device reports -- 8 on an MI355X in SPX mode; a partitioned device shows fewer and gets no padding it cannot use)
-  const int xq = c->n_xcds;
-  const int chunk_stride = (xcd_env && xq > 1 && plan.n_chunks >= 64) ? (plan.n_chunks + xq - 1) / xq * xq : plan.n_chunks;
-  auto fill_common = [&](auto& a) {
-    a.b = b;
-    a.stream = stream_grouped;
-    a.hap_len = reinterpret_cast<const int32_t*>(dp + L.hap_len);
-    a.hap_pos = reinterpret_cast<const int32_t*>(dp + L.hap_pos);
-    a.hap_orig = reinterpret_cast<const int32_t*>(dp + L.hap_orig);
-    a.hap_has_n = hap_has_n;
-    a.groups = reinterpret_cast<const HapGroup*>(dp + L.groups);
-    a.n_groups = (int)plan.groups.size();
-    a.chunk_lanes = c->lanes_main.as<LaneSlot>();
-    a.n_chunks = plan.n_chunks;
-    a.chunk_stride = chunk_stride;
-    a.jobs = c->jobs.as<FwdJob>();
-    a.job_count = c->counters.as<int32_t>() + 2;
-    a.job_next = c->counters.as<int32_t>() + 3;
-    // the fp32 programs fetch a separator lane's priors from beyond the LDS allocation: only where that reads 0 (dev_init)
-    constexpr bool is_f32 = std::is_same<typename std::decay<decltype(a)>::type, FwdArgs<float>>::value;
-    a.asm_general = (c->asm_general && (!is_f32 || c->lds_oob_zero)) ? 1 : 0;
-  };
-
-  FinalizeArgs fa;
-  fa.raw32 = c->raw32.as<float>(); fa.raw64 = c->raw64.as<double>(); fa.out = out_dev;
-  fa.used64 = c->used64.as<uint8_t>();
-  fa.count = c->counters.as<int32_t>(); fa.n = n_pairs; fa.mode = finalize_mode;
-  fa.read_fail = c->read_fail.as<int32_t>(); fa.n_haps = n_haps;
-  fa.log10_init_f = host_tables_f32().log10_initial;
-  fa.log10_init32_as_f64 = std::log10(std::ldexp(1.0, 120));
-  fa.log10_init_d = host_tables_f64().log10_initial;
-
-  const int n_main_blocks = chunk_stride * (int)plan.groups.size();
-  // persistent wavefronts of the striped long-read kernel: one per job up to two per SIMD (each owns two carry rows of
-  // the longest stream group: ~110 KB)
-  const int n_long_waves = (int)std::min<size_t>(2048, std::max<size_t>(512, std::max(long_jobs.size(), (size_t)n_long64 * plan.groups.size())));
-  // ... and, when a read needs more wavefronts than a wide workgroup holds, the super-stripe kernel's carry rows behind them
-  const size_t striped_carry_bytes = (size_t)n_long_waves * 2 * (3 * (size_t)carry_len + 64) * sizeof(double);
-  const bool super_long = (blocks_for(plan.max_read_len, kRplF32) + kLanes - 1) / kLanes > kWideWavesMax;
-  const int64_t xsteps = super_long ? super_steps(carry_len, plan.max_read_len, kRplF32) : 0;   // (fp32 and fp64 both run the long reads at 8 rows per lane)
-  static_assert(kRplF32 == kRplF64Wide, "one array depth for the long reads of both precisions");
-  unsigned char* xcarry = nullptr;
-  if (n_long_main > 0 || n_long64 > 0) {
-    if ((rc = c->carry.reserve(striped_carry_bytes + (size_t)super_blocks_max<float>() * 2 * (size_t)xsteps * 32))) return rc;
-    if (super_long) xcarry = c->carry.as<unsigned char>() + striped_carry_bytes;
-  }
-  st.n_long_pairs = (int32_t)std::min<int64_t>((int64_t)n_long_main * n_haps, 0x7fffffff);
-  st.n_chunks = plan.n_chunks;
-  st.n_hap_groups = (int)plan.groups.size();
-  st.rows_per_lane = rpl_main;
-  st.lane_fill = plan.n_chunks ? (float)((double)plan.useful_rows / ((double)plan.n_chunks * 64 * rpl_main)) : 0.f;
-  st.cells = (int64_t)rl * (int64_t)hl;
-
-  if (ev) HIP_TRY(hipEventRecord(c->ev[1], s));
-  if (use_double) {
-    FwdArgs<double> a{};
-    fill_common(a);
-    a.tab = c->dt64;
-    a.y0 = reinterpret_cast<const double*>(dp + L.y0_64);
-    a.raw = c->raw64.as<double>();
-    if (n_main_blocks > 0) launch_stream<double, kRplF64Jobs>(a, fma, n_main_blocks, s);
-    if (n_long_main > 0) {
-      FwdArgs<double> la = a;
-      la.chunk_lanes = reinterpret_cast<const LaneSlot*>(dp + L.long_lanes);
-      la.jobs = reinterpret_cast<const FwdJob*>(dp + L.long_jobs);
-      la.job_count = reinterpret_cast<const int32_t*>(dp + L.long_count);
-      la.job_next = c->counters.as<int32_t>() + 7;
-      launch_long_jobs<double, kRplF64Wide, kRplF64>(la, fma, n_long_waves, plan.max_read_len, c->carry.as<double>(), carry_len, s, xcarry, xsteps, c->counters.as<int32_t>() + 12);
-    }
-    if (ev) HIP_TRY(hipEventRecord(c->ev[2], s));
-    hipLaunchKernelGGL(finalize64_kernel, dim3((unsigned)((n_pairs + 255) / 256)), dim3(256), 0, s, fa, 1);
-    if (ev) { HIP_TRY(hipEventRecord(c->ev[3], s)); HIP_TRY(hipEventRecord(c->ev[4], s)); }
-    HIP_TRY(hipEventRecord(c->policy_done, s));  // (host path: "results are final from here")
-  } else {
-    FwdArgs<float> a{};
-    fill_common(a);
+// The main pass in precision T (fp32 of the policy mode, fp64 of the all-fp64 mode).
+template <typename T>
+FwdArgs<T> fwd_args(const DevCtx* c, const CallPlan& P, const StagedCall& S) {
+  constexpr bool is_f32 = std::is_same<T, float>::value;
+  const PlanLayout& L = P.L;
+  unsigned char* dp = S.dp;
+  FwdArgs<T> a{};
+  a.b = S.b;
+  a.stream = S.stream_grouped;
+  a.hap_len = reinterpret_cast<const int32_t*>(dp + L.hap_len);
+  a.hap_pos = reinterpret_cast<const int32_t*>(dp + L.hap_pos);
+  a.hap_orig = reinterpret_cast<const int32_t*>(dp + L.hap_orig);
+  a.hap_has_n = S.hap_has_n;
+  a.groups = reinterpret_cast<const HapGroup*>(dp + L.groups);
+  a.n_groups = (int)c->plan.groups.size();
+  a.chunk_lanes = c->lanes_main.as<LaneSlot>();
+  a.n_chunks = c->plan.n_chunks;
+  a.chunk_stride = P.chunk_stride;
+  a.jobs = c->jobs.as<FwdJob>();
+  a.job_count = c->counters.as<int32_t>() + 2;
+  a.job_next = c->counters.as<int32_t>() + 3;
+  // the fp32 programs fetch a separator lane's priors from beyond the LDS allocation: only where that reads 0 (dev_init)
+  a.asm_general = (c->asm_general && (!is_f32 || c->lds_oob_zero)) ? 1 : 0;
+  if constexpr (is_f32) {
     a.tab = c->dt32;
     a.y0 = reinterpret_cast<const float*>(dp + L.y0_32);
     a.raw = c->raw32.as<float>();
-    // (the small-call path applies the policy per pair and writes the words itself)
-    const bool fold_packed = finalize_mode == kModePacked && !per_pair_call;
-    a.packed_out = fold_packed ? reinterpret_cast<uint64_t*>(out_dev) : nullptr;
-    if (deferred_launch) {
-      defer->call.f = a;
-      defer->call.rpl_main = rpl_main;
-      defer->call.main_blocks = n_main_blocks;
-      defer->call.fused = fused_call ? 1 : 0;
-    } else if (n_main_blocks > 0 && !fused_call) {
-      launch_main_f32(a, rpl_main, fma, n_main_blocks, s);
-    }
-    if (n_long_main > 0) {
-      FwdArgs<float> la = a;
-      la.chunk_lanes = reinterpret_cast<const LaneSlot*>(dp + L.long_lanes);
-      la.jobs = reinterpret_cast<const FwdJob*>(dp + L.long_jobs);
-      la.job_count = reinterpret_cast<const int32_t*>(dp + L.long_count);
-      la.job_next = c->counters.as<int32_t>() + 7;
-      if (rpl_main <= 4) launch_long<float, 4>(la, fma, n_long_waves, c->carry.as<float>(), carry_len, s);  // (2 is only chosen without long reads)
-      else               launch_long_jobs<float, kRplF32, kRplF32>(la, fma, n_long_waves, plan.max_read_len, c->carry.as<float>(), carry_len, s, xcarry, xsteps, c->counters.as<int32_t>() + 12);
-    }
-    if (ev) HIP_TRY(hipEventRecord(c->ev[2], s));
-
-    // fp64 arguments shared by the two ways of recomputing (the flat stream: a job may run across stream groups)
-    FwdArgs<double> d{};
-    fill_common(d);
-    d.tab = c->dt64;
-    d.y0 = reinterpret_cast<const double*>(dp + L.y0_64);
-    d.raw = c->raw64.as<double>();
-    d.stream = stream_flat;
-    d.hap_pos = reinterpret_cast<const int32_t*>(dp + L.hap_pos_flat);
-    // (the planned fp64 pass leaves the packed words of the recomputed pairs to finalize64_kernel: its jobs run as whole-job
-    //  asm programs that store the raw sums only)
-    d.packed_out = nullptr;
-    d.packed_only_flagged = c->used64.as<uint8_t>();
-    int32_t* cnts = c->counters.as<int32_t>();
-    // Small calls (one GATK region): policy + fp64 recomputation + finalisation of one pair per wavefront in ONE launch
-    // (pairhmm_pair_policy_kernel); rows per lane by the longest read.
-    const bool per_pair = per_pair_call;
-    if (per_pair) {
-      PairPolicyArgs q;
-      q.raw32 = c->raw32.as<float>(); q.out = out_dev; q.used64 = c->used64.as<uint8_t>(); q.count = cnts;
-      q.hap_sidx = reinterpret_cast<const int32_t*>(dp + L.hap_sidx);
-      q.mode = finalize_mode;
-      q.log10_init_f = fa.log10_init_f; q.log10_init32_as_f64 = fa.log10_init32_as_f64; q.log10_init_d = fa.log10_init_d;
-      const int rows = plan.max_read_len <= 2 * kLanes - 1 ? 2 : plan.max_read_len <= 4 * kLanes - 1 ? 4 : kRplF64;
-      if (deferred_launch) {
-        SmallCall& k = defer->call;
-        k.d = d; k.q = q; k.rows = rows; k.n_pairs = (int32_t)n_pairs; k.fma = fma; k.speculate = c->speculate_fp64;
-        memcpy(hs + L.desc, &k, sizeof k);  // nothing has been launched yet: the block is still ours to write
-        defer->desc_pinned = reinterpret_cast<const SmallCall*>(hs_dev + L.desc);
-        defer->desc_dev = reinterpret_cast<const SmallCall*>(dp + L.desc);
-        defer->filled = true;
-        c->last_pairs = n_pairs;
-        c->last_stream = s;
-        c->have_last = true;
-        st.n_fallback = -1;
-        return GKLHIP_OK;
-      }
-      if (ev) HIP_TRY(hipEventRecord(c->ev[3], s));
-      if (fused_call) {
-        launch_pair_fused(a, d, q, rows, fma, n_pairs, s, c->speculate_fp64 && g_host_calls_in_flight.load(std::memory_order_relaxed) <= 1);
-      } else if (n_pairs > kTwoStepFrom) {
-        if ((rc = c->fail_order.reserve((size_t)n_pairs * 4))) return rc;
-        launch_pair_policy_two_step(d, q, rows, fma, n_pairs, c->fail_order.as<int32_t>(), s);
-      } else {
-        launch_pair_policy(d, q, rows, fma, n_pairs, s);
-      }
-      if (ev) HIP_TRY(hipEventRecord(c->ev[4], s));
-      HIP_TRY(hipEventRecord(c->policy_done, s));
-    } else {
-    // ---- precision policy + device-side planning of the fp64 recomputation (three launches, no host round trip) ----
-    const size_t jobs_per_chunk = (size_t)n_haps;  // a job holds at least one haplotype and the jobs of a chunk do not overlap
-    const size_t max_jobs = (size_t)n_reads * jobs_per_chunk;
-    if ((rc = c->fail_order.reserve(((size_t)n_reads + (size_t)n_long64) * 4))) return rc;
-    if ((rc = c->lanes2.reserve((size_t)n_reads * kLanes * sizeof(LaneSlot)))) return rc;
-    if ((rc = c->jobs.reserve(2 * max_jobs * sizeof(FwdJob)))) return rc;  // as built + sorted by length
-    if (n_long64 > 0 && (rc = c->jobs_long.reserve((size_t)n_long64 * jobs_per_chunk * sizeof(FwdJob)))) return rc;
-    const LaneSlot* pl = reinterpret_cast<const LaneSlot*>(dp + L.long_lanes);
-    {
-      PlanArgs pa;
-      pa.fa = fa;
-      pa.n_reads = n_reads; pa.n_haps = n_haps; pa.n_pairs_i = (int32_t)n_pairs;
-      pa.read_off = b.read_off;
-      pa.rpl = kRplF64Jobs; pa.max_len = kLanes * kRplF64Jobs - 1;
-      pa.cnts = cnts;
-      pa.hist = c->fail_hist.as<int32_t>();
-      pa.pos = pa.hist + (n_haps + 2);
-      pa.order = c->fail_order.as<int32_t>();
-      pa.lanes2 = c->lanes2.as<LaneSlot>();
-      pa.hap_orig = reinterpret_cast<const int32_t*>(dp + L.hap_orig);
-      pa.hap_group = reinterpret_cast<const int32_t*>(dp + L.hap_group);
-      pa.hap_pos = reinterpret_cast<const int32_t*>(dp + L.hap_pos_flat);
-      pa.hap_len = reinterpret_cast<const int32_t*>(dp + L.hap_len);
-      pa.jobs = c->jobs.as<FwdJob>();
-      pa.sorted = c->jobs.as<FwdJob>() + max_jobs;
-      pa.long_lanes = pl + (size_t)n_long_main * kLanes;
-      pa.n_long = n_long64;
-      pa.jobs_long = c->jobs_long.as<FwdJob>();
-      pa.long_chunk_jobs = c->fail_order.as<int32_t>() + n_reads;
-      pa.total_cols = (int32_t)std::min<int64_t>((int64_t)hl + n_haps, 0x7fffffff);
-      const int wanted_env = g_env.fb_wanted_jobs;
-      // (a shard of the batch wants fewer, longer jobs: 4096 for an eighth, measured on the 1250 x 128 shard)
-      pa.wanted_jobs = wanted_env > 0 ? wanted_env : (int)std::min<int64_t>(kFallbackWantedJobs, std::max<int64_t>(4096, n_pairs / 100));
-      pa.min_job_cols = 256;
-      pa.packed_by_kernels = fold_packed ? 1 : 0;
-      // Three stream-ordered launches (pairhmm_aux_kernels.h): no block waits for another, so nothing limits how many
-      // of these are in flight per device or process.  The policy takes a block per 4096 pairs (up to one per CU), the
-      // packing a wavefront per window of affected reads, the run detection a wavefront per chunk (grid-stride).
-      const int blocks_env = g_env.plan_blocks;
-      const int policy_grid = std::max(1, blocks_env > 0 ? blocks_env : (int)std::min<int64_t>(c->n_cus, std::max<int64_t>(16, n_pairs / 4096)));
-      const int64_t max_windows = ((int64_t)n_reads + kPackWindow - 1) / kPackWindow;
-      const int pack_grid = (int)std::max<int64_t>(1, std::min<int64_t>(kPlanBlocks, (max_windows + kPlanBlock / 64 - 1) / (kPlanBlock / 64)));
-      const int jobs_grid = std::max(1, std::min(c->n_cus, blocks_env > 0 ? blocks_env : (int)std::min<int64_t>(kPlanBlocks, std::max<int64_t>(16, n_pairs / 8192))));
-      hipLaunchKernelGGL(plan_policy_kernel, dim3((unsigned)policy_grid), dim3(kPlanBlock), 0, s, pa);
-      // The policy's flags and the kept pairs' words are final here: the log10 of the kept pairs (side stream below; the
-      // host's early pass in host-buffer calls) starts now and overlaps the two small planning launches -- behind them it
-      // would queue up against the fp64 pass, whose persistent wavefronts leave it no registers until they drain.
-      HIP_TRY(hipEventRecord(c->policy_done, s));
-      hipLaunchKernelGGL(plan_pack_kernel, dim3((unsigned)pack_grid), dim3(kPlanBlock), 0, s, pa);
-      hipLaunchKernelGGL(plan_jobs_kernel, dim3((unsigned)jobs_grid), dim3(kPlanBlock), 0, s, pa);
-    }
-    const bool side_finalize = finalize_mode == GKLHIP_FINALIZE_DEVICE_F64 || finalize_mode == GKLHIP_FINALIZE_DEVICE_REF32;
-    if (side_finalize) {
-      if ((rc = aux_streams(c))) return rc;
-      HIP_TRY(hipStreamWaitEvent(c->copy_stream, c->policy_done, 0));
-      hipLaunchKernelGGL(finalize32_kernel, dim3((unsigned)((n_pairs + 255) / 256)), dim3(256), 0, c->copy_stream, fa);
-      HIP_TRY(hipEventRecord(c->early_copy_done, c->copy_stream));
-    }
-    // ---- fp64 recomputation of the underflowed pairs: persistent wavefronts stream the job list -- same WaveJob
-    // template as the main pass, T = double (no jobs: the kernel's wavefronts leave at once) ----
-    d.chunk_lanes = c->lanes2.as<LaneSlot>();
-    d.n_chunks = n_reads;  // upper bound; the job list only names packed chunks
-    d.jobs = c->jobs.as<FwdJob>() + max_jobs;
-    if (ev) HIP_TRY(hipEventRecord(c->ev[3], s));
-    launch_jobs<double, kRplF64Jobs>(d, fma, (int)std::min<int64_t>(n_pairs, (int64_t)c->n_cus * 16), s);
-    if (n_long64 > 0) {
-      // reads too long for a chunk: one pseudo-chunk each, same run detection, striped kernel
-      FwdArgs<double> ld = d;
-      ld.chunk_lanes = pl + (size_t)n_long_main * kLanes;
-      ld.jobs = c->jobs_long.as<FwdJob>();
-      ld.job_count = cnts + 8;
-      ld.job_next = cnts + 9;
-      launch_long_jobs<double, kRplF64Wide, kRplF64>(ld, fma, n_long_waves, plan.max_read_len, c->carry.as<double>(), carry_len, s, xcarry, xsteps, cnts + 13);
-    }
-    if (ev) HIP_TRY(hipEventRecord(c->ev[4], s));
-    // (log10 of the recomputed pairs / host-buffer calls: their packed words)
-    hipLaunchKernelGGL(finalize64_kernel, dim3((unsigned)((n_pairs + 255) / 256)), dim3(256), 0, s, fa, 0);
-    if (side_finalize) HIP_TRY(hipStreamWaitEvent(s, c->early_copy_done, 0));  // join the side stream
-    }  // !per_pair
+    // host-exact packed words straight from the forward kernels (the per-pair path applies the policy per pair and
+    // writes the words itself)
+    a.packed_out = (P.finalize_mode == kModePacked && !P.per_pair) ? reinterpret_cast<uint64_t*>(S.out) : nullptr;
+  } else {
+    a.tab = c->dt64;
+    a.y0 = reinterpret_cast<const double*>(dp + L.y0_64);
+    a.raw = c->raw64.as<double>();
   }
+  return a;
+}
+// ... its long reads: the pseudo-chunks and jobs that came with the plan block
+template <typename T>
+FwdArgs<T> long_main_args(const DevCtx* c, const CallPlan& P, const StagedCall& S, const FwdArgs<T>& a) {
+  FwdArgs<T> la = a;
+  la.chunk_lanes = reinterpret_cast<const LaneSlot*>(S.dp + P.L.long_lanes);
+  la.jobs = reinterpret_cast<const FwdJob*>(S.dp + P.L.long_jobs);
+  la.job_count = reinterpret_cast<const int32_t*>(S.dp + P.L.long_count);
+  la.job_next = c->counters.as<int32_t>() + 7;
+  return la;
+}
+// fp64 arguments shared by the two ways of recomputing (the flat stream: a job may run across stream groups)
+FwdArgs<double> recompute_args(const DevCtx* c, const CallPlan& P, const StagedCall& S) {
+  FwdArgs<double> d = fwd_args<double>(c, P, S);
+  d.stream = S.stream_flat;
+  d.hap_pos = reinterpret_cast<const int32_t*>(S.dp + P.L.hap_pos_flat);
+  // (the planned fp64 pass leaves the packed words of the recomputed pairs to finalize64_kernel: its jobs run as whole-job
+  //  asm programs that store the raw sums only)
+  d.packed_out = nullptr;
+  d.packed_only_flagged = c->used64.as<uint8_t>();
+  return d;
+}
+FinalizeArgs finalize_args(const DevCtx* c, const CallPlan& P, const StagedCall& S) {
+  FinalizeArgs fa;
+  fa.raw32 = c->raw32.as<float>(); fa.raw64 = c->raw64.as<double>(); fa.out = S.out;
+  fa.used64 = c->used64.as<uint8_t>();
+  fa.count = c->counters.as<int32_t>(); fa.n = P.n_pairs; fa.mode = P.finalize_mode;
+  fa.read_fail = c->read_fail.as<int32_t>(); fa.n_haps = P.n_haps;
+  fa.log10_init_f = host_tables_f32().log10_initial; fa.log10_init32_as_f64 = std::log10(std::ldexp(1.0, 120)); fa.log10_init_d = host_tables_f64().log10_initial;
+  return fa;
+}
+PairPolicyArgs pair_policy_args(const DevCtx* c, const CallPlan& P, const StagedCall& S) {
+  PairPolicyArgs q;
+  q.raw32 = c->raw32.as<float>(); q.out = S.out; q.used64 = c->used64.as<uint8_t>(); q.count = c->counters.as<int32_t>();
+  q.hap_sidx = reinterpret_cast<const int32_t*>(S.dp + P.L.hap_sidx);
+  q.mode = P.finalize_mode;
+  q.log10_init_f = host_tables_f32().log10_initial; q.log10_init32_as_f64 = std::log10(std::ldexp(1.0, 120)); q.log10_init_d = host_tables_f64().log10_initial;
+  return q;
+}
+// precision policy + device-side planning of the fp64 recomputation (buffers: launch_planned_fp64 reserves them)
+size_t planned_max_jobs(const CallPlan& P) { return (size_t)P.n_reads * (size_t)P.n_haps; }  // a job holds at least one haplotype and the jobs of a chunk do not overlap
+PlanArgs plan_args(const DevCtx* c, const CallPlan& P, const StagedCall& S) {
+  const PlanLayout& L = P.L;
+  unsigned char* dp = S.dp;
+  const int n_reads = P.n_reads, n_haps = P.n_haps;
+  PlanArgs pa;
+  pa.fa = finalize_args(c, P, S);
+  pa.n_reads = n_reads; pa.n_haps = n_haps; pa.n_pairs_i = (int32_t)P.n_pairs;
+  pa.read_off = S.b.read_off;
+  pa.rpl = kRplF64Jobs; pa.max_len = kLanes * kRplF64Jobs - 1;
+  pa.cnts = c->counters.as<int32_t>();
+  pa.hist = c->fail_hist.as<int32_t>();
+  pa.pos = pa.hist + (n_haps + 2);
+  pa.order = c->fail_order.as<int32_t>();
+  pa.lanes2 = c->lanes2.as<LaneSlot>();
+  pa.hap_orig = reinterpret_cast<const int32_t*>(dp + L.hap_orig);
+  pa.hap_group = reinterpret_cast<const int32_t*>(dp + L.hap_group);
+  pa.hap_pos = reinterpret_cast<const int32_t*>(dp + L.hap_pos_flat);
+  pa.hap_len = reinterpret_cast<const int32_t*>(dp + L.hap_len);
+  pa.jobs = c->jobs.as<FwdJob>();
+  pa.sorted = c->jobs.as<FwdJob>() + planned_max_jobs(P);
+  pa.long_lanes = reinterpret_cast<const LaneSlot*>(dp + L.long_lanes) + (size_t)P.n_long_main * kLanes;
+  pa.n_long = P.n_long64;
+  pa.jobs_long = c->jobs_long.as<FwdJob>();
+  pa.long_chunk_jobs = c->fail_order.as<int32_t>() + n_reads;
+  pa.total_cols = (int32_t)std::min<int64_t>((int64_t)P.hl + n_haps, 0x7fffffff);
+  // (a shard of the batch wants fewer, longer jobs: 4096 for an eighth, measured on the 1250 x 128 shard)
+  pa.wanted_jobs = g_env.fb_wanted_jobs > 0 ? g_env.fb_wanted_jobs : (int)std::min<int64_t>(kFallbackWantedJobs, std::max<int64_t>(4096, P.n_pairs / 100));
+  pa.min_job_cols = 256;
+  pa.packed_by_kernels = (P.finalize_mode == kModePacked && !P.per_pair) ? 1 : 0;
+  return pa;
+}
+
+// ---- step 4: the launches on S.s, one function per shape, each with its event records; no host synchronisation
+// before finish_call.  In the policy mode a big call is 7 launches (prep, fp32 forward, the three launches of policy +
+// planning of the fp64 pass, fp64 forward over the job list, log10 / packed words of the recomputed pairs; + the log10
+// of the kept pairs on a side stream in the device finalisation modes), a call of up to 65 536 pairs 3-4 (prep, fp32
+// forward, per-pair policy in one or two launches), one of up to 2048 pairs 2 (prep, the fused per-pair kernel). ----
+int launch_prep(DevCtx* c, const CallPlan& P, const StagedCall& S) {
+  const bool ev = c->cfg.record_events != 0;
+  if (ev) {
+    const bool deferred = c->cfg.record_events == 2;
+    c->ev = c->ev_ring[deferred ? c->calls % DevCtx::kEventRing : 0];
+    c->ring_double[deferred ? c->calls % DevCtx::kEventRing : 0] = P.use_double;
+    c->calls++;
+    HIP_TRY(hipEventRecord(c->ev[0], S.s));
+  }
+  const PrepArgs pa = prep_args(c, P, S);
+  hipLaunchKernelGGL(prep_kernel, dim3((unsigned)prep_grid(pa, P)), dim3(kPrepBlock), 0, S.s, pa);
+  if (P.pull) HIP_TRY(hipEventRecord(c->stage_free_slot[S.slot], S.s));
+  return GKLHIP_OK;
+}
+// the carry rows of the long-read kernels (a call without long reads reserves none)
+int reserve_carry(DevCtx* c, const CallPlan& P, StagedCall* S) {
+  if (P.n_long_main == 0 && P.n_long64 == 0) return GKLHIP_OK;
+  if (int rc = c->carry.reserve(P.striped_carry_bytes + (size_t)super_blocks_max<float>() * 2 * (size_t)P.xsteps * 32)) return rc;
+  if (P.xsteps > 0) S->xcarry = c->carry.as<unsigned char>() + P.striped_carry_bytes;
+  return GKLHIP_OK;
+}
+int launch_all_double(DevCtx* c, const CallPlan& P, const StagedCall& S) {
+  const bool ev = c->cfg.record_events != 0;
+  hipStream_t s = S.s;
+  const FwdArgs<double> a = fwd_args<double>(c, P, S);
+  if (P.n_main_blocks > 0) launch_stream<double, kRplF64Jobs>(a, P.fma, P.n_main_blocks, s);
+  if (P.n_long_main > 0)
+    launch_long_jobs<double, kRplF64Wide, kRplF64>(long_main_args(c, P, S, a), P.fma, P.n_long_waves, c->plan.max_read_len, c->carry.as<double>(), P.carry_len, s,
+                                                   S.xcarry, P.xsteps, c->counters.as<int32_t>() + 12);
+  if (ev) HIP_TRY(hipEventRecord(c->ev[2], s));
+  hipLaunchKernelGGL(finalize64_kernel, dim3((unsigned)((P.n_pairs + 255) / 256)), dim3(256), 0, s, finalize_args(c, P, S), 1);
+  if (ev) { HIP_TRY(hipEventRecord(c->ev[3], s)); HIP_TRY(hipEventRecord(c->ev[4], s)); }
+  HIP_TRY(hipEventRecord(c->policy_done, s));  // (host path: "results are final from here")
+  return GKLHIP_OK;
+}
+// the fp32 main pass (a fused call's runs inside its per-pair kernel) and its long reads
+int launch_main_pass_f32(DevCtx* c, const CallPlan& P, const StagedCall& S, const FwdArgs<float>& a) {
+  hipStream_t s = S.s;
+  if (P.n_main_blocks > 0 && !P.fused) launch_main_f32(a, P.rpl_main, P.fma, P.n_main_blocks, s);
+  if (P.n_long_main > 0) {
+    const FwdArgs<float> la = long_main_args(c, P, S, a);
+    if (P.rpl_main <= 4) launch_long<float, 4>(la, P.fma, P.n_long_waves, c->carry.as<float>(), P.carry_len, s);  // (2 is only chosen without long reads)
+    else                 launch_long_jobs<float, kRplF32, kRplF32>(la, P.fma, P.n_long_waves, c->plan.max_read_len, c->carry.as<float>(), P.carry_len, s, S.xcarry, P.xsteps, c->counters.as<int32_t>() + 12);
+  }
+  if (c->cfg.record_events != 0) HIP_TRY(hipEventRecord(c->ev[2], s));
+  return GKLHIP_OK;
+}
+// Small calls (one GATK region): policy + fp64 recomputation + finalisation of one pair per wavefront -- fused with the
+// fp32 recurrence, in ONE launch (pairhmm_pair_policy_kernel), or from kTwoStepFrom pairs in two.
+int launch_per_pair(DevCtx* c, const CallPlan& P, const StagedCall& S, const FwdArgs<float>& a) {
+  const bool ev = c->cfg.record_events != 0;
+  hipStream_t s = S.s;
+  const FwdArgs<double> d = recompute_args(c, P, S);
+  const PairPolicyArgs q = pair_policy_args(c, P, S);
+  if (ev) HIP_TRY(hipEventRecord(c->ev[3], s));
+  if (P.fused) {
+    launch_pair_fused(a, d, q, P.rows, P.fma, P.n_pairs, s, c->speculate_fp64 && g_host_calls_in_flight.load(std::memory_order_relaxed) <= 1);
+  } else if (P.n_pairs > kTwoStepFrom) {
+    if (int rc = c->fail_order.reserve((size_t)P.n_pairs * 4)) return rc;
+    launch_pair_policy_two_step(d, q, P.rows, P.fma, P.n_pairs, c->fail_order.as<int32_t>(), s);
+  } else {
+    launch_pair_policy(d, q, P.rows, P.fma, P.n_pairs, s);
+  }
+  if (ev) HIP_TRY(hipEventRecord(c->ev[4], s));
+  HIP_TRY(hipEventRecord(c->policy_done, s));
+  return GKLHIP_OK;
+}
+// Precision policy + device-side planning of the fp64 recomputation (three launches, no host round trip), the fp64
+// recomputation of the underflowed pairs and their finalisation.
+int launch_planned_fp64(DevCtx* c, const CallPlan& P, const StagedCall& S) {
+  const bool ev = c->cfg.record_events != 0;
+  hipStream_t s = S.s;
+  const int n_reads = P.n_reads;
+  const int64_t n_pairs = P.n_pairs;
+  const size_t max_jobs = planned_max_jobs(P);
+  int rc;
+  if ((rc = c->fail_order.reserve(((size_t)n_reads + (size_t)P.n_long64) * 4))) return rc;
+  if ((rc = c->lanes2.reserve((size_t)n_reads * kLanes * sizeof(LaneSlot)))) return rc;
+  if ((rc = c->jobs.reserve(2 * max_jobs * sizeof(FwdJob)))) return rc;  // as built + sorted by length
+  if (P.n_long64 > 0 && (rc = c->jobs_long.reserve((size_t)P.n_long64 * (size_t)P.n_haps * sizeof(FwdJob)))) return rc;
+  const PlanArgs pa = plan_args(c, P, S);
+  // Three stream-ordered launches (pairhmm_aux_kernels.h): no block waits for another, so nothing limits how many
+  // of these are in flight per device or process.  The policy takes a block per 4096 pairs (up to one per CU), the
+  // packing a wavefront per window of affected reads, the run detection a wavefront per chunk (grid-stride).
+  const int blocks_env = g_env.plan_blocks;
+  const int policy_grid = std::max(1, blocks_env > 0 ? blocks_env : (int)std::min<int64_t>(c->n_cus, std::max<int64_t>(16, n_pairs / 4096)));
+  const int64_t max_windows = ((int64_t)n_reads + kPackWindow - 1) / kPackWindow;
+  const int pack_grid = (int)std::max<int64_t>(1, std::min<int64_t>(kPlanBlocks, (max_windows + kPlanBlock / 64 - 1) / (kPlanBlock / 64)));
+  const int jobs_grid = std::max(1, std::min(c->n_cus, blocks_env > 0 ? blocks_env : (int)std::min<int64_t>(kPlanBlocks, std::max<int64_t>(16, n_pairs / 8192))));
+  hipLaunchKernelGGL(plan_policy_kernel, dim3((unsigned)policy_grid), dim3(kPlanBlock), 0, s, pa);
+  // The policy's flags and the kept pairs' words are final here: the log10 of the kept pairs (side stream below; the
+  // host's early pass in host-buffer calls) starts now and overlaps the two small planning launches -- behind them it
+  // would queue up against the fp64 pass, whose persistent wavefronts leave it no registers until they drain.
+  HIP_TRY(hipEventRecord(c->policy_done, s));
+  hipLaunchKernelGGL(plan_pack_kernel, dim3((unsigned)pack_grid), dim3(kPlanBlock), 0, s, pa);
+  hipLaunchKernelGGL(plan_jobs_kernel, dim3((unsigned)jobs_grid), dim3(kPlanBlock), 0, s, pa);
+  const bool side_finalize = finalizes_on_device(P.finalize_mode);
+  if (side_finalize) {
+    if ((rc = aux_streams(c))) return rc;
+    HIP_TRY(hipStreamWaitEvent(c->copy_stream, c->policy_done, 0));
+    hipLaunchKernelGGL(finalize32_kernel, dim3((unsigned)((n_pairs + 255) / 256)), dim3(256), 0, c->copy_stream, pa.fa);
+    HIP_TRY(hipEventRecord(c->early_copy_done, c->copy_stream));
+  }
+  // ---- fp64 recomputation of the underflowed pairs: persistent wavefronts stream the job list -- same WaveJob
+  // template as the main pass, T = double (no jobs: the kernel's wavefronts leave at once) ----
+  FwdArgs<double> d = recompute_args(c, P, S);
+  d.chunk_lanes = c->lanes2.as<LaneSlot>();
+  d.n_chunks = n_reads;  // upper bound; the job list only names packed chunks
+  d.jobs = c->jobs.as<FwdJob>() + max_jobs;
+  if (ev) HIP_TRY(hipEventRecord(c->ev[3], s));
+  launch_jobs<double, kRplF64Jobs>(d, P.fma, (int)std::min<int64_t>(n_pairs, (int64_t)c->n_cus * 16), s);
+  if (P.n_long64 > 0) {
+    // reads too long for a chunk: one pseudo-chunk each, same run detection, striped kernel
+    int32_t* cnts = c->counters.as<int32_t>();
+    FwdArgs<double> ld = d;
+    ld.chunk_lanes = pa.long_lanes;
+    ld.jobs = c->jobs_long.as<FwdJob>();
+    ld.job_count = cnts + 8;
+    ld.job_next = cnts + 9;
+    launch_long_jobs<double, kRplF64Wide, kRplF64>(ld, P.fma, P.n_long_waves, c->plan.max_read_len, c->carry.as<double>(), P.carry_len, s, S.xcarry, P.xsteps, cnts + 13);
+  }
+  if (ev) HIP_TRY(hipEventRecord(c->ev[4], s));
+  // (log10 of the recomputed pairs / host-buffer calls: their packed words)
+  hipLaunchKernelGGL(finalize64_kernel, dim3((unsigned)((n_pairs + 255) / 256)), dim3(256), 0, s, pa.fa, 0);
+  if (side_finalize) HIP_TRY(hipStreamWaitEvent(s, c->early_copy_done, 0));  // join the side stream
+  return GKLHIP_OK;
+}
+// The end of a launched call: its events, and -- record_events == 1 -- the statistics read back.
+int finish_call(DevCtx* c, const CallPlan& P, const StagedCall& S) {
+  const bool ev = c->cfg.record_events != 0;
+  hipStream_t s = S.s;
+  gklhip_stats& st = c->stats;
   if (ev) HIP_TRY(hipEventRecord(c->ev[5], s));
   HIP_TRY(hipGetLastError());
 
-  HIP_TRY(hipEventRecord(c->plan_unused_slot[slot], s));
+  HIP_TRY(hipEventRecord(c->plan_unused_slot[S.slot], s));
   HIP_TRY(hipEventRecord(c->call_done, s));
   c->have_call_done = true;
-  c->last_pairs = n_pairs;
+  c->last_pairs = P.n_pairs;
   c->last_stream = s;
   c->have_last = true;
 
-  if (ev && !deferred) {
+  if (ev && c->cfg.record_events != 2) {
     HIP_TRY(hipEventSynchronize(c->ev[5]));
     float ms = 0;
     HIP_TRY(hipEventElapsedTime(&ms, c->ev[1], c->ev[2])); st.ms_fwd_main = ms;
-    HIP_TRY(hipEventElapsedTime(&ms, c->ev[3], c->ev[4])); st.ms_fwd_fallback = use_double ? 0.f : ms;
+    HIP_TRY(hipEventElapsedTime(&ms, c->ev[3], c->ev[4])); st.ms_fwd_fallback = P.use_double ? 0.f : ms;
     HIP_TRY(hipEventElapsedTime(&ms, c->ev[0], c->ev[5])); st.ms_total_device = ms;
     int32_t cnt[2] = {0, 0};
     HIP_TRY(hipMemcpyAsync(cnt, c->counters.p, 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
-    st.n_fallback = use_double ? n_pairs : cnt[0];
-    if (timing && !use_double) {
+    st.n_fallback = P.use_double ? P.n_pairs : cnt[0];
+    if (g_env.timing && !P.use_double) {
       int32_t k[32];
       HIP_TRY(hipMemcpy(k, c->counters.p, sizeof k, hipMemcpyDeviceToHost));
       fprintf(stderr, "[gklhip] policy+plan phases, each from the start of its own launch (us): hist %.1f scan %.1f scatter %.1f pack %.1f jobs %.1f sort %.1f | "
@@ -828,9 +895,56 @@ int run_device(DevCtx* c, const gklhip_batch* db, double* out_dev, int finalize_
               k[4], k[5], k[2], k[22] * 0.01, k[23] * 0.01, k[24] * 0.01, k[25] * 0.01, k[26] * 0.01);
     }
   } else {
-    st.n_fallback = use_double ? n_pairs : -1;  // unknown without a sync; gklhip_get_raw fills it in
+    st.n_fallback = P.use_double ? P.n_pairs : -1;  // unknown without a sync; gklhip_get_raw fills it in
   }
   return GKLHIP_OK;
+}
+
+// ---- step 5: the deferred exit.  Nothing is launched: the call's descriptor, from the same builders, goes into the
+// staging block (still ours to write) and to the combiner. ----
+void describe_small_call(DevCtx* c, const CallPlan& P, const StagedCall& S, SmallLaunch* out) {
+  SmallCall& k = out->call;
+  k.prep = prep_args(c, P, S);
+  k.prep_grid = prep_grid(k.prep, P);
+  k.f = fwd_args<float>(c, P, S);
+  k.d = recompute_args(c, P, S);
+  k.q = pair_policy_args(c, P, S);
+  k.rpl_main = P.rpl_main; k.main_blocks = P.n_main_blocks; k.rows = P.rows; k.n_pairs = (int32_t)P.n_pairs; k.fma = P.fma;
+  k.fused = P.fused ? 1 : 0;
+  k.speculate = c->speculate_fp64;
+  memcpy(S.hs + P.L.desc, &k, sizeof k);
+  out->desc_pinned = reinterpret_cast<const SmallCall*>(S.hs_dev + P.L.desc);
+  out->desc_dev = reinterpret_cast<const SmallCall*>(S.dp + P.L.desc);
+  c->last_pairs = P.n_pairs;
+  c->last_stream = S.s;
+  c->have_last = true;
+  c->stats.n_fallback = -1;
+}
+
+// ---- step 6: the callers compose.  A planned call that does not defer: staged, launched on `s`, finished. ----
+int launch_call(DevCtx* c, const gklhip_batch* db, const CallPlan& P, double* out_dev, hipStream_t s) {
+  if (P.n_pairs == 0) return GKLHIP_OK;
+  StagedCall S;
+  int rc;
+  if ((rc = stage_call(c, db, P, out_dev, s, &S))) return rc;
+  if ((rc = launch_prep(c, P, S))) return rc;
+  if ((rc = reserve_carry(c, P, &S))) return rc;
+  if (c->cfg.record_events != 0) HIP_TRY(hipEventRecord(c->ev[1], s));
+  if (P.use_double) {
+    rc = launch_all_double(c, P, S);
+  } else {
+    const FwdArgs<float> a = fwd_args<float>(c, P, S);
+    if ((rc = launch_main_pass_f32(c, P, S, a))) return rc;
+    rc = P.per_pair ? launch_per_pair(c, P, S, a) : launch_planned_fp64(c, P, S);
+  }
+  return rc ? rc : finish_call(c, P, S);
+}
+// The whole pass of a call that is never deferred (device-resident and multi-device callers, host calls with device
+// finalisation) on stream `s`: `db` as for stage_call.
+int run_device(DevCtx* c, const gklhip_batch* db, double* out_dev, int finalize_mode, hipStream_t s, bool inline_host) {
+  CallPlan P;
+  plan_call(c, db, finalize_mode, inline_host, false, call_load(false), &P);
+  return launch_call(c, db, P, out_dev, s);
 }
 
 }  // namespace

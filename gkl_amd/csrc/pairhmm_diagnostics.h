@@ -1,7 +1,6 @@
 // Diagnostics and self-tests behind the C ABI (inside its extern "C" block): small-call counts, the issue-ceiling measurement, the RCCL
 // self-test.
-// Part of the ONE translation unit gkl_amd/csrc/pairhmm_api.hip (included there, in this order: pairhmm_ctx.h, pairhmm_device_pass.h,
-// pairhmm_ctx_lifecycle.h, pairhmm_host_call.h, pairhmm_multi_device.h, pairhmm_diagnostics.h); not a stand-alone header.
+// Part of the ONE translation unit gkl_amd/csrc/pairhmm_api.hip, which includes it in the order it needs; not a stand-alone header.
 #pragma once
 
 int gklhip_small_call_counts(int device, int64_t out[3], int reset) {

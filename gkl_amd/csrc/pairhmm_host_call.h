@@ -1,7 +1,6 @@
 // The host-buffer call of one device (dev_compute_host: H2D, device pass, reference-exact host log10), the small-call combiner that launches
 // the GATK-sized calls of several threads together, and the multi-region call that hands it whole sets (dev_compute_host_multi).
-// Part of the ONE translation unit gkl_amd/csrc/pairhmm_api.hip (included there, in this order: pairhmm_ctx.h, pairhmm_device_pass.h,
-// pairhmm_ctx_lifecycle.h, pairhmm_host_call.h, pairhmm_multi_device.h, pairhmm_diagnostics.h); not a stand-alone header.
+// Part of the ONE translation unit gkl_amd/csrc/pairhmm_api.hip, which includes it in the order it needs; not a stand-alone header.
 #pragma once
 
 namespace {
@@ -281,30 +280,24 @@ SmallCombiner* small_combiner(int device) {
   }
   return all[(size_t)device];
 }
+int64_t one_pass_min() { return g_env.finalize_min > 0 ? g_env.finalize_min : 8192; }
 int dev_compute_host_impl(DevCtx* c, const gklhip_batch* hb, double* out_host) {
   const int64_t n_pairs = (int64_t)hb->n_reads * hb->n_haps;
   HIP_TRY(hipSetDevice(c->device));
   hipStream_t s = c->stream;
   int rc;
-  const size_t rl = (size_t)hb->read_off[hb->n_reads], hl = (size_t)hb->hap_off[hb->n_haps];
-  const size_t stride = align_up(rl);
-  const size_t all_bytes = 5 * stride + align_up(hl);
-  // a GATK-sized call: the six arrays travel inside the plan block (ONE copy launch for plan + inputs)
-  const bool inline_inputs = all_bytes <= kSmallBatchBytes;
+  const bool inline_inputs = inputs_inline(hb);
   gklhip_batch db = *hb;
   if (!inline_inputs) {
     // H2D of the six byte arrays (one allocation, 256-byte aligned sub-buffers)
-    if ((rc = c->batch_dev.reserve(all_bytes))) return rc;
+    if ((rc = c->batch_dev.reserve(six_arrays_bytes(hb)))) return rc;
     unsigned char* d = c->batch_dev.as<unsigned char>();
     if (c->have_call_done && c->last_stream != s) HIP_TRY(hipStreamWaitEvent(s, c->call_done, 0));
-    const uint8_t* srcs[5] = {hb->read_bases, hb->read_quals, hb->ins_gop, hb->del_gop, hb->gcp};
-    for (int i = 0; i < 5; i++) HIP_TRY(hipMemcpyAsync(d + i * stride, srcs[i], rl, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d + 5 * stride, hb->hap_bases, hl, hipMemcpyHostToDevice, s));
-    db.read_bases = d; db.read_quals = d + stride; db.ins_gop = d + 2 * stride;
-    db.del_gop = d + 3 * stride; db.gcp = d + 4 * stride; db.hap_bases = d + 5 * stride;
+    const size_t stride = align_up((size_t)hb->read_off[hb->n_reads]);
+    if ((rc = copy_six_arrays(*hb, stride, [d, s](size_t at, const uint8_t* src, size_t n) -> int { HIP_TRY(hipMemcpyAsync(d + at, src, n, hipMemcpyHostToDevice, s)); return GKLHIP_OK; }))) return rc;
+    db = batch_at(*hb, d, stride);
   }
   const int mode = c->cfg.finalize;
-  const bool on_device = (mode == GKLHIP_FINALIZE_DEVICE_F64 || mode == GKLHIP_FINALIZE_DEVICE_REF32);
   // The kernels store their results straight into pinned host memory (posted writes over PCIe, 8 bytes per pair):
   // a copy-engine transfer behind the last kernel costs a small call ~15 us of queue hand-offs, and in a big call
   // the runtime's copy kernel for the early results slowed the fp64 pass it was meant to overlap with by a third.
@@ -315,7 +308,7 @@ int dev_compute_host_impl(DevCtx* c, const gklhip_batch* hb, double* out_host) {
     HIP_TRY(hipHostGetDevicePointer(&p, c->res_pin.p, 0));
     pin_out = static_cast<double*>(p);
   }
-  if (on_device) {
+  if (finalizes_on_device(mode)) {
     if ((rc = run_device(c, &db, pin_out, mode, s, inline_inputs))) return rc;
     HIP_TRY(hipStreamSynchronize(s));
     memcpy(out_host, c->res_pin.p, (size_t)n_pairs * 8);
@@ -327,33 +320,37 @@ int dev_compute_host_impl(DevCtx* c, const gklhip_batch* hb, double* out_host) {
   // the early pass skips every word that is not fp32-tagged, whatever it holds at that moment).
   const HostCallInFlight in_flight;
   const int threads = finalize_threads(c, in_flight.share);
-  // one-pass finalisation (calls up to kOnePassPairs): a region of 400 reads x 40 haplotypes is 16 000 log10's = 0.08 ms
-  // on one thread, a fifth of the call -- spread over the workers from 8192 pairs on (400 x 40: 0.416 -> 0.378 ms; at 4096
-  // the hand-off costs a 150 x 30 call more than it saves: 0.236 -> 0.245; tools/mid_finalize_ab.py)
-  const int64_t one_pass_min = g_env.finalize_min > 0 ? g_env.finalize_min : 8192;
   HostFinalizer fin;
   // (a context with an asynchronous device-resident call still in flight keeps the stream-ordered path)
-  SmallLaunch small;
-  const bool may_defer = small_call_defers(c, inline_inputs) && (!c->have_call_done || hipEventQuery(c->call_done) == hipSuccess);
+  const bool may_defer = deferral_offered(inline_inputs) && (!c->have_call_done || hipEventQuery(c->call_done) == hipSuccess);
   (void)hipGetLastError();  // (hipErrorNotReady of the query)
   const int64_t t_call = SmallCombiner::now_ns();
-  if ((rc = run_device(c, &db, pin_out, kModePacked, s, inline_inputs, may_defer ? &small : nullptr))) return rc;  // records policy_done
-  if (small.filled) {
+  CallPlan P;
+  plan_call(c, &db, kModePacked, inline_inputs, may_defer, call_load(may_defer), &P);
+  if (P.defers) {   // staged and described here, launched by the combiner
+    StagedCall S;
+    SmallLaunch small;
+    if ((rc = stage_call(c, &db, P, pin_out, s, &S))) return rc;
+    describe_small_call(c, P, S, &small);
     SmallCombiner* k = small_combiner(c->device);
     const int64_t t_staged = SmallCombiner::now_ns();
     if ((rc = k->run(small, s))) return rc;
     const int64_t t_done = SmallCombiner::now_ns();
-    c->stats.n_fallback = fin.all(&c->workers, c->res_pin.as<uint64_t>(), out_host, n_pairs, threads, one_pass_min);
+    c->stats.n_fallback = fin.all(&c->workers, c->res_pin.as<uint64_t>(), out_host, n_pairs, threads, one_pass_min());
     k->ns_stage.fetch_add(t_staged - t_call, std::memory_order_relaxed);
     k->ns_run.fetch_add(t_done - t_staged, std::memory_order_relaxed);
     k->ns_finalize.fetch_add(SmallCombiner::now_ns() - t_done, std::memory_order_relaxed);
     return GKLHIP_OK;
   }
+  if ((rc = launch_call(c, &db, P, pin_out, s))) return rc;  // records policy_done
   if (c->cfg.use_double || n_pairs <= kOnePassPairs) {
     // all-fp64 mode, or a GATK-sized call (the fp64 stage of a region without underflowed pairs -- the usual case --
     // is two launches that find nothing to do): one pass over the words once the last kernel is done
+    // (from 8192 pairs on spread over the workers: a region of 400 reads x 40 haplotypes is 16 000 log10's = 0.08 ms on one
+    //  thread, a fifth of the call -- 400 x 40: 0.416 -> 0.378 ms; at 4096 the hand-off costs a 150 x 30 call more than it
+    //  saves: 0.236 -> 0.245; tools/mid_finalize_ab.py)
     HIP_TRY(hipStreamSynchronize(s));
-    c->stats.n_fallback = fin.all(&c->workers, c->res_pin.as<uint64_t>(), out_host, n_pairs, threads, one_pass_min);
+    c->stats.n_fallback = fin.all(&c->workers, c->res_pin.as<uint64_t>(), out_host, n_pairs, threads, one_pass_min());
     return GKLHIP_OK;
   }
   HIP_TRY(hipEventSynchronize(c->policy_done));
@@ -402,9 +399,10 @@ struct MultiRegion {
   gklhip_stats stats;
 };
 
-// The regions that the single-call path would defer are staged on the context's lanes -- by run_device, exactly as a single
-// call stages itself --, cut into sets (multi_cut_sets) and leave set by set through the combiner's launches; each region's
-// packed words are then finalised on the host as a single call's are.  Every other region comes back marked `alone`.
+// The regions that the single-call path would defer are staged on the context's lanes -- plan_call, stage_call and
+// describe_small_call, exactly as a single call stages itself --, cut into sets (multi_cut_sets) and leave set by set through
+// the combiner's launches; each region's packed words are then finalised on the host as a single call's are.  Every other
+// region comes back marked `alone`.
 // Up to kMultiMax regions are staged first and cut afterwards; a longer list is planned twice: once to learn which regions
 // qualify (the cut needs that of the whole list), once more when the region's set is staged.
 // A failure is the region's own (`rc`, `err`), a failed set's the failure of every region in it; the return value is for
@@ -413,23 +411,19 @@ int dev_compute_host_multi(DevCtx* c, std::vector<DevCtx*>& lanes, std::vector<M
   HIP_TRY(hipSetDevice(c->device));
   const HostCallInFlight in_flight;
   const int threads = finalize_threads(c, in_flight.share);
-  const int64_t one_pass_min = g_env.finalize_min > 0 ? g_env.finalize_min : 8192;
-  const int mode = c->cfg.finalize;
-  const bool on_device = (mode == GKLHIP_FINALIZE_DEVICE_F64 || mode == GKLHIP_FINALIZE_DEVICE_REF32);
+  const bool on_device = finalizes_on_device(c->cfg.finalize);
   SmallCombiner* k = small_combiner(c->device);
   const int n = (int)R.size();
   const bool stage_first = n <= kMultiMax;
   std::vector<SmallLaunch> staged((size_t)kMultiMax);   // by lane
   std::vector<int> owner((size_t)kMultiMax, -1);        // by lane: the region whose raw sums it holds
   auto fail_region = [](MultiRegion& r, int rc) { r.rc = rc; r.err = g_err; };
-  // Plans region i on lane `li` and stages it there (probe: only asks whether it would be).  False: no set for this region
-  // (it does not qualify: r.alone; it failed: r.rc).
-  auto stage = [&](int i, int li, bool probe) {
+  // Plans region i on lane `li` and -- unless plan_only -- stages it there.  False: no set for this region (it does not
+  // qualify: r.alone; it failed: r.rc).  *fused: the kind of a region that qualifies.
+  auto stage = [&](int i, int li, bool plan_only, uint8_t* fused) {
     MultiRegion& r = R[(size_t)i];
     const gklhip_batch* hb = r.hb;
-    const size_t rl = (size_t)hb->read_off[hb->n_reads], hl = (size_t)hb->hap_off[hb->n_haps];
-    const bool inline_inputs = 5 * align_up(rl) + align_up(hl) <= kSmallBatchBytes;
-    if (on_device || !small_call_defers(c, inline_inputs)) { r.alone = true; return false; }
+    if (on_device || !deferral_offered(inputs_inline(hb))) { r.alone = true; return false; }
     while ((int)lanes.size() <= li) {   // lanes are made on first use
       DevCtx* ln = nullptr;
       const int rc = lane_init(c, &ln);
@@ -437,30 +431,28 @@ int dev_compute_host_multi(DevCtx* c, std::vector<DevCtx*>& lanes, std::vector<M
       lanes.push_back(ln);
     }
     DevCtx* ln = lanes[(size_t)li];
-    SmallLaunch& sl = staged[(size_t)li];
-    sl = SmallLaunch();
-    sl.only = true;
-    sl.probe = probe;
     int rc = GKLHIP_OK;
     void* pin_out = nullptr;
-    if (!probe) {
+    if (!plan_only) {
       if (owner[(size_t)li] >= 0) R[(size_t)owner[(size_t)li]].lane = -1;   // an earlier set's region: its raw sums go now
       owner[(size_t)li] = -1;
       rc = ln->res_pin.reserve((size_t)hb->n_reads * (size_t)hb->n_haps * 8);
       if (rc == GKLHIP_OK && hipHostGetDevicePointer(&pin_out, ln->res_pin.p, 0) != hipSuccess) { (void)hipGetLastError(); rc = fail(GKLHIP_ERR_HIP, "hipHostGetDevicePointer failed"); }
+      if (rc != GKLHIP_OK) { fail_region(r, rc); return false; }
     }
-    if (rc == GKLHIP_OK) rc = run_device(ln, hb, static_cast<double*>(pin_out), kModePacked, c->stream, true, &sl);
-    if (rc != GKLHIP_OK) { fail_region(r, rc); return false; }
-    if (!sl.qualifies) { r.alone = true; return false; }
-    if (!probe) { owner[(size_t)li] = i; r.lane = li; }
+    CallPlan P;
+    plan_call(ln, hb, kModePacked, true, true, call_load(true), &P);
+    if (!P.defers) { r.alone = true; return false; }
+    *fused = P.fused ? 1 : 0;
+    if (plan_only) return true;
+    StagedCall S;   // (the regions of a multi call are staged on lanes that have no stream of their own)
+    if ((rc = stage_call(ln, hb, P, static_cast<double*>(pin_out), c->stream, &S))) { fail_region(r, rc); return false; }
+    describe_small_call(ln, P, S, &staged[(size_t)li]);
+    owner[(size_t)li] = i; r.lane = li;
     return true;
   };
   std::vector<uint8_t> qualifies((size_t)n), kind((size_t)n);
-  for (int i = 0; i < n; i++) {
-    const int li = stage_first ? i : 0;
-    qualifies[(size_t)i] = stage(i, li, !stage_first) ? 1 : 0;
-    kind[(size_t)i] = qualifies[(size_t)i] ? (uint8_t)staged[(size_t)li].call.fused : 0;
-  }
+  for (int i = 0; i < n; i++) qualifies[(size_t)i] = stage(i, stage_first ? i : 0, !stage_first, &kind[(size_t)i]) ? 1 : 0;
   std::vector<int32_t> set_of((size_t)n);
   const int n_sets = multi_cut_sets(qualifies.data(), kind.data(), n, set_of.data());
   for (int s = 0, i = 0; s < n_sets; s++) {
@@ -468,7 +460,7 @@ int dev_compute_host_multi(DevCtx* c, std::vector<DevCtx*>& lanes, std::vector<M
     int members[kMultiMax], m = 0;
     for (; i < n && set_of[(size_t)i] <= s; i++) {
       if (set_of[(size_t)i] != s) continue;
-      if (!stage_first && !stage(i, m, false)) continue;   // (planned under another load, it no longer qualifies: alone after all)
+      if (!stage_first && !stage(i, m, false, &kind[(size_t)i])) continue;   // (planned under another load, it no longer qualifies: alone after all)
       calls[m] = &staged[(size_t)R[(size_t)i].lane];
       members[m++] = i;
     }
@@ -479,7 +471,7 @@ int dev_compute_host_multi(DevCtx* c, std::vector<DevCtx*>& lanes, std::vector<M
       DevCtx* ln = lanes[(size_t)r.lane];
       if (rc != GKLHIP_OK) { fail_region(r, rc); owner[(size_t)r.lane] = -1; r.lane = -1; continue; }
       const HostFinalizer fin;
-      ln->stats.n_fallback = fin.all(&c->workers, ln->res_pin.as<uint64_t>(), r.out, ln->stats.n_pairs, threads, one_pass_min);
+      ln->stats.n_fallback = fin.all(&c->workers, ln->res_pin.as<uint64_t>(), r.out, ln->stats.n_pairs, threads, one_pass_min());
       r.stats = ln->stats;
     }
   }

@@ -1,7 +1,6 @@
 // Several devices behind one context: per-device worker threads, the lazily loaded RCCL gather with its peer-copy fall-back, gklhip_ctx,
 // read partitioning, multi_compute_host / multi_compute_device.
-// Part of the ONE translation unit gkl_amd/csrc/pairhmm_api.hip (included there, in this order: pairhmm_ctx.h, pairhmm_device_pass.h,
-// pairhmm_ctx_lifecycle.h, pairhmm_host_call.h, pairhmm_multi_device.h, pairhmm_diagnostics.h); not a stand-alone header.
+// Part of the ONE translation unit gkl_amd/csrc/pairhmm_api.hip, which includes it in the order it needs; not a stand-alone header.
 #pragma once
 
 namespace {
@@ -311,7 +310,6 @@ int multi_compute_device(gklhip_ctx* c, int set, const gklhip_batch* db, double*
   HIP_TRY(hipSetDevice(root->device));
   HIP_TRY(hipEventRecord(inputs_ready, s));
   const int n_haps = db->n_haps;
-  const size_t hl = (size_t)db->hap_off[n_haps];
   const std::vector<DevCtx*>* dp = &devs;
   const std::vector<hipEvent_t>* sdp = &shard_done;
   int rc = for_each_shard(c, n, [=](int d) -> int {
@@ -320,19 +318,15 @@ int multi_compute_device(gklhip_ctx* c, int set, const gklhip_batch* db, double*
     if (d == 0) return run_device(dc, &v, out_dev, mode, s, false);
     HIP_TRY(hipSetDevice(dc->device));
     hipStream_t sd = dc->stream;
-    const size_t rl = (size_t)v.read_off[v.n_reads], stride = align_up(rl);
+    const size_t stride = align_up((size_t)v.read_off[v.n_reads]);
     int r;
-    if ((r = dc->batch_dev.reserve(5 * stride + align_up(hl)))) return r;
+    if ((r = dc->batch_dev.reserve(six_arrays_bytes(&v)))) return r;
     if ((r = dc->out_dev.reserve((size_t)v.n_reads * n_haps * 8))) return r;
     unsigned char* dst = dc->batch_dev.as<unsigned char>();
     HIP_TRY(hipStreamWaitEvent(sd, inputs_ready, 0));
-    const uint8_t* srcs[5] = {v.read_bases, v.read_quals, v.ins_gop, v.del_gop, v.gcp};
-    for (int i = 0; i < 5; i++)
-      HIP_TRY(hipMemcpyPeerAsync(dst + i * stride, dc->device, srcs[i], root->device, rl, sd));
-    HIP_TRY(hipMemcpyPeerAsync(dst + 5 * stride, dc->device, v.hap_bases, root->device, hl, sd));
-    gklhip_batch lv = v;
-    lv.read_bases = dst; lv.read_quals = dst + stride; lv.ins_gop = dst + 2 * stride;
-    lv.del_gop = dst + 3 * stride; lv.gcp = dst + 4 * stride; lv.hap_bases = dst + 5 * stride;
+    const int from = root->device, to = dc->device;
+    if ((r = copy_six_arrays(v, stride, [=](size_t at, const uint8_t* src, size_t bytes) -> int { HIP_TRY(hipMemcpyPeerAsync(dst + at, to, src, from, bytes, sd)); return GKLHIP_OK; }))) return r;
+    const gklhip_batch lv = batch_at(v, dst, stride);
     if ((r = run_device(dc, &lv, dc->out_dev.as<double>(), mode, sd, false))) return r;
     if (!use_rccl) {
       HIP_TRY(hipMemcpyPeerAsync(out_dev + (int64_t)c->bounds[(size_t)d] * n_haps, root->device, dc->out_dev.p, dc->device,
