@@ -104,7 +104,7 @@ __global__ __launch_bounds__(256) void pull_words_kernel(const uint32_t* src, ui
 // ---- several small host-buffer calls in ONE set of launches (pairhmm_api.hip: SmallCombiner) ----
 // The device executes the kernels of about four queues at a time (tools/ubench_launch.hip), so sixteen callers with a
 // GATK-sized region each get no more through than four.  When calls arrive while others are in flight, their three
-// launches (prep, fp32 forward, per-pair policy) are issued once for all of them: a block finds its call from the block
+// launches (prep, fp32 forward, per-pair policy; a mid-size region's policy is two) are issued once for all of them: a block finds its call from the block
 // offsets in the kernel arguments and runs that call's part exactly as the single-call kernel would.  The per-call
 // arguments are the call's descriptor, which travels in its plan block.
 struct SmallCall {
@@ -115,7 +115,13 @@ struct SmallCall {
   int32_t prep_grid, rpl_main, main_blocks, rows, n_pairs, fma;
   int32_t fused;  // the whole pair in one wavefront (pair_fused_block) instead of the packed fp32 pass + per-pair policy
   int32_t speculate;  // host side only: the context asked for the fp64 pass beside the fp32 one when the call runs alone
+  // a mid-size call (kSmallTwoStep): the policy in two launches -- the list of the pairs it flags (n_pairs entries, the
+  // call's own; its counter is q.count) and the call's blocks in the flag and the recomputation launch
+  int32_t kind;   // kSmallOneLaunch / kSmallFused / kSmallTwoStep: calls of one kind share a set
+  int32_t flag_grid, recompute_grid;
+  int32_t* list;
 };
+enum : int32_t { kSmallOneLaunch = 0, kSmallFused = 1, kSmallTwoStep = 2 };
 // A set holds up to kMultiMax (64) calls, all in the kernel arguments (776 bytes; pairhmm_multi_sets.h: the limits, the
 // prefix sums and the lookup, shared with the host).
 struct MultiArgs {
@@ -171,6 +177,32 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kRplF64 <= 4
   const FwdArgs<double> d = c->d;
   const PairPolicyArgs q = c->q;
   pair_fused_block<kRplF64, FMA>(f, d, q, p, lds);
+}
+
+// Mid-size calls (kSmallTwoStep) of a set: the two launches of their policy.  A block belongs to ONE region -- region k
+// owns multi_flag_blocks(n_pairs_k) blocks of the flag launch and multi_recompute_blocks(n_pairs_k) of the recomputation,
+// what its single call launches -- and appends to / walks that region's own list through that region's own counter.
+static_assert(kFlagBlock == kPairFlagBlock, "the host's grid arithmetic and the kernel's block");
+__global__ __launch_bounds__(kPairFlagBlock) void pair_flag_multi_kernel(MultiArgs m) {
+  const int r = multi_find(m, (int)blockIdx.x);
+  const SmallCall* c = m.call[r];
+  const PairPolicyArgs q = c->q;
+  pair_flag_block(q, c->n_pairs, c->list, multi_local(m.begin, r, (int)blockIdx.x));
+}
+template <bool FMA, int MAXR>  // MAXR: rows per lane of the set's longest read (2, 4 or kRplF64); a pair takes the variant its own read needs
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) void pair_recompute_multi_kernel(MultiArgs m) {
+  __shared__ __attribute__((aligned(16))) unsigned char lds[PairRecomputeLds<MAXR, FMA>::bytes];
+  const int r = multi_find(m, (int)blockIdx.x);
+  const SmallCall* c = m.call[r];
+  // What every region of a set has in common is said here as constants (mid_call_shares: host finalisation of packed
+  // words; recompute_args: no packed output of the forward kernels): the device log10 of the other finalisation modes
+  // and the forward kernels' packed stores are then not compiled in -- their hoisted constants were what made the
+  // kRplF64 forms spill more than their single forms.
+  FwdArgs<double> d = c->d;
+  d.packed_out = nullptr;
+  PairPolicyArgs q = c->q;
+  q.mode = kModePackedWords;
+  pair_recompute_block<MAXR, FMA>(d, q, c->list, multi_local(m.begin, r, (int)blockIdx.x), c->recompute_grid, lds);
 }
 
 constexpr int kModePacked = kModePackedWords;  // FinalizeArgs::mode: `out` receives packed raw sums (kPackedF32Tag, pairhmm_fwd_kernel.h)

@@ -250,8 +250,8 @@ int pick_f32_rpl(int forced, int n_reads, int n_haps, const int64_t* read_off, c
 
 // the per-pair policy of a mid-size call in two launches (pairhmm_pair_flag_kernel): `list` holds n_pairs entries
 void launch_pair_policy_two_step(const FwdArgs<double>& d, const PairPolicyArgs& q, int rows, int fma, int64_t n_pairs, int32_t* list, hipStream_t s) {
-  hipLaunchKernelGGL(pairhmm_pair_flag_kernel, dim3((unsigned)((n_pairs + 255) / 256)), dim3(256), 0, s, q, (int32_t)n_pairs, list);
-  const dim3 grid((unsigned)std::max<int64_t>(256, n_pairs / 2)), block(64);
+  hipLaunchKernelGGL(pairhmm_pair_flag_kernel, dim3((unsigned)multi_flag_blocks((int)n_pairs)), dim3(kFlagBlock), 0, s, q, (int32_t)n_pairs, list);
+  const dim3 grid((unsigned)multi_recompute_blocks((int)n_pairs)), block(64);
   if (fma) {
     if (rows == 2)      hipLaunchKernelGGL((pairhmm_pair_recompute_kernel<2, true>), grid, block, 0, s, d, q, list);
     else if (rows == 4) hipLaunchKernelGGL((pairhmm_pair_recompute_kernel<4, true>), grid, block, 0, s, d, q, list);
@@ -357,6 +357,13 @@ bool deferral_offered(bool inline_host) { return g_env.combine && inline_host; }
 bool small_call_defers(const DevCtx* c, const CallPlan& P) {
   return deferral_offered(P.inline_host) && P.pull && c->cfg.record_events == 0 && P.per_pair && c->plan.long_reads.empty() &&
          P.finalize_mode == kModePacked && c->plan.n_chunks > 0 && P.n_pairs <= kTwoStepFrom;
+}
+// A mid-size region of a gklhip_compute_multi call shares a set with others of its kind (dev_compute_host_multi) when
+// everything above holds except the size: kTwoStepFrom < pairs <= kDirectPairs (per_pair says so), its policy in two
+// launches (not fused).  Asked of a plan that small_call_defers turned down; a SINGLE call never asks.
+bool mid_call_shares(const DevCtx* c, const CallPlan& P) {
+  return deferral_offered(P.inline_host) && P.pull && c->cfg.record_events == 0 && P.per_pair && !P.fused && c->plan.long_reads.empty() &&
+         P.finalize_mode == kModePacked && c->plan.n_chunks > 0 && P.n_pairs > kTwoStepFrom && P.n_pairs <= kDirectPairs;
 }
 // `load` of pick_f32_rpl: 1 for a call that is not offered deferral.  (About half of the calls inside the library are on
 // the device at any moment, the others are being staged or finalised: 16 callers of 100 x 10 regions keep the 4-row
@@ -912,6 +919,12 @@ void describe_small_call(DevCtx* c, const CallPlan& P, const StagedCall& S, Smal
   k.rpl_main = P.rpl_main; k.main_blocks = P.n_main_blocks; k.rows = P.rows; k.n_pairs = (int32_t)P.n_pairs; k.fma = P.fma;
   k.fused = P.fused ? 1 : 0;
   k.speculate = c->speculate_fp64;
+  // (a mid-size region: its list is the lane's fail_order, reserved for n_pairs entries by whoever staged it)
+  const bool two_step = !P.fused && P.n_pairs > kTwoStepFrom;
+  k.kind = P.fused ? kSmallFused : two_step ? kSmallTwoStep : kSmallOneLaunch;
+  k.flag_grid = two_step ? multi_flag_blocks(k.n_pairs) : 0;
+  k.recompute_grid = two_step ? multi_recompute_blocks(k.n_pairs) : 0;
+  k.list = two_step ? c->fail_order.as<int32_t>() : nullptr;
   memcpy(S.hs + P.L.desc, &k, sizeof k);
   out->desc_pinned = reinterpret_cast<const SmallCall*>(S.hs_dev + P.L.desc);
   out->desc_dev = reinterpret_cast<const SmallCall*>(S.dp + P.L.desc);

@@ -947,8 +947,10 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(3))) void p
 // to 100 us late (tools/small_scaling.py: 66 us for 1000 pairs, 165 us for 16 000 with the same share recomputing).
 // Here a thread per pair applies the policy and compacts the failing pairs into a list; the recomputing wavefronts
 // then sit at the FRONT of a grid half the size and start at once.
-__global__ __launch_bounds__(256) void pairhmm_pair_flag_kernel(PairPolicyArgs q, int32_t n_pairs, int32_t* list) {
-  const int p = blockIdx.x * 256 + threadIdx.x;
+constexpr int kPairFlagBlock = 256;
+// (block `block` of one call's flag launch: shared with pair_flag_multi_kernel, pairhmm_aux_kernels.h)
+__device__ __forceinline__ void pair_flag_block(const PairPolicyArgs& q, int32_t n_pairs, int32_t* list, int block) {
+  const int p = block * kPairFlagBlock + threadIdx.x;
   const int lane = threadIdx.x & 63;
   bool fails = false;
   if (p < n_pairs) {
@@ -969,13 +971,22 @@ __global__ __launch_bounds__(256) void pairhmm_pair_flag_kernel(PairPolicyArgs q
     if (fails) list[base + __popcll(m & ((1ull << lane) - 1ull))] = p;
   }
 }
+__global__ __launch_bounds__(kPairFlagBlock) void pairhmm_pair_flag_kernel(PairPolicyArgs q, int32_t n_pairs, int32_t* list) {
+  pair_flag_block(q, n_pairs, list, (int)blockIdx.x);
+}
+// LDS of a recomputing wavefront: the table of the widest variant it may take
 template <int MAXR, bool FMA>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) void pairhmm_pair_recompute_kernel(FwdArgs<double> a, PairPolicyArgs q,
-                                                                                                           const int32_t* list) {
-  constexpr int kLds2 = WaveJob<double, 2, FMA>::kLdsBytes, kLds4 = WaveJob<double, 4, FMA>::kLdsBytes, kLdsR = WaveJob<double, MAXR, FMA>::kLdsBytes;
-  __shared__ __attribute__((aligned(16))) unsigned char lds[kLdsR > kLds4 ? (kLdsR > kLds2 ? kLdsR : kLds2) : (kLds4 > kLds2 ? kLds4 : kLds2)];
+struct PairRecomputeLds {
+  static constexpr int k2 = WaveJob<double, 2, FMA>::kLdsBytes, k4 = WaveJob<double, 4, FMA>::kLdsBytes, kR = WaveJob<double, MAXR, FMA>::kLdsBytes;
+  static constexpr int bytes = kR > k4 ? (kR > k2 ? kR : k2) : (k4 > k2 ? k4 : k2);
+};
+// Block `block` of the `grid` blocks that recompute one call's list: entries block, block + grid, ... (every entry of
+// the list once over the grid); shared with pair_recompute_multi_kernel.
+template <int MAXR, bool FMA>
+__device__ __forceinline__ void pair_recompute_block(const FwdArgs<double>& a, const PairPolicyArgs& q, const int32_t* list, int block, int grid,
+                                                     unsigned char* lds) {
   const int n = *reinterpret_cast<const volatile int32_t*>(q.count);
-  for (int i = blockIdx.x; i < n; i += gridDim.x) {
+  for (int i = block; i < n; i += grid) {
     const int64_t p = list[i];
     const int r = (int)(p / a.b.n_haps), k = q.hap_sidx[(int)(p - (int64_t)r * a.b.n_haps)];
     const int R = (int)(a.b.read_off[r + 1] - a.b.read_off[r]);
@@ -984,6 +995,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) void pa
     else                                      pair_policy_recompute<MAXR, FMA>(a, q, p, r, R, k, lds);
     __syncthreads();  // (a block that takes a second pair reuses the prior table)
   }
+}
+template <int MAXR, bool FMA>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) void pairhmm_pair_recompute_kernel(FwdArgs<double> a, PairPolicyArgs q,
+                                                                                                           const int32_t* list) {
+  __shared__ __attribute__((aligned(16))) unsigned char lds[PairRecomputeLds<MAXR, FMA>::bytes];
+  pair_recompute_block<MAXR, FMA>(a, q, list, (int)blockIdx.x, (int)gridDim.x, lds);
 }
 
 // Long-read pass: a read with more rows than one chunk holds is processed stripe by stripe by

@@ -117,19 +117,39 @@ struct SmallCombiner {
     return GKLHIP_OK;
   }
   int launch_multi(const SmallLaunch* const* calls, int n, int fma, Slot& sl) {
+    const bool two_step = calls[0]->call.kind == kSmallTwoStep;   // a set of mid-size regions (gklhip_compute_multi only)
     MultiArgs mp{}, mf{}, mq{};
     mp.n = mf.n = mq.n = n;
-    int32_t prep_blocks[kMultiMax], main_blocks[kMultiMax], pair_blocks[kMultiMax];
+    int32_t prep_blocks[kMultiMax], main_blocks[kMultiMax], pair_blocks[kMultiMax];   // pair_blocks: the policy launch (two-step: the flag launch)
     for (int i = 0; i < n; i++) {
       const SmallLaunch& L = *calls[i];
       mp.call[i] = L.desc_pinned; mf.call[i] = L.desc_dev; mq.call[i] = L.desc_dev;
-      prep_blocks[i] = L.call.prep_grid; main_blocks[i] = L.call.main_blocks; pair_blocks[i] = L.call.n_pairs;
+      prep_blocks[i] = L.call.prep_grid; main_blocks[i] = L.call.main_blocks; pair_blocks[i] = two_step ? L.call.flag_grid : L.call.n_pairs;
     }
     multi_begin(prep_blocks, n, mp.begin);
     multi_begin(main_blocks, n, mf.begin);
     multi_begin(pair_blocks, n, mq.begin);
     hipLaunchKernelGGL(prep_multi_kernel, dim3((unsigned)mp.begin[n]), dim3(kPrepBlock), 0, sl.stream, mp);
-    if (calls[0]->call.fused) {  // (every call of a set is of one kind: a leader only takes calls like its own, a multi call cuts its sets by kind)
+    if (two_step) {   // the packed fp32 pass, then the policy in two launches
+      MultiArgs mr = mq;
+      int32_t rec_blocks[kMultiMax];
+      int rows = 2;   // of the set's longest read
+      for (int i = 0; i < n; i++) { rec_blocks[i] = calls[i]->call.recompute_grid; rows = std::max(rows, calls[i]->call.rows); }
+      multi_begin(rec_blocks, n, mr.begin);
+      const dim3 grid((unsigned)mr.begin[n]), block(64);
+      if (fma) hipLaunchKernelGGL((fwd_stream_multi_kernel<true, kRplF32>), dim3((unsigned)mf.begin[n]), dim3(64), 0, sl.stream, mf);
+      else     hipLaunchKernelGGL((fwd_stream_multi_kernel<false, kRplF32>), dim3((unsigned)mf.begin[n]), dim3(64), 0, sl.stream, mf);
+      hipLaunchKernelGGL(pair_flag_multi_kernel, dim3((unsigned)mq.begin[n]), dim3(kFlagBlock), 0, sl.stream, mq);
+      if (fma) {
+        if (rows == 2)      hipLaunchKernelGGL((pair_recompute_multi_kernel<true, 2>), grid, block, 0, sl.stream, mr);
+        else if (rows == 4) hipLaunchKernelGGL((pair_recompute_multi_kernel<true, 4>), grid, block, 0, sl.stream, mr);
+        else                hipLaunchKernelGGL((pair_recompute_multi_kernel<true, kRplF64>), grid, block, 0, sl.stream, mr);
+      } else {
+        if (rows == 2)      hipLaunchKernelGGL((pair_recompute_multi_kernel<false, 2>), grid, block, 0, sl.stream, mr);
+        else if (rows == 4) hipLaunchKernelGGL((pair_recompute_multi_kernel<false, 4>), grid, block, 0, sl.stream, mr);
+        else                hipLaunchKernelGGL((pair_recompute_multi_kernel<false, kRplF64>), grid, block, 0, sl.stream, mr);
+      }
+    } else if (calls[0]->call.fused) {  // (every call of a set is of one kind: a leader only takes calls like its own, a multi call cuts its sets by kind)
       bool narrow = true;   // reads of at most 255 bases in every call of the set: the four-wavefronts-per-SIMD variant
       for (int i = 0; i < n; i++) narrow = narrow && calls[i]->call.rows <= 4;
       const dim3 grid((unsigned)mq.begin[n]), block(64);
@@ -401,8 +421,9 @@ struct MultiRegion {
 
 // The regions that the single-call path would defer are staged on the context's lanes -- plan_call, stage_call and
 // describe_small_call, exactly as a single call stages itself --, cut into sets (multi_cut_sets) and leave set by set through
-// the combiner's launches; each region's packed words are then finalised on the host as a single call's are.  Every other
-// region comes back marked `alone`.
+// the combiner's launches; each region's packed words are then finalised on the host as a single call's are.  Mid-size
+// regions (mid_call_shares) are staged the same way and cut among themselves (multi_cut_mid_sets): two or more of them
+// share sets of their own, one alone is no set.  Every other region comes back marked `alone`.
 // Up to kMultiMax regions are staged first and cut afterwards; a longer list is planned twice: once to learn which regions
 // qualify (the cut needs that of the whole list), once more when the region's set is staged.
 // A failure is the region's own (`rc`, `err`), a failed set's the failure of every region in it; the return value is for
@@ -418,61 +439,88 @@ int dev_compute_host_multi(DevCtx* c, std::vector<DevCtx*>& lanes, std::vector<M
   std::vector<SmallLaunch> staged((size_t)kMultiMax);   // by lane
   std::vector<int> owner((size_t)kMultiMax, -1);        // by lane: the region whose raw sums it holds
   auto fail_region = [](MultiRegion& r, int rc) { r.rc = rc; r.err = g_err; };
-  // Plans region i on lane `li` and -- unless plan_only -- stages it there.  False: no set for this region (it does not
-  // qualify: r.alone; it failed: r.rc).  *fused: the kind of a region that qualifies.
-  auto stage = [&](int i, int li, bool plan_only, uint8_t* fused) {
+  enum { kNone, kSmall, kMid };
+  // Plans region i on lane `li` and -- unless plan_only -- stages it there.  kNone: no set for this region (it does not
+  // qualify: r.alone; it failed: r.rc).  *fused: the kind of a small region that qualifies.
+  auto stage = [&](int i, int li, bool plan_only, uint8_t* fused) -> int {
     MultiRegion& r = R[(size_t)i];
     const gklhip_batch* hb = r.hb;
-    if (on_device || !deferral_offered(inputs_inline(hb))) { r.alone = true; return false; }
+    if (on_device || !deferral_offered(inputs_inline(hb))) { r.alone = true; return kNone; }
     while ((int)lanes.size() <= li) {   // lanes are made on first use
       DevCtx* ln = nullptr;
       const int rc = lane_init(c, &ln);
-      if (rc != GKLHIP_OK) { fail_region(r, rc); return false; }
+      if (rc != GKLHIP_OK) { fail_region(r, rc); return kNone; }
       lanes.push_back(ln);
     }
     DevCtx* ln = lanes[(size_t)li];
-    int rc = GKLHIP_OK;
-    void* pin_out = nullptr;
-    if (!plan_only) {
-      if (owner[(size_t)li] >= 0) R[(size_t)owner[(size_t)li]].lane = -1;   // an earlier set's region: its raw sums go now
-      owner[(size_t)li] = -1;
-      rc = ln->res_pin.reserve((size_t)hb->n_reads * (size_t)hb->n_haps * 8);
-      if (rc == GKLHIP_OK && hipHostGetDevicePointer(&pin_out, ln->res_pin.p, 0) != hipSuccess) { (void)hipGetLastError(); rc = fail(GKLHIP_ERR_HIP, "hipHostGetDevicePointer failed"); }
-      if (rc != GKLHIP_OK) { fail_region(r, rc); return false; }
-    }
     CallPlan P;
     plan_call(ln, hb, kModePacked, true, true, call_load(true), &P);
-    if (!P.defers) { r.alone = true; return false; }
+    const bool mid = !P.defers && mid_call_shares(ln, P);
+    if (!P.defers && !mid) { r.alone = true; return kNone; }
+    P.defers = true;   // (a mid-size region too is staged for the combiner: see stage_call)
     *fused = P.fused ? 1 : 0;
-    if (plan_only) return true;
+    const int what = mid ? kMid : kSmall;
+    if (plan_only) return what;
+    int rc = GKLHIP_OK;
+    void* pin_out = nullptr;
+    if (owner[(size_t)li] >= 0) R[(size_t)owner[(size_t)li]].lane = -1;   // an earlier set's region: its raw sums go now
+    owner[(size_t)li] = -1;
+    rc = ln->res_pin.reserve((size_t)hb->n_reads * (size_t)hb->n_haps * 8);
+    if (rc == GKLHIP_OK && hipHostGetDevicePointer(&pin_out, ln->res_pin.p, 0) != hipSuccess) { (void)hipGetLastError(); rc = fail(GKLHIP_ERR_HIP, "hipHostGetDevicePointer failed"); }
+    if (rc != GKLHIP_OK) { fail_region(r, rc); return kNone; }
     StagedCall S;   // (the regions of a multi call are staged on lanes that have no stream of their own)
-    if ((rc = stage_call(ln, hb, P, static_cast<double*>(pin_out), c->stream, &S))) { fail_region(r, rc); return false; }
+    if ((rc = stage_call(ln, hb, P, static_cast<double*>(pin_out), c->stream, &S))) { fail_region(r, rc); return kNone; }
+    if (mid && (rc = ln->fail_order.reserve((size_t)P.n_pairs * 4))) { fail_region(r, rc); return kNone; }   // the list of its flagged pairs
     describe_small_call(ln, P, S, &staged[(size_t)li]);
     owner[(size_t)li] = i; r.lane = li;
-    return true;
+    return what;
   };
-  std::vector<uint8_t> qualifies((size_t)n), kind((size_t)n);
-  for (int i = 0; i < n; i++) qualifies[(size_t)i] = stage(i, stage_first ? i : 0, !stage_first, &kind[(size_t)i]) ? 1 : 0;
-  std::vector<int32_t> set_of((size_t)n);
-  const int n_sets = multi_cut_sets(qualifies.data(), kind.data(), n, set_of.data());
-  for (int s = 0, i = 0; s < n_sets; s++) {
-    const SmallLaunch* calls[kMultiMax];
-    int members[kMultiMax], m = 0;
-    for (; i < n && set_of[(size_t)i] <= s; i++) {
-      if (set_of[(size_t)i] != s) continue;
-      if (!stage_first && !stage(i, m, false, &kind[(size_t)i])) continue;   // (planned under another load, it no longer qualifies: alone after all)
-      calls[m] = &staged[(size_t)R[(size_t)i].lane];
-      members[m++] = i;
-    }
-    if (m == 0) continue;
-    const int rc = k->run_set(calls, m, c->stream);
-    for (int j = 0; j < m; j++) {
-      MultiRegion& r = R[(size_t)members[j]];
-      DevCtx* ln = lanes[(size_t)r.lane];
-      if (rc != GKLHIP_OK) { fail_region(r, rc); owner[(size_t)r.lane] = -1; r.lane = -1; continue; }
-      const HostFinalizer fin;
-      ln->stats.n_fallback = fin.all(&c->workers, ln->res_pin.as<uint64_t>(), r.out, ln->stats.n_pairs, threads, one_pass_min());
-      r.stats = ln->stats;
+  // A region that was staged and then finds no set: through the single-call path after all.
+  auto run_alone = [&](int i) {
+    MultiRegion& r = R[(size_t)i];
+    if (r.lane >= 0) owner[(size_t)r.lane] = -1;
+    r.lane = -1; r.alone = true;
+  };
+  std::vector<uint8_t> qualifies((size_t)n), mid((size_t)n), kind((size_t)n);
+  for (int i = 0; i < n; i++) {
+    const int what = stage(i, stage_first ? i : 0, !stage_first, &kind[(size_t)i]);
+    qualifies[(size_t)i] = what == kSmall ? 1 : 0;
+    mid[(size_t)i] = what == kMid ? 1 : 0;
+  }
+  std::vector<int32_t> set_of((size_t)n), mid_set_of((size_t)n);
+  const int n_small_sets = multi_cut_sets(qualifies.data(), kind.data(), n, set_of.data());
+  const int n_mid_sets = multi_cut_mid_sets(mid.data(), n, mid_set_of.data());
+  for (int i = 0; i < n; i++)
+    if (mid[(size_t)i] && mid_set_of[(size_t)i] < 0) run_alone(i);
+  // the small regions' sets, then the mid-size regions' (a set is of one kind)
+  for (int pass = 0; pass < 2; pass++) {
+    const std::vector<int32_t>& of = pass == 0 ? set_of : mid_set_of;
+    const int n_sets = pass == 0 ? n_small_sets : n_mid_sets;
+    const int want = pass == 0 ? kSmall : kMid;
+    for (int s = 0, i = 0; s < n_sets; s++) {
+      const SmallLaunch* calls[kMultiMax];
+      int members[kMultiMax], m = 0;
+      for (; i < n && of[(size_t)i] <= s; i++) {
+        if (of[(size_t)i] != s) continue;
+        if (!stage_first) {
+          const int what = stage(i, m, false, &kind[(size_t)i]);
+          if (what == kNone) continue;                          // (planned under another load, it no longer qualifies: alone after all)
+          if (what != want) { run_alone(i); continue; }
+        }
+        calls[m] = &staged[(size_t)R[(size_t)i].lane];
+        members[m++] = i;
+      }
+      if (m == 0) continue;
+      if (pass == 1 && m == 1) { run_alone(members[0]); continue; }   // (its company failed to stage: one mid-size region is no set)
+      const int rc = k->run_set(calls, m, c->stream);
+      for (int j = 0; j < m; j++) {
+        MultiRegion& r = R[(size_t)members[j]];
+        DevCtx* ln = lanes[(size_t)r.lane];
+        if (rc != GKLHIP_OK) { fail_region(r, rc); owner[(size_t)r.lane] = -1; r.lane = -1; continue; }
+        const HostFinalizer fin;
+        ln->stats.n_fallback = fin.all(&c->workers, ln->res_pin.as<uint64_t>(), r.out, ln->stats.n_pairs, threads, one_pass_min());
+        r.stats = ln->stats;
+      }
     }
   }
   return GKLHIP_OK;

@@ -46,6 +46,30 @@ inline int multi_cut_sets(const uint8_t* qualifies, const uint8_t* kind, int n, 
   return n_sets;
 }
 
+// Mid-size regions (two-launch per-pair policy: more than kTwoStepFrom pairs, pairhmm_device_pass.h) share sets of their
+// own kind only, and are cut apart from the small ones: for the small regions' cut they are regions that do not qualify
+// (they do not interrupt a run of small regions), and here the small ones do not interrupt them.  The mid-size regions of
+// the call, in input order, are cut by the rule above -- at most kMultiMax per set, sizes differing by at most one -- and a
+// set of ONE region is no set: that region runs alone through the single-call path (set_of -1).  Sets are numbered from 0.
+inline int multi_cut_mid_sets(const uint8_t* mid, int n, int32_t* set_of) {
+  int m = 0;
+  for (int k = 0; k < n; k++) m += mid[k] ? 1 : 0;
+  const int sets = m < 2 ? 0 : (m + kMultiMax - 1) / kMultiMax;
+  for (int k = 0, i = 0; k < n; k++) {
+    if (!mid[k] || sets == 0) { set_of[k] = -1; continue; }
+    set_of[k] = (int)((int64_t)i * sets / m);
+    i++;
+  }
+  return sets;
+}
+
+// The two launches of a mid-size region's policy, as the single call sizes them (launch_pair_policy_two_step) and as the
+// region's share of a set's launches: a thread per pair flags, then `multi_recompute_blocks` one-wavefront blocks walk the
+// list of the flagged pairs -- local block b takes entries b, b + g, b + 2 g, ... of the region's count.
+constexpr int kFlagBlock = 256;
+GKL_MS_HD int multi_flag_blocks(int n_pairs) { return (n_pairs + kFlagBlock - 1) / kFlagBlock; }
+GKL_MS_HD int multi_recompute_blocks(int n_pairs) { return n_pairs / 2 > 256 ? n_pairs / 2 : 256; }
+
 // begin[0 .. n]: first block of each call in a launch of `blocks[k]` blocks per call (begin[n] = the grid).
 inline void multi_begin(const int32_t* blocks, int n, int32_t* begin) {
   begin[0] = 0;

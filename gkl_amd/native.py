@@ -383,7 +383,8 @@ class PairHmmContext:
         return out
 
     def compute_multi(self, batches) -> list:
-        """Several region calls, the GATK-sized ones in one set of launches (gklhip_compute_multi): batches is a list of
+        """Several region calls in shared sets of launches (gklhip_compute_multi): the GATK-sized regions of up to 2048
+        pairs among themselves, the mid-size ones of up to 65 536 pairs among themselves.  batches is a list of
         FlatBatch; returns the list of their likelihood arrays, each byte for byte what compute() returns for it alone.
         When regions fail, the others are still computed: PairHmmMultiError carries their arrays and every region's
         status and exception."""

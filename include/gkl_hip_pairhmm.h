@@ -160,14 +160,24 @@ int gklhip_compute(gklhip_ctx* ctx, const gklhip_batch* host_batch, double* out_
  * checks of the single call run per region before anything touches the device: a region that fails them is left out and
  * the rest still run.  A region with n_reads * n_haps == 0 succeeds and writes nothing.  A HIP failure of a shared set of
  * launches fails every region in that set (after its stream has been drained).
- * Which regions share a set: those the single call hands to the small-call combiner (inputs of at most 1 MB, at most
- * 2048 pairs, no read of 384 bases or more, host finalisation, no use_double, no record_events).  In input order they
- * are cut into sets of one kind (with rows_per_lane == 0: the fused per-pair kernel) of at most 64 regions; each region
- * is planned and staged exactly as a single call is, on one of up to 64 staging lanes of the context (made on first
- * use, given back by gklhip_release_idle), and a set leaves through the combiner's launches: it waits for a flight slot
- * like the set of any concurrent callers, but takes nobody else's calls and waits for no company.  Every other region --
- * and every region of a multi-device context, of a process with GKL_HIP_COMBINE=0 and of a client context, whose wire
- * protocol has no multi request -- is computed afterwards through the single-call path, in input order.
+ * Which regions share a set: SMALL ones, those the single call hands to the small-call combiner (inputs of at most 1 MB,
+ * at most 2048 pairs, no read of 384 bases or more, host finalisation, no use_double, no record_events), and MID-SIZE
+ * ones, for which all of that holds except the size: 2049 to 65 536 pairs.  The two are cut apart.  The small regions,
+ * in input order, are cut into sets of one kind (with rows_per_lane == 0: the fused per-pair kernel) of at most 64
+ * regions.  The mid-size regions share sets among themselves only -- prep, the packed fp32 pass, and the per-pair
+ * policy in two launches, once for the whole set -- in input order, at most 64 per set, and they need company of their
+ * own kind: ONE mid-size region in a call is no set and runs alone, as before.  Each region of a set is planned and staged
+ * exactly as a single call is, on one of up to 64 staging lanes of the context (made on first use, given back by
+ * gklhip_release_idle), and a set leaves through the combiner's launches: it waits for a flight slot like the set of any
+ * concurrent callers, but takes nobody else's calls and waits for no company.  Every other region -- and every region of
+ * a multi-device context, of a process with GKL_HIP_COMBINE=0 and of a client context, whose wire protocol has no multi
+ * request -- is computed afterwards through the single-call path, in input order.  A single gklhip_compute of a mid-size
+ * region is never combined with anything.
+ * Memory: a lane keeps the buffers of the biggest region it staged until gklhip_release_idle.  One that held a
+ * 65 536-pair region keeps at most about 7 MB of device memory (two plan blocks of up to 1 MB, the haplotype streams,
+ * 4 + 8 + 1 bytes per pair of raw sums and flags, the 4 bytes per pair of its list of flagged pairs, its lane map; each
+ * allocated a quarter above its size) and 3 MB of pinned host memory (two staging blocks, 8 bytes per pair of result
+ * words): 64 such lanes under 0.5 GB and 0.2 GB.  A lane that only ever held 100 x 10 regions keeps a few hundred KB.
  * gklhip_small_call_counts: a set of n regions adds n to the calls, n to the combined calls when n > 1, and 1 to the
  * sets; a region that ran alone counts as a single call does.  Afterwards gklhip_get_stats holds the sums over the
  * regions of n_pairs, n_fallback, cells and cells_fp64 (the other fields are 0), gklhip_get_raw fails ("no completed call

@@ -1,10 +1,11 @@
 #!/usr/bin/env python3
-"""K distinct seeded `hc` regions of 100 reads x 10 haplotypes as ONE gklhip_compute_multi call against K consecutive
-gklhip_compute calls on the same context: median host-to-host time of each, K in --counts, the two arms alternating in one
-process.  Both arms are made on prebuilt arguments: nothing but the C ABI is timed.  Checks that both give the same bytes
-and reports how many sets of launches the multi call took (gklhip_small_call_counts).
+"""K distinct seeded `hc` regions of READS x HAPS (--region, default 100 reads x 10 haplotypes) as ONE gklhip_compute_multi
+call against K consecutive gklhip_compute calls on the same context: median host-to-host time of each, K in --counts, the
+two arms alternating in one process.  Both arms are made on prebuilt arguments: nothing but the C ABI is timed.  Checks that
+both give the same bytes and reports how many sets of launches the multi call took (gklhip_small_call_counts: calls,
+combined calls, sets).  A mid-size shape (400x40, 250x128, 1000x50) measures the mid-size sets of docs/NOTES.md 69.
 
-usage: tools/pairhmm_multi_timing.py [--counts 1,2,4,8,16,64] [--reps 30] [--warmup 10] [--out FILE]"""
+usage: tools/pairhmm_multi_timing.py [--region 100x10] [--counts 1,2,4,8,16,64] [--reps 30] [--warmup 10] [--out FILE]"""
 import argparse
 import ctypes as C
 import json
@@ -20,6 +21,7 @@ sys.path.insert(0, ROOT)
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--region", default="100x10", help="READSxHAPS of every region")
     ap.add_argument("--counts", default="1,2,4,8,16,64")
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=10)
@@ -27,13 +29,19 @@ def main():
     a = ap.parse_args()
     if a.reps < 30:
         raise SystemExit("at least 30 repetitions")
+    try:
+        n_reads, n_haps = (int(x) for x in a.region.lower().split("x"))
+    except ValueError:
+        raise SystemExit("--region wants READSxHAPS, e.g. 400x40")
+    if n_reads < 1 or n_haps < 1:
+        raise SystemExit("--region wants at least one read and one haplotype")
     from gkl_amd import native
     from gkl_amd.synth import make_batch
     ctx = native.PairHmmContext(device=0)
     lib, h = ctx.lib, ctx.handle
-    result = {"region": "hc 100 x 10", "reps": a.reps, "warmup": a.warmup, "rows": []}
+    result = {"region": f"hc {n_reads} x {n_haps}", "reps": a.reps, "warmup": a.warmup, "rows": []}
     for K in (int(x) for x in a.counts.split(",")):
-        batches = [make_batch("hc", 100, 10, seed=1000 + k) for k in range(K)]
+        batches = [make_batch("hc", n_reads, n_haps, seed=1000 + k) for k in range(K)]
         keep, cbs = [], (native.CBatch * K)()
         for k, b in enumerate(batches):
             arrs = [np.ascontiguousarray(x, np.uint8) for x in (b.read_bases, b.read_quals, b.ins_gop, b.del_gop, b.gcp, b.hap_bases)]
