@@ -102,6 +102,7 @@ static int init_devices_impl(const gklhip_config* cfg, const int32_t* devices, i
     dcfg.device = d;
     const int rc = dev_init(dcfg, d, ndev, &dc);
     if (rc) return rc;
+    dc->multi_device = list.size() > 1;
     c->dev.push_back(dc);
   }
   const int n = (int)c->dev.size();
@@ -570,7 +571,7 @@ static int get_raw_region_impl(gklhip_ctx* ctx, int32_t region, float* raw32, do
   DevCtx* c = ctx->lanes[(size_t)lane];
   HIP_TRY(hipSetDevice(c->device));
   hipStream_t s = ctx->dev[0]->stream;   // (the region's set has ended: any stream will do)
-  if (raw32) HIP_TRY(hipMemcpyAsync(raw32, c->raw32.p, n * 4, hipMemcpyDeviceToHost, s));
+  if (raw32 && !c->cfg.use_double) HIP_TRY(hipMemcpyAsync(raw32, c->raw32.p, n * 4, hipMemcpyDeviceToHost, s));   // (as gklhip_get_raw: a double-precision context has no fp32 sums)
   if (raw64) HIP_TRY(hipMemcpyAsync(raw64, c->raw64.p, n * 8, hipMemcpyDeviceToHost, s));
   if (used64) HIP_TRY(hipMemcpyAsync(used64, c->used64.p, n, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));

@@ -117,11 +117,12 @@ struct SmallCall {
   int32_t speculate;  // host side only: the context asked for the fp64 pass beside the fp32 one when the call runs alone
   // a mid-size call (kSmallTwoStep): the policy in two launches -- the list of the pairs it flags (n_pairs entries, the
   // call's own; its counter is q.count) and the call's blocks in the flag and the recomputation launch
-  int32_t kind;   // kSmallOneLaunch / kSmallFused / kSmallTwoStep: calls of one kind share a set
+  int32_t kind;   // kSmallOneLaunch / kSmallFused / kSmallTwoStep / kSmallDouble: calls of one kind share a set
   int32_t flag_grid, recompute_grid;
   int32_t* list;
 };
-enum : int32_t { kSmallOneLaunch = 0, kSmallFused = 1, kSmallTwoStep = 2 };
+// (kSmallDouble: a small call of a double-precision context -- every pair through pair_f64_block; `f` and q.raw32 are unset)
+enum : int32_t { kSmallOneLaunch = 0, kSmallFused = 1, kSmallTwoStep = 2, kSmallDouble = 3 };
 // A set holds up to kMultiMax (64) calls, all in the kernel arguments (776 bytes; pairhmm_multi_sets.h: the limits, the
 // prefix sums and the lookup, shared with the host).
 struct MultiArgs {
@@ -177,6 +178,24 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kRplF64 <= 4
   const FwdArgs<double> d = c->d;
   const PairPolicyArgs q = c->q;
   pair_fused_block<kRplF64, FMA>(f, d, q, p, lds);
+}
+
+// Small calls of double-precision contexts (kSmallDouble) of a set: every pair of every call in double precision, one
+// pair per block (pair_f64_block).  MAXR: rows per lane of the set's longest read (4: no read of 256 bases or more in the
+// set, the four-wavefronts-per-SIMD form; kRplF64 otherwise).
+template <bool FMA, int MAXR>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MAXR <= 4 ? 4 : 3))) void pair_f64_multi_kernel(MultiArgs m) {
+  __shared__ __attribute__((aligned(16))) unsigned char lds[PairRecomputeLds<MAXR, FMA>::bytes];
+  const int r = multi_find(m, (int)blockIdx.x);
+  const SmallCall* c = m.call[r];
+  const int64_t p = multi_local(m.begin, r, (int)blockIdx.x);
+  // What every call of such a set has in common, as constants (small_call_defers: host finalisation of packed words;
+  // recompute_args: no packed output of the forward kernels): the device log10 paths are not compiled in.
+  FwdArgs<double> d = c->d;
+  d.packed_out = nullptr;
+  PairPolicyArgs q = c->q;
+  q.mode = kModePackedWords;
+  pair_f64_block<MAXR, FMA>(d, q, p, lds);
 }
 
 // Mid-size calls (kSmallTwoStep) of a set: the two launches of their policy.  A block belongs to ONE region -- region k

@@ -40,6 +40,7 @@ const EnvSwitches g_env;
 struct DevCtx {
   gklhip_config cfg;
   int device = 0;
+  bool multi_device = false;   // one of several engines of a multi-device context (set by gklhip_init_devices): its shards of a double-precision call keep the general pass
   int n_cus = 256;
   int n_xcds = 8;   // hipDeviceAttributeNumberOfXccs: workgroups go to the XCDs round-robin by index
   // development / cross-check switches, read from the environment ONCE per context (dev_init), never on a call path

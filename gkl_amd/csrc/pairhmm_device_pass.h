@@ -208,6 +208,7 @@ constexpr int kRplF64Wide = 8;
 constexpr size_t kSmallBatchBytes = 1 << 20;  // host-buffer calls up to this size send their inputs inside the plan block
 constexpr int64_t kDirectPairs = 65536;        // calls up to this many pairs: policy + fp64 recomputation of one pair per wavefront (host calls of 24k / 38k / 50k pairs: 0.64 / 0.74 / 0.96 ms against 0.81 / 0.82 / 1.09 through the planned fp64 pass; equal at 80k)
 constexpr int64_t kTwoStepFrom = 2048;         // ... from this many pairs in two launches: policy + list of the failing pairs, then their recomputation (10k / 16k / 32k pairs: 0.37 / 0.45-0.48 / 0.72-0.84 ms against 0.43 / 0.49-0.54 / 0.76-0.97 in one)
+constexpr int64_t kSmallDoublePairs = kTwoStepFrom;   // a small call of a double-precision context (kSmallDouble: every pair through pairhmm_pair_f64_kernel): at most this many pairs
 constexpr int kPlanBlocks = 64;                // 1024-thread blocks of the packing / run-detection launches of the fp64 plan
 constexpr int kFallbackWantedJobs = 12288;     // the packed fp64 pass is cut into about this many jobs (4 per wavefront slot)
 constexpr int64_t kHostShardPairs = 400000;    // single-device host-buffer calls from this many pairs run as two half-batches (see gklhip_ctx::host_dev)
@@ -304,6 +305,19 @@ void launch_pair_fused(const FwdArgs<float>& f, const FwdArgs<double>& d, const 
   else     hipLaunchKernelGGL((pairhmm_pair_fused_kernel<kRplF64, false>), grid, block, 0, s, f, d, q);
 }
 
+// small calls of a double-precision context: every pair in fp64, ONE pair per wavefront (pairhmm_pair_f64_kernel); `rows`:
+// by the call's longest read -- up to 4: the four-wavefronts-per-SIMD variant
+void launch_pair_f64(const FwdArgs<double>& d, const PairPolicyArgs& q, int rows, int fma, int64_t n_pairs, hipStream_t s) {
+  const dim3 grid((unsigned)n_pairs), block(64);
+  if (rows <= 4) {
+    if (fma) hipLaunchKernelGGL((pairhmm_pair_f64_kernel<4, true>), grid, block, 0, s, d, q);
+    else     hipLaunchKernelGGL((pairhmm_pair_f64_kernel<4, false>), grid, block, 0, s, d, q);
+    return;
+  }
+  if (fma) hipLaunchKernelGGL((pairhmm_pair_f64_kernel<kRplF64, true>), grid, block, 0, s, d, q);
+  else     hipLaunchKernelGGL((pairhmm_pair_f64_kernel<kRplF64, false>), grid, block, 0, s, d, q);
+}
+
 // A small plan (GATK-sized call) is PULLED from the pinned staging block by the prep kernel itself: no copy-engine hop at all.
 bool plan_pulled(size_t plan_bytes) { return plan_bytes < (1u << 20); }  // (256 KB .. 2 MB measure within 2 % on calls of 4k-50k pairs, 1 MB best)
 bool finalizes_on_device(int mode) { return mode == GKLHIP_FINALIZE_DEVICE_F64 || mode == GKLHIP_FINALIZE_DEVICE_REF32; }
@@ -340,6 +354,7 @@ struct CallPlan {
   PlanLayout L;
   bool pull;                     // the prep kernel pulls the block from pinned memory (plan_pulled)
   bool per_pair, fused;          // policy + fp64 of one pair per wavefront; ... with the fp32 recurrence in the same wavefront and launch
+  bool pair_double;              // a double-precision single-device context's call that fits the fp64 per-pair kernel (no read of 384 bases or more)
   int rows;                      // rows per lane of the per-pair kernels, by the longest read
   bool defers;                   // planned and staged, then handed to the small-call combiner (small_call_defers)
   int n_hist, chunk_stride, n_main_blocks, n_long_waves;   // grids and sizes that follow from the plan
@@ -353,10 +368,12 @@ struct CallPlan {
 // knows before it is planned (whether to offer deferral at all): inputs inline, not switched off (GKL_HIP_COMBINE=0) ...
 bool deferral_offered(bool inline_host) { return g_env.combine && inline_host; }
 // ... and of a planned call that was offered it (plan_call, nowhere else): plan block pulled, per-pair call, no long
-// read, host-exact packed finalisation, no event recording, at most kTwoStepFrom pairs.
+// read, host-exact packed finalisation, no event recording, at most kTwoStepFrom pairs.  A double-precision context's
+// call (kSmallDouble) under the same conditions: its per-pair kernel holds reads of up to 383 bases (pair_double), and its
+// size limit has a name of its own (kSmallDoublePairs).
 bool small_call_defers(const DevCtx* c, const CallPlan& P) {
-  return deferral_offered(P.inline_host) && P.pull && c->cfg.record_events == 0 && P.per_pair && c->plan.long_reads.empty() &&
-         P.finalize_mode == kModePacked && c->plan.n_chunks > 0 && P.n_pairs <= kTwoStepFrom;
+  return deferral_offered(P.inline_host) && P.pull && c->cfg.record_events == 0 && (P.per_pair || P.pair_double) && c->plan.long_reads.empty() &&
+         P.finalize_mode == kModePacked && c->plan.n_chunks > 0 && P.n_pairs <= (P.pair_double ? kSmallDoublePairs : kTwoStepFrom);
 }
 // A mid-size region of a gklhip_compute_multi call shares a set with others of its kind (dev_compute_host_multi) when
 // everything above holds except the size: kTwoStepFrom < pairs <= kDirectPairs (per_pair says so), its policy in two
@@ -422,6 +439,9 @@ void plan_call(DevCtx* c, const gklhip_batch* db, int finalize_mode, bool inline
   const int64_t fused_max = g_env.fused_max >= 0 ? g_env.fused_max : (int64_t)kTwoStepFrom;
   P.fused = P.per_pair && g_env.fused_pairs && P.n_pairs <= fused_max && P.n_long_main == 0 && c->cfg.rows_per_lane == 0;
   P.rows = plan.max_read_len <= 2 * kLanes - 1 ? 2 : plan.max_read_len <= 4 * kLanes - 1 ? 4 : kRplF64;
+  // a double-precision context: every pair through the same fp64 per-pair code, when the call's reads fit it (the shards
+  // of a multi-device context keep the general pass: that mode is as it was)
+  P.pair_double = P.use_double && !c->multi_device && plan.max_read_len <= kLanes * kRplF64 - 1;
   P.defers = deferral && small_call_defers(c, P);
 
   P.n_hist = P.use_double ? 0 : 2 * (n_haps + 2);
@@ -740,7 +760,9 @@ PlanArgs plan_args(const DevCtx* c, const CallPlan& P, const StagedCall& S) {
 // before finish_call.  In the policy mode a big call is 7 launches (prep, fp32 forward, the three launches of policy +
 // planning of the fp64 pass, fp64 forward over the job list, log10 / packed words of the recomputed pairs; + the log10
 // of the kept pairs on a side stream in the device finalisation modes), a call of up to 65 536 pairs 3-4 (prep, fp32
-// forward, per-pair policy in one or two launches), one of up to 2048 pairs 2 (prep, the fused per-pair kernel). ----
+// forward, per-pair policy in one or two launches), one of up to 2048 pairs 2 (prep, the fused per-pair kernel).  A
+// double-precision context's call is 3 (prep, fp64 forward, log10 / packed words) -- or, deferred (kSmallDouble), 2 from
+// the combiner (prep, pairhmm_pair_f64_kernel). ----
 int launch_prep(DevCtx* c, const CallPlan& P, const StagedCall& S) {
   const bool ev = c->cfg.record_events != 0;
   if (ev) {
@@ -907,21 +929,28 @@ int finish_call(DevCtx* c, const CallPlan& P, const StagedCall& S) {
   return GKLHIP_OK;
 }
 
+// The kind of a call that is staged for the combiner (SmallCall::kind; the multi call cuts its sets by it): one place
+// for the descriptor and the cut.
+int32_t small_call_kind(const CallPlan& P) {
+  return P.pair_double ? kSmallDouble : P.fused ? kSmallFused : P.n_pairs > kTwoStepFrom ? kSmallTwoStep : kSmallOneLaunch;
+}
+
 // ---- step 5: the deferred exit.  Nothing is launched: the call's descriptor, from the same builders, goes into the
 // staging block (still ours to write) and to the combiner. ----
 void describe_small_call(DevCtx* c, const CallPlan& P, const StagedCall& S, SmallLaunch* out) {
   SmallCall& k = out->call;
   k.prep = prep_args(c, P, S);
   k.prep_grid = prep_grid(k.prep, P);
-  k.f = fwd_args<float>(c, P, S);
+  k.f = P.pair_double ? FwdArgs<float>{} : fwd_args<float>(c, P, S);
   k.d = recompute_args(c, P, S);
   k.q = pair_policy_args(c, P, S);
+  if (P.pair_double) k.q.raw32 = nullptr;   // (kSmallDouble: no fp32 buffer is read or written)
   k.rpl_main = P.rpl_main; k.main_blocks = P.n_main_blocks; k.rows = P.rows; k.n_pairs = (int32_t)P.n_pairs; k.fma = P.fma;
   k.fused = P.fused ? 1 : 0;
   k.speculate = c->speculate_fp64;
   // (a mid-size region: its list is the lane's fail_order, reserved for n_pairs entries by whoever staged it)
-  const bool two_step = !P.fused && P.n_pairs > kTwoStepFrom;
-  k.kind = P.fused ? kSmallFused : two_step ? kSmallTwoStep : kSmallOneLaunch;
+  k.kind = small_call_kind(P);
+  const bool two_step = k.kind == kSmallTwoStep;
   k.flag_grid = two_step ? multi_flag_blocks(k.n_pairs) : 0;
   k.recompute_grid = two_step ? multi_recompute_blocks(k.n_pairs) : 0;
   k.list = two_step ? c->fail_order.as<int32_t>() : nullptr;

@@ -790,7 +790,9 @@ __device__ __forceinline__ bool pair_policy_head(const PairPolicyArgs& q, int64_
   if (lane == 0) atomicAdd(q.count, 1);
   return true;
 }
-template <int RPL, bool FMA>
+// (MARK: the pair was not flagged by a policy in front -- the all-fp64 per-pair kernels, pair_f64_block -- so the lane that
+//  holds the sum also sets its flag and counts it)
+template <int RPL, bool FMA, bool MARK = false>
 __device__ __forceinline__ void pair_policy_recompute(const FwdArgs<double>& a, const PairPolicyArgs& q, int64_t p, int r, int R, int k,
                                                       unsigned char* lds) {
   using Job = WaveJob<double, RPL, FMA>;
@@ -807,6 +809,10 @@ __device__ __forceinline__ void pair_policy_recompute(const FwdArgs<double>& a, 
     const double sum = a.raw[p];
     if (q.mode == kModePackedWords) reinterpret_cast<uint64_t*>(q.out)[p] = packed_word(sum);
     else if (q.mode >= 0) q.out[p] = log10(sum) - q.log10_init_d;
+    if (MARK) {
+      q.used64[p] = 1;
+      atomicAdd(q.count, 1);
+    }
   }
 }
 // One pair per wavefront.  MAXR rows per lane hold the longest read of the call; a pair whose read fits fewer rows per
@@ -896,6 +902,37 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MAXR64 <= 4 
   pair_fused_block<MAXR64, FMA>(f, d, q, (int64_t)blockIdx.x, lds);
 }
 
+// LDS of a recomputing wavefront: the table of the widest variant it may take
+template <int MAXR, bool FMA>
+struct PairRecomputeLds {
+  static constexpr int k2 = WaveJob<double, 2, FMA>::kLdsBytes, k4 = WaveJob<double, 4, FMA>::kLdsBytes, kR = WaveJob<double, MAXR, FMA>::kLdsBytes;
+  static constexpr int bytes = kR > k4 ? (kR > k2 ? kR : k2) : (k4 > k2 ? k4 : k2);
+};
+// Small calls of a double-precision context (gklhip_config.use_double; kSmallDouble): EVERY pair in double precision, one
+// pair per wavefront in one launch behind the preparation -- the fp64 recurrence of the fused kernel's failing pairs with
+// no fp32 recurrence and no policy in front.  The read is alone in the wavefront, rows per lane by its own length; the lane
+// that holds the sum stores the pair's packed word, its flag and counts it.  Nothing here reads or writes an fp32 buffer.
+// One wavefront per block: no __syncthreads() anywhere (the table is the wavefront's own).
+template <int MAXR, bool FMA>
+__device__ __forceinline__ void pair_f64_block(const FwdArgs<double>& d, const PairPolicyArgs& q, int64_t p, unsigned char* lds) {
+  const int r = (int)(p / d.b.n_haps), k = q.hap_sidx[(int)(p - (int64_t)r * d.b.n_haps)];
+  const int R = (int)(d.b.read_off[r + 1] - d.b.read_off[r]);
+  if (MAXR > 2 && R <= 2 * kLanes - 1)      pair_policy_recompute<2, FMA, true>(d, q, p, r, R, k, lds);
+  else if (MAXR > 4 && R <= 4 * kLanes - 1) pair_policy_recompute<4, FMA, true>(d, q, p, r, R, k, lds);
+  else                                      pair_policy_recompute<MAXR, FMA, true>(d, q, p, r, R, k, lds);
+}
+// MAXR = 4: the variant for calls whose reads have at most 255 bases (no kRplF64 code in the kernel: four wavefronts per
+// SIMD, as the narrow fused kernel); MAXR = kRplF64: reads of up to 383 bases, three.
+// A call only gets here deferred (small_call_defers: host finalisation of packed words; recompute_args: no packed output
+// of the forward kernels), said as constants: the device log10 of the other finalisation modes is not compiled in.
+template <int MAXR, bool FMA>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MAXR <= 4 ? 4 : 3))) void pairhmm_pair_f64_kernel(FwdArgs<double> d, PairPolicyArgs q) {
+  __shared__ __attribute__((aligned(16))) unsigned char lds[PairRecomputeLds<MAXR, FMA>::bytes];
+  d.packed_out = nullptr;
+  q.mode = kModePackedWords;
+  pair_f64_block<MAXR, FMA>(d, q, (int64_t)blockIdx.x, lds);
+}
+
 // The same with the fp64 recomputation SPECULATED: two wavefronts per pair, one runs the fp32 recurrence, the other the
 // fp64 one at the same time; the policy then picks.  Five times the fp64 work a call needs (16 % of the pairs fail) --
 // chosen only when the call is alone on the device (one HaplotypeCaller thread sending region after region: the usual
@@ -974,12 +1011,6 @@ __device__ __forceinline__ void pair_flag_block(const PairPolicyArgs& q, int32_t
 __global__ __launch_bounds__(kPairFlagBlock) void pairhmm_pair_flag_kernel(PairPolicyArgs q, int32_t n_pairs, int32_t* list) {
   pair_flag_block(q, n_pairs, list, (int)blockIdx.x);
 }
-// LDS of a recomputing wavefront: the table of the widest variant it may take
-template <int MAXR, bool FMA>
-struct PairRecomputeLds {
-  static constexpr int k2 = WaveJob<double, 2, FMA>::kLdsBytes, k4 = WaveJob<double, 4, FMA>::kLdsBytes, kR = WaveJob<double, MAXR, FMA>::kLdsBytes;
-  static constexpr int bytes = kR > k4 ? (kR > k2 ? kR : k2) : (k4 > k2 ? k4 : k2);
-};
 // Block `block` of the `grid` blocks that recompute one call's list: entries block, block + grid, ... (every entry of
 // the list once over the grid); shared with pair_recompute_multi_kernel.
 template <int MAXR, bool FMA>

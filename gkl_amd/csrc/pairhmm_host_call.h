@@ -107,7 +107,9 @@ struct SmallCombiner {
 
   int launch_single(const SmallCall& k, hipStream_t s, bool alone) {
     hipLaunchKernelGGL(prep_kernel, dim3((unsigned)k.prep_grid), dim3(kPrepBlock), 0, s, k.prep);
-    if (k.fused) {
+    if (k.kind == kSmallDouble) {
+      launch_pair_f64(k.d, k.q, k.rows, k.fma, k.n_pairs, s);
+    } else if (k.fused) {
       launch_pair_fused(k.f, k.d, k.q, k.rows, k.fma, k.n_pairs, s, alone && k.speculate);
     } else {
       launch_main_f32(k.f, k.rpl_main, k.fma, k.main_blocks, s);
@@ -149,6 +151,14 @@ struct SmallCombiner {
         else if (rows == 4) hipLaunchKernelGGL((pair_recompute_multi_kernel<false, 4>), grid, block, 0, sl.stream, mr);
         else                hipLaunchKernelGGL((pair_recompute_multi_kernel<false, kRplF64>), grid, block, 0, sl.stream, mr);
       }
+    } else if (calls[0]->call.kind == kSmallDouble) {   // calls of double-precision contexts: one launch, every pair in fp64
+      bool narrow = true;   // as below
+      for (int i = 0; i < n; i++) narrow = narrow && calls[i]->call.rows <= 4;
+      const dim3 grid((unsigned)mq.begin[n]), block(64);
+      if (narrow && fma)  hipLaunchKernelGGL((pair_f64_multi_kernel<true, 4>), grid, block, 0, sl.stream, mq);
+      else if (narrow)    hipLaunchKernelGGL((pair_f64_multi_kernel<false, 4>), grid, block, 0, sl.stream, mq);
+      else if (fma)       hipLaunchKernelGGL((pair_f64_multi_kernel<true, kRplF64>), grid, block, 0, sl.stream, mq);
+      else                hipLaunchKernelGGL((pair_f64_multi_kernel<false, kRplF64>), grid, block, 0, sl.stream, mq);
     } else if (calls[0]->call.fused) {  // (every call of a set is of one kind: a leader only takes calls like its own, a multi call cuts its sets by kind)
       bool narrow = true;   // reads of at most 255 bases in every call of the set: the four-wavefronts-per-SIMD variant
       for (int i = 0; i < n; i++) narrow = narrow && calls[i]->call.rows <= 4;
@@ -258,7 +268,8 @@ struct SmallCombiner {
           continue;
         }
       }
-      // lead: this call first, then the waiting calls of the same arithmetic mode
+      // lead: this call first, then the waiting calls of the same arithmetic mode and kind (a set never mixes the fused
+      // and the one-launch fp32 calls, nor either with the calls of a double-precision context)
       const int64_t t_lead = now_ns();
       ns_queued += t_lead - t_in;
       const SmallLaunch* calls[kCombineMax];
@@ -267,7 +278,7 @@ struct SmallCombiner {
       calls[n++] = &mine;
       for (auto it = queue.begin(); it != queue.end();) {
         if (*it == &t) { it = queue.erase(it); continue; }
-        if (n < kCombineMax && (*it)->sl->call.fma == mine.call.fma && (*it)->sl->call.fused == mine.call.fused) {
+        if (n < kCombineMax && (*it)->sl->call.fma == mine.call.fma && (*it)->sl->call.kind == mine.call.kind) {
           (*it)->state = 4;  // taken: its owner keeps sleeping until this thread reports the launch (or the end)
           ns_queued += t_lead - (*it)->t_in;
           others[n - 1] = *it;
@@ -441,8 +452,8 @@ int dev_compute_host_multi(DevCtx* c, std::vector<DevCtx*>& lanes, std::vector<M
   auto fail_region = [](MultiRegion& r, int rc) { r.rc = rc; r.err = g_err; };
   enum { kNone, kSmall, kMid };
   // Plans region i on lane `li` and -- unless plan_only -- stages it there.  kNone: no set for this region (it does not
-  // qualify: r.alone; it failed: r.rc).  *fused: the kind of a small region that qualifies.
-  auto stage = [&](int i, int li, bool plan_only, uint8_t* fused) -> int {
+  // qualify: r.alone; it failed: r.rc).  *kind_out: the kind of a small region that qualifies (multi_cut_sets cuts by it).
+  auto stage = [&](int i, int li, bool plan_only, uint8_t* kind_out) -> int {
     MultiRegion& r = R[(size_t)i];
     const gklhip_batch* hb = r.hb;
     if (on_device || !deferral_offered(inputs_inline(hb))) { r.alone = true; return kNone; }
@@ -458,7 +469,7 @@ int dev_compute_host_multi(DevCtx* c, std::vector<DevCtx*>& lanes, std::vector<M
     const bool mid = !P.defers && mid_call_shares(ln, P);
     if (!P.defers && !mid) { r.alone = true; return kNone; }
     P.defers = true;   // (a mid-size region too is staged for the combiner: see stage_call)
-    *fused = P.fused ? 1 : 0;
+    *kind_out = (uint8_t)small_call_kind(P);
     const int what = mid ? kMid : kSmall;
     if (plan_only) return what;
     int rc = GKLHIP_OK;

@@ -22,8 +22,9 @@ constexpr int kMultiMax = 64;     // calls per set of launches (what MultiArgs h
 constexpr int kCombineMax = 16;   // ... of which a leader of concurrent callers takes at most this many (SmallCombiner::run)
 
 // The set-cutting rule of gklhip_compute_multi.  The regions that qualify for a shared set (the single call would defer
-// them: small_call_defers) form runs in input order: a run ends where the next qualifying region is of the other kind
-// (fused per-pair kernel or not); regions that do not qualify run alone and do not interrupt a run.  A run of m regions
+// them: small_call_defers) form runs in input order: a run ends where the next qualifying region is of another kind
+// (`kind`: any values -- the fused per-pair kernel, the one-launch policy, the all-fp64 per-pair kernel of a
+// double-precision context); regions that do not qualify run alone and do not interrupt a run.  A run of m regions
 // is cut into ceil(m / kMultiMax) sets of consecutive regions whose sizes differ by at most one -- 65 regions leave as
 // 33 + 32, not as 64 and one region that pays a set of launches alone.
 // set_of[k]: the set of region k, numbered from 0 in input order, or -1 for a region that does not qualify.  Returns the

@@ -161,10 +161,15 @@ int gklhip_compute(gklhip_ctx* ctx, const gklhip_batch* host_batch, double* out_
  * the rest still run.  A region with n_reads * n_haps == 0 succeeds and writes nothing.  A HIP failure of a shared set of
  * launches fails every region in that set (after its stream has been drained).
  * Which regions share a set: SMALL ones, those the single call hands to the small-call combiner (inputs of at most 1 MB,
- * at most 2048 pairs, no read of 384 bases or more, host finalisation, no use_double, no record_events), and MID-SIZE
+ * at most 2048 pairs, no read of 384 bases or more, host finalisation, no record_events), and MID-SIZE
  * ones, for which all of that holds except the size: 2049 to 65 536 pairs.  The two are cut apart.  The small regions,
  * in input order, are cut into sets of one kind (with rows_per_lane == 0: the fused per-pair kernel) of at most 64
- * regions.  The mid-size regions share sets among themselves only -- prep, the packed fp32 pass, and the per-pair
+ * regions.  Small calls come in kinds, and a set -- of a multi call or of concurrent callers -- holds one kind only: the
+ * fused per-pair kernel, the fp32 pass + per-pair policy (rows_per_lane != 0), and, on a use_double context, the
+ * all-fp64 per-pair kernel (every pair in double precision, one pair per wavefront; its size limit is the same 2048
+ * pairs, kSmallDoublePairs; rows_per_lane, an fp32 setting, does not matter there).  A context has one precision, so the
+ * regions of one multi call never mix; callers on contexts of different precision never share a set.  MID-SIZE regions
+ * are fp32-context regions only: a use_double region of more than 2048 pairs runs alone.  The mid-size regions share sets among themselves only -- prep, the packed fp32 pass, and the per-pair
  * policy in two launches, once for the whole set -- in input order, at most 64 per set, and they need company of their
  * own kind: ONE mid-size region in a call is no set and runs alone, as before.  Each region of a set is planned and staged
  * exactly as a single call is, on one of up to 64 staging lanes of the context (made on first use, given back by
@@ -237,7 +242,8 @@ int gklhip_measure_issue_ceiling(gklhip_ctx* ctx, int use_double, double ms_budg
 /* Diagnostics: concurrent small host-buffer calls (a GATK region each, from several threads or JNI slots) are launched
  * together when they meet on the device (GKL_HIP_COMBINE).  Process-wide counts for `device`:
  * out[0] calls that took the small-call path, out[1] those of them launched together with other calls, out[2] sets of
- * launches issued.  reset != 0 zeroes the counts after reading. */
+ * launches issued.  reset != 0 zeroes the counts after reading.  The qualifying calls of use_double contexts are small
+ * calls too and are counted like the fp32 ones (they used to take the general pass and count nothing). */
 int gklhip_small_call_counts(int device, int64_t out[3], int reset);
 
 /* Gives back what an IDLE context holds only for speed: the streams it made for big calls (every stream is a hardware

@@ -4,8 +4,10 @@ call against K consecutive gklhip_compute calls on the same context: median host
 two arms alternating in one process.  Both arms are made on prebuilt arguments: nothing but the C ABI is timed.  Checks that
 both give the same bytes and reports how many sets of launches the multi call took (gklhip_small_call_counts: calls,
 combined calls, sets).  A mid-size shape (400x40, 250x128, 1000x50) measures the mid-size sets of docs/NOTES.md 69.
+--double: the same on a double-precision context (gklhip_config.use_double, GATK's --native-pair-hmm-use-double-precision):
+docs/NOTES.md 70.  --lib FILE: development only -- another build of libgklhip_pairhmm.so (A/B against an earlier commit's, same process layout).
 
-usage: tools/pairhmm_multi_timing.py [--region 100x10] [--counts 1,2,4,8,16,64] [--reps 30] [--warmup 10] [--out FILE]"""
+usage: tools/pairhmm_multi_timing.py [--double] [--region 100x10] [--counts 1,2,4,8,16,64] [--reps 30] [--warmup 10] [--lib FILE] [--out FILE]"""
 import argparse
 import ctypes as C
 import json
@@ -26,6 +28,8 @@ def main():
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--out", default="")
+    ap.add_argument("--double", action="store_true", help="a use_double context")
+    ap.add_argument("--lib", default="", help="the libgklhip_pairhmm.so to load (default: the tree's)")
     a = ap.parse_args()
     if a.reps < 30:
         raise SystemExit("at least 30 repetitions")
@@ -37,9 +41,11 @@ def main():
         raise SystemExit("--region wants at least one read and one haplotype")
     from gkl_amd import native
     from gkl_amd.synth import make_batch
-    ctx = native.PairHmmContext(device=0)
+    if a.lib:
+        native.LIB_PATH = os.path.abspath(a.lib)   # (before the first load: the counters below come from the same library)
+    ctx = native.PairHmmContext(device=0, use_double=a.double)
     lib, h = ctx.lib, ctx.handle
-    result = {"region": f"hc {n_reads} x {n_haps}", "reps": a.reps, "warmup": a.warmup, "rows": []}
+    result = {"region": f"hc {n_reads} x {n_haps}", "use_double": bool(a.double), "lib": a.lib or "tree", "reps": a.reps, "warmup": a.warmup, "rows": []}
     for K in (int(x) for x in a.counts.split(",")):
         batches = [make_batch("hc", n_reads, n_haps, seed=1000 + k) for k in range(K)]
         keep, cbs = [], (native.CBatch * K)()
