@@ -117,12 +117,15 @@ struct SmallCall {
   int32_t speculate;  // host side only: the context asked for the fp64 pass beside the fp32 one when the call runs alone
   // a mid-size call (kSmallTwoStep): the policy in two launches -- the list of the pairs it flags (n_pairs entries, the
   // call's own; its counter is q.count) and the call's blocks in the flag and the recomputation launch
-  int32_t kind;   // kSmallOneLaunch / kSmallFused / kSmallTwoStep / kSmallDouble: calls of one kind share a set
+  int32_t kind;   // kSmallOneLaunch / kSmallFused / kSmallTwoStep / kSmallDouble / kSmallDoubleStream: calls of one kind share a set
   int32_t flag_grid, recompute_grid;
   int32_t* list;
 };
 // (kSmallDouble: a small call of a double-precision context -- every pair through pair_f64_block; `f` and q.raw32 are unset)
-enum : int32_t { kSmallOneLaunch = 0, kSmallFused = 1, kSmallTwoStep = 2, kSmallDouble = 3 };
+// (kSmallDoubleStream: a mid-size region of a double-precision context -- the packed fp64 streaming pass over `d`, the
+//  grouped stream of the general pass, on main_blocks blocks, then its packed words on flag_grid blocks; `f`, q.raw32 and
+//  `list` are unset)
+enum : int32_t { kSmallOneLaunch = 0, kSmallFused = 1, kSmallTwoStep = 2, kSmallDouble = 3, kSmallDoubleStream = 4 };
 // A set holds up to kMultiMax (64) calls, all in the kernel arguments (776 bytes; pairhmm_multi_sets.h: the limits, the
 // prefix sums and the lookup, shared with the host).
 struct MultiArgs {
@@ -222,6 +225,48 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) void pa
   PairPolicyArgs q = c->q;
   q.mode = kModePackedWords;
   pair_recompute_block<MAXR, FMA>(d, q, c->list, multi_local(m.begin, r, (int)blockIdx.x), c->recompute_grid, lds);
+}
+
+// Mid-size regions of a double-precision context (kSmallDoubleStream) of a set: the packed fp64 streaming pass and its
+// packed words, behind prep_multi_kernel.  Region k owns main_blocks blocks of the streaming launch -- its plan's grid,
+// chunk_stride x groups: from 64 chunks on that holds up to 7 padded blocks per group, which leave at once in
+// fwd_stream_block as they do in the single kernel -- and multi_flag_blocks(n_pairs_k) blocks of the finalisation.
+// kRplJobs: kRplF64Jobs (as the single kernel has for double: two wavefronts per SIMD).
+// A pointer that arrives in a kernel ARGUMENT is a global pointer to the compiler; one read from a descriptor in memory
+// is a generic one: its loads are flat loads with a 64-bit address in a VGPR pair each, where the single kernel has
+// global loads off an SGPR base.  In a kernel at the 256-VGPR limit that was the difference between 64 / 56 and 132 bytes
+// of scratch per lane.  global_ptr says what the pointer is: its bits as a pointer of the global address space (through
+// an integer: the plain cast there and back is folded away before the address-space inference sees it).
+template <typename P>
+__device__ __forceinline__ P* global_ptr(P* p) { return (P*)(__attribute__((address_space(1))) P*)(uintptr_t)p; }
+template <bool FMA, int kRplJobs>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void fwd_stream_f64_multi_kernel(MultiArgs m) {
+  __shared__ __attribute__((aligned(16))) unsigned char lds[WaveJob<double, kRplJobs, FMA>::kLdsBytes];
+  const int r = multi_find(m, (int)blockIdx.x);
+  const SmallCall* c = m.call[r];
+  const int block = multi_local(m.begin, r, (int)blockIdx.x);
+  // What every region of such a set has in common, as a constant (double_mid_shares: host finalisation of packed words,
+  // which finalize64_multi_kernel stores): no packed output of the forward kernel -- WaveJob::run keeps the whole-job asm
+  // programs only without one.
+  FwdArgs<double> a = c->d;
+  a.packed_out = nullptr;
+  a.b.read_bases = global_ptr(a.b.read_bases); a.b.read_quals = global_ptr(a.b.read_quals); a.b.ins = global_ptr(a.b.ins);
+  a.b.del = global_ptr(a.b.del); a.b.gcp = global_ptr(a.b.gcp); a.b.read_off = global_ptr(a.b.read_off);
+  a.tab.ph2pr = global_ptr(a.tab.ph2pr); a.tab.div3 = global_ptr(a.tab.div3); a.tab.mm = global_ptr(a.tab.mm);
+  a.stream = global_ptr(a.stream); a.hap_len = global_ptr(a.hap_len); a.hap_pos = global_ptr(a.hap_pos);
+  a.hap_orig = global_ptr(a.hap_orig); a.y0 = global_ptr(a.y0); a.hap_has_n = global_ptr(a.hap_has_n);
+  a.groups = global_ptr(a.groups); a.chunk_lanes = global_ptr(a.chunk_lanes); a.raw = global_ptr(a.raw);
+  fwd_stream_block<double, kRplJobs, FMA>(a, block, lds);
+}
+// ... and what finalize64_kernel(a, all_pairs = 1) does in kModePacked, a thread per pair: the flag and the packed word of
+// the fp64 sum in the region's pinned output (no device log10 here: a region only gets here with host finalisation).
+__global__ __launch_bounds__(kFlagBlock) void finalize64_multi_kernel(MultiArgs m) {
+  const int r = multi_find(m, (int)blockIdx.x);
+  const SmallCall* c = m.call[r];
+  const int p = multi_local(m.begin, r, (int)blockIdx.x) * kFlagBlock + (int)threadIdx.x;
+  if (p >= c->n_pairs) return;
+  c->q.used64[p] = 1;
+  reinterpret_cast<uint64_t*>(c->q.out)[p] = packed_word(c->d.raw[p]);
 }
 
 constexpr int kModePacked = kModePackedWords;  // FinalizeArgs::mode: `out` receives packed raw sums (kPackedF32Tag, pairhmm_fwd_kernel.h)

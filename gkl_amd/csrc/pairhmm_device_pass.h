@@ -382,6 +382,13 @@ bool mid_call_shares(const DevCtx* c, const CallPlan& P) {
   return deferral_offered(P.inline_host) && P.pull && c->cfg.record_events == 0 && P.per_pair && !P.fused && c->plan.long_reads.empty() &&
          P.finalize_mode == kModePacked && c->plan.n_chunks > 0 && P.n_pairs > kTwoStepFrom && P.n_pairs <= kDirectPairs;
 }
+// ... and a mid-size region of a double-precision context (kSmallDoubleStream): the same of the all-fp64 pass.  No read
+// too long for a chunk of the packed fp64 pass (639 bases at kRplF64Jobs rows per lane: the limit is the chunk, not the
+// per-pair kernel's 383), a single-device context (a multi-device one keeps the general pass, as for kSmallDouble).
+bool double_mid_shares(const DevCtx* c, const CallPlan& P) {
+  return deferral_offered(P.inline_host) && P.pull && c->cfg.record_events == 0 && P.use_double && !c->multi_device && c->plan.long_reads.empty() &&
+         P.finalize_mode == kModePacked && c->plan.n_chunks > 0 && P.n_pairs > kTwoStepFrom && P.n_pairs <= kDirectPairs;
+}
 // `load` of pick_f32_rpl: 1 for a call that is not offered deferral.  (About half of the calls inside the library are on
 // the device at any moment, the others are being staged or finalised: 16 callers of 100 x 10 regions keep the 4-row
 // kernel -- the 8-row one needs three wavefronts per SIMD to pay, tools/small_scaling.py -- and 32 callers get the 8-row one.)
@@ -762,7 +769,8 @@ PlanArgs plan_args(const DevCtx* c, const CallPlan& P, const StagedCall& S) {
 // of the kept pairs on a side stream in the device finalisation modes), a call of up to 65 536 pairs 3-4 (prep, fp32
 // forward, per-pair policy in one or two launches), one of up to 2048 pairs 2 (prep, the fused per-pair kernel).  A
 // double-precision context's call is 3 (prep, fp64 forward, log10 / packed words) -- or, deferred (kSmallDouble), 2 from
-// the combiner (prep, pairhmm_pair_f64_kernel). ----
+// the combiner (prep, pairhmm_pair_f64_kernel); its mid-size regions of one multi call (kSmallDoubleStream) take the same 3
+// once per set of up to 64 (SmallCombiner::launch_multi). ----
 int launch_prep(DevCtx* c, const CallPlan& P, const StagedCall& S) {
   const bool ev = c->cfg.record_events != 0;
   if (ev) {
@@ -932,6 +940,7 @@ int finish_call(DevCtx* c, const CallPlan& P, const StagedCall& S) {
 // The kind of a call that is staged for the combiner (SmallCall::kind; the multi call cuts its sets by it): one place
 // for the descriptor and the cut.
 int32_t small_call_kind(const CallPlan& P) {
+  if (P.use_double && P.n_pairs > kSmallDoublePairs) return kSmallDoubleStream;
   return P.pair_double ? kSmallDouble : P.fused ? kSmallFused : P.n_pairs > kTwoStepFrom ? kSmallTwoStep : kSmallOneLaunch;
 }
 
@@ -941,17 +950,19 @@ void describe_small_call(DevCtx* c, const CallPlan& P, const StagedCall& S, Smal
   SmallCall& k = out->call;
   k.prep = prep_args(c, P, S);
   k.prep_grid = prep_grid(k.prep, P);
-  k.f = P.pair_double ? FwdArgs<float>{} : fwd_args<float>(c, P, S);
-  k.d = recompute_args(c, P, S);
+  k.kind = small_call_kind(P);
+  // (kSmallDoubleStream: the grouped stream of the general all-fp64 pass, not the flat one of the per-pair kernels)
+  const bool all_double = k.kind == kSmallDouble || k.kind == kSmallDoubleStream;
+  k.f = all_double ? FwdArgs<float>{} : fwd_args<float>(c, P, S);
+  k.d = k.kind == kSmallDoubleStream ? fwd_args<double>(c, P, S) : recompute_args(c, P, S);
   k.q = pair_policy_args(c, P, S);
-  if (P.pair_double) k.q.raw32 = nullptr;   // (kSmallDouble: no fp32 buffer is read or written)
+  if (all_double) k.q.raw32 = nullptr;   // (no fp32 buffer is read or written)
   k.rpl_main = P.rpl_main; k.main_blocks = P.n_main_blocks; k.rows = P.rows; k.n_pairs = (int32_t)P.n_pairs; k.fma = P.fma;
   k.fused = P.fused ? 1 : 0;
   k.speculate = c->speculate_fp64;
   // (a mid-size region: its list is the lane's fail_order, reserved for n_pairs entries by whoever staged it)
-  k.kind = small_call_kind(P);
   const bool two_step = k.kind == kSmallTwoStep;
-  k.flag_grid = two_step ? multi_flag_blocks(k.n_pairs) : 0;
+  k.flag_grid = two_step || k.kind == kSmallDoubleStream ? multi_flag_blocks(k.n_pairs) : 0;
   k.recompute_grid = two_step ? multi_recompute_blocks(k.n_pairs) : 0;
   k.list = two_step ? c->fail_order.as<int32_t>() : nullptr;
   memcpy(S.hs + P.L.desc, &k, sizeof k);

@@ -151,6 +151,12 @@ struct SmallCombiner {
         else if (rows == 4) hipLaunchKernelGGL((pair_recompute_multi_kernel<false, 4>), grid, block, 0, sl.stream, mr);
         else                hipLaunchKernelGGL((pair_recompute_multi_kernel<false, kRplF64>), grid, block, 0, sl.stream, mr);
       }
+    } else if (calls[0]->call.kind == kSmallDoubleStream) {   // mid-size regions of a double-precision context: the packed fp64 pass, then its packed words
+      for (int i = 0; i < n; i++) pair_blocks[i] = calls[i]->call.flag_grid;
+      multi_begin(pair_blocks, n, mq.begin);
+      if (fma) hipLaunchKernelGGL((fwd_stream_f64_multi_kernel<true, kRplF64Jobs>), dim3((unsigned)mf.begin[n]), dim3(64), 0, sl.stream, mf);
+      else     hipLaunchKernelGGL((fwd_stream_f64_multi_kernel<false, kRplF64Jobs>), dim3((unsigned)mf.begin[n]), dim3(64), 0, sl.stream, mf);
+      hipLaunchKernelGGL(finalize64_multi_kernel, dim3((unsigned)mq.begin[n]), dim3(kFlagBlock), 0, sl.stream, mq);
     } else if (calls[0]->call.kind == kSmallDouble) {   // calls of double-precision contexts: one launch, every pair in fp64
       bool narrow = true;   // as below
       for (int i = 0; i < n; i++) narrow = narrow && calls[i]->call.rows <= 4;
@@ -433,7 +439,7 @@ struct MultiRegion {
 // The regions that the single-call path would defer are staged on the context's lanes -- plan_call, stage_call and
 // describe_small_call, exactly as a single call stages itself --, cut into sets (multi_cut_sets) and leave set by set through
 // the combiner's launches; each region's packed words are then finalised on the host as a single call's are.  Mid-size
-// regions (mid_call_shares) are staged the same way and cut among themselves (multi_cut_mid_sets): two or more of them
+// regions (mid_call_shares; a double-precision context's: double_mid_shares) are staged the same way and cut among themselves (multi_cut_mid_sets): two or more of them
 // share sets of their own, one alone is no set.  Every other region comes back marked `alone`.
 // Up to kMultiMax regions are staged first and cut afterwards; a longer list is planned twice: once to learn which regions
 // qualify (the cut needs that of the whole list), once more when the region's set is staged.
@@ -451,9 +457,9 @@ int dev_compute_host_multi(DevCtx* c, std::vector<DevCtx*>& lanes, std::vector<M
   std::vector<int> owner((size_t)kMultiMax, -1);        // by lane: the region whose raw sums it holds
   auto fail_region = [](MultiRegion& r, int rc) { r.rc = rc; r.err = g_err; };
   enum { kNone, kSmall, kMid };
-  // Plans region i on lane `li` and -- unless plan_only -- stages it there.  kNone: no set for this region (it does not
-  // qualify: r.alone; it failed: r.rc).  *kind_out: the kind of a small region that qualifies (multi_cut_sets cuts by it).
-  auto stage = [&](int i, int li, bool plan_only, uint8_t* kind_out) -> int {
+  // Plans region i on lane `li`.  kNone: no set for this region (it does not qualify: r.alone; it failed: r.rc).
+  // *kind_out: the kind of a small region that qualifies (multi_cut_sets cuts by it).
+  auto plan = [&](int i, int li, CallPlan* plan_out, uint8_t* kind_out) -> int {
     MultiRegion& r = R[(size_t)i];
     const gklhip_batch* hb = r.hb;
     if (on_device || !deferral_offered(inputs_inline(hb))) { r.alone = true; return kNone; }
@@ -464,27 +470,38 @@ int dev_compute_host_multi(DevCtx* c, std::vector<DevCtx*>& lanes, std::vector<M
       lanes.push_back(ln);
     }
     DevCtx* ln = lanes[(size_t)li];
-    CallPlan P;
+    CallPlan& P = *plan_out;
     plan_call(ln, hb, kModePacked, true, true, call_load(true), &P);
-    const bool mid = !P.defers && mid_call_shares(ln, P);
+    const bool mid = !P.defers && (mid_call_shares(ln, P) || double_mid_shares(ln, P));
     if (!P.defers && !mid) { r.alone = true; return kNone; }
     P.defers = true;   // (a mid-size region too is staged for the combiner: see stage_call)
     *kind_out = (uint8_t)small_call_kind(P);
-    const int what = mid ? kMid : kSmall;
-    if (plan_only) return what;
+    return mid ? kMid : kSmall;
+  };
+  // ... and stages it there, from that plan (nothing else was planned on the lane in between).  false: it failed (r.rc).
+  auto put = [&](int i, int li, const CallPlan& P, bool mid) -> bool {
+    MultiRegion& r = R[(size_t)i];
+    const gklhip_batch* hb = r.hb;
+    DevCtx* ln = lanes[(size_t)li];
     int rc = GKLHIP_OK;
     void* pin_out = nullptr;
     if (owner[(size_t)li] >= 0) R[(size_t)owner[(size_t)li]].lane = -1;   // an earlier set's region: its raw sums go now
     owner[(size_t)li] = -1;
     rc = ln->res_pin.reserve((size_t)hb->n_reads * (size_t)hb->n_haps * 8);
     if (rc == GKLHIP_OK && hipHostGetDevicePointer(&pin_out, ln->res_pin.p, 0) != hipSuccess) { (void)hipGetLastError(); rc = fail(GKLHIP_ERR_HIP, "hipHostGetDevicePointer failed"); }
-    if (rc != GKLHIP_OK) { fail_region(r, rc); return kNone; }
+    if (rc != GKLHIP_OK) { fail_region(r, rc); return false; }
     StagedCall S;   // (the regions of a multi call are staged on lanes that have no stream of their own)
-    if ((rc = stage_call(ln, hb, P, static_cast<double*>(pin_out), c->stream, &S))) { fail_region(r, rc); return kNone; }
-    if (mid && (rc = ln->fail_order.reserve((size_t)P.n_pairs * 4))) { fail_region(r, rc); return kNone; }   // the list of its flagged pairs
+    if ((rc = stage_call(ln, hb, P, static_cast<double*>(pin_out), c->stream, &S))) { fail_region(r, rc); return false; }
+    if (mid && !P.use_double && (rc = ln->fail_order.reserve((size_t)P.n_pairs * 4))) { fail_region(r, rc); return false; }   // the list of its flagged pairs
     describe_small_call(ln, P, S, &staged[(size_t)li]);
     owner[(size_t)li] = i; r.lane = li;
-    return what;
+    return true;
+  };
+  auto stage = [&](int i, int li, bool plan_only, uint8_t* kind_out) -> int {
+    CallPlan P;
+    const int what = plan(i, li, &P, kind_out);
+    if (what == kNone || plan_only) return what;
+    return put(i, li, P, what == kMid) ? what : kNone;
   };
   // A region that was staged and then finds no set: through the single-call path after all.
   auto run_alone = [&](int i) {
@@ -493,8 +510,30 @@ int dev_compute_host_multi(DevCtx* c, std::vector<DevCtx*>& lanes, std::vector<M
     r.lane = -1; r.alone = true;
   };
   std::vector<uint8_t> qualifies((size_t)n), mid((size_t)n), kind((size_t)n);
+  // A double-precision context's first mid-size region is held back, planned, until a second one shows up: one alone is no
+  // set, and a call with ONE such region costs what it did before these regions shared (its plan here, then the single-call
+  // path) -- staged and dropped it measured 0.01 - 0.03 ms more (400 x 40: 0.39 -> 0.41 ms).  Its lane keeps the plan.
+  int held = -1;
+  CallPlan held_plan;
+  bool any_mid = false;
   for (int i = 0; i < n; i++) {
-    const int what = stage(i, stage_first ? i : 0, !stage_first, &kind[(size_t)i]);
+    int what;
+    if (!stage_first) {
+      what = stage(i, 0, true, &kind[(size_t)i]);
+    } else {
+      CallPlan P;
+      what = plan(i, i, &P, &kind[(size_t)i]);
+      if (what == kMid && P.use_double && !any_mid) {
+        held = i; held_plan = P;
+      } else if (what != kNone) {
+        if (what == kMid && held >= 0) {
+          if (!put(held, held, held_plan, true)) mid[(size_t)held] = 0;
+          held = -1;
+        }
+        if (!put(i, i, P, what == kMid)) what = kNone;
+      }
+      any_mid = any_mid || what == kMid;
+    }
     qualifies[(size_t)i] = what == kSmall ? 1 : 0;
     mid[(size_t)i] = what == kMid ? 1 : 0;
   }

@@ -168,9 +168,10 @@ int gklhip_compute(gklhip_ctx* ctx, const gklhip_batch* host_batch, double* out_
  * fused per-pair kernel, the fp32 pass + per-pair policy (rows_per_lane != 0), and, on a use_double context, the
  * all-fp64 per-pair kernel (every pair in double precision, one pair per wavefront; its size limit is the same 2048
  * pairs, kSmallDoublePairs; rows_per_lane, an fp32 setting, does not matter there).  A context has one precision, so the
- * regions of one multi call never mix; callers on contexts of different precision never share a set.  MID-SIZE regions
- * are fp32-context regions only: a use_double region of more than 2048 pairs runs alone.  The mid-size regions share sets among themselves only -- prep, the packed fp32 pass, and the per-pair
- * policy in two launches, once for the whole set -- in input order, at most 64 per set, and they need company of their
+ * regions of one multi call never mix; callers on contexts of different precision never share a set.  The mid-size
+ * regions share sets among themselves only -- prep, the packed fp32 pass, and the per-pair policy in two launches, once
+ * for the whole set; on a use_double context prep, the packed fp64 pass and the packed words of its sums: three launches,
+ * and there the read-length limit is the chunk of that pass, 639 bases -- in input order, at most 64 per set, and they need company of their
  * own kind: ONE mid-size region in a call is no set and runs alone, as before.  Each region of a set is planned and staged
  * exactly as a single call is, on one of up to 64 staging lanes of the context (made on first use, given back by
  * gklhip_release_idle), and a set leaves through the combiner's launches: it waits for a flight slot like the set of any

@@ -5,7 +5,7 @@ two arms alternating in one process.  Both arms are made on prebuilt arguments: 
 both give the same bytes and reports how many sets of launches the multi call took (gklhip_small_call_counts: calls,
 combined calls, sets).  A mid-size shape (400x40, 250x128, 1000x50) measures the mid-size sets of docs/NOTES.md 69.
 --double: the same on a double-precision context (gklhip_config.use_double, GATK's --native-pair-hmm-use-double-precision):
-docs/NOTES.md 70.  --lib FILE: development only -- another build of libgklhip_pairhmm.so (A/B against an earlier commit's, same process layout).
+docs/NOTES.md 70; with a mid-size --region: the mid-size fp64 sets of docs/NOTES.md 71.  --lib FILE: development only -- another build of libgklhip_pairhmm.so (A/B against an earlier commit's, same process layout).
 
 usage: tools/pairhmm_multi_timing.py [--double] [--region 100x10] [--counts 1,2,4,8,16,64] [--reps 30] [--warmup 10] [--lib FILE] [--out FILE]"""
 import argparse
