@@ -316,6 +316,7 @@ static int compute_device_impl(gklhip_ctx* c, const gklhip_batch* dev_batch, dou
       for (DevCtx* d : c->dev) {
         DevCtx* twin = nullptr;
         if (dev_init(d->cfg, d->device, ndev, &twin) != GKLHIP_OK) break;   // e.g. out of memory: stay with one set
+        twin->small_read_limit = d->small_read_limit;
         made.push_back(twin);
       }
       bool ok = made.size() == c->dev.size();
@@ -387,6 +388,7 @@ static int compute_locked(gklhip_ctx* c, const gklhip_batch* hb, double* out_hos
       int ndev = 0;
       HIP_TRY(hipGetDeviceCount(&ndev));
       if ((rc = dev_init(c->dev[0]->cfg, c->dev[0]->device, ndev, &twin))) { c->host_shards = (int)c->host_dev.size(); break; }  // e.g. out of memory: stay whole
+      twin->small_read_limit = c->dev[0]->small_read_limit;
       c->twins.push_back(twin);
       c->host_dev.push_back(twin);
     }

@@ -158,11 +158,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void fw
   else if (rpl == 4) fwd_stream_block<float, 4, FMA>(a, block, lds);
   else               fwd_stream_block<float, kRplF32, FMA>(a, block, lds);
 }
-template <bool FMA, int kRplF64>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) void pair_policy_multi_kernel(MultiArgs m) {
+template <bool FMA, int kRplF64>   // kRplF64: rows per lane of the set's longest read (kRplF64, or kRplPair8 with a read of 384 bases or more)
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kRplF64 <= 6 ? 3 : 2))) void pair_policy_multi_kernel(MultiArgs m) {
   __shared__ __attribute__((aligned(16))) unsigned char lds[WaveJob<double, kRplF64, FMA>::kLdsBytes];
   static_assert(WaveJob<double, 2, FMA>::kLdsBytes <= WaveJob<double, kRplF64, FMA>::kLdsBytes &&
-                WaveJob<double, 4, FMA>::kLdsBytes <= WaveJob<double, kRplF64, FMA>::kLdsBytes, "LDS of the widest job");
+                WaveJob<double, 4, FMA>::kLdsBytes <= WaveJob<double, kRplF64, FMA>::kLdsBytes &&
+                (kRplF64 <= 6 || WaveJob<double, 6, FMA>::kLdsBytes <= WaveJob<double, kRplF64, FMA>::kLdsBytes), "LDS of the widest job");
   const int r = multi_find(m, (int)blockIdx.x);
   const SmallCall* c = m.call[r];
   const int64_t p = multi_local(m.begin, r, (int)blockIdx.x);
@@ -172,7 +173,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) void pa
 }
 
 template <bool FMA, int kRplF64>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kRplF64 <= 4 ? 4 : 3))) void pair_fused_multi_kernel(MultiArgs m) {
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(pair_waves_per_eu(kRplF64)))) void pair_fused_multi_kernel(MultiArgs m) {
   __shared__ __attribute__((aligned(16))) unsigned char lds[PairFusedLds<kRplF64, FMA>::bytes];
   const int r = multi_find(m, (int)blockIdx.x);
   const SmallCall* c = m.call[r];
@@ -185,9 +186,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kRplF64 <= 4
 
 // Small calls of double-precision contexts (kSmallDouble) of a set: every pair of every call in double precision, one
 // pair per block (pair_f64_block).  MAXR: rows per lane of the set's longest read (4: no read of 256 bases or more in the
-// set, the four-wavefronts-per-SIMD form; kRplF64 otherwise).
+// set, the four-wavefronts-per-SIMD form; kRplF64 up to 383 bases; kRplPair8 up to 511).
 template <bool FMA, int MAXR>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MAXR <= 4 ? 4 : 3))) void pair_f64_multi_kernel(MultiArgs m) {
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(pair_waves_per_eu(MAXR)))) void pair_f64_multi_kernel(MultiArgs m) {
   __shared__ __attribute__((aligned(16))) unsigned char lds[PairRecomputeLds<MAXR, FMA>::bytes];
   const int r = multi_find(m, (int)blockIdx.x);
   const SmallCall* c = m.call[r];
@@ -211,8 +212,8 @@ __global__ __launch_bounds__(kPairFlagBlock) void pair_flag_multi_kernel(MultiAr
   const PairPolicyArgs q = c->q;
   pair_flag_block(q, c->n_pairs, c->list, multi_local(m.begin, r, (int)blockIdx.x));
 }
-template <bool FMA, int MAXR>  // MAXR: rows per lane of the set's longest read (2, 4 or kRplF64); a pair takes the variant its own read needs
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) void pair_recompute_multi_kernel(MultiArgs m) {
+template <bool FMA, int MAXR>  // MAXR: rows per lane of the set's longest read (2, 4, kRplF64 or kRplPair8); a pair takes the variant its own read needs
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MAXR <= 6 ? 3 : 2))) void pair_recompute_multi_kernel(MultiArgs m) {
   __shared__ __attribute__((aligned(16))) unsigned char lds[PairRecomputeLds<MAXR, FMA>::bytes];
   const int r = multi_find(m, (int)blockIdx.x);
   const SmallCall* c = m.call[r];

@@ -28,6 +28,9 @@ struct EnvSwitches {
   const bool combine = [] { const char* v = getenv("GKL_HIP_COMBINE"); return !(v && v[0] == '0'); }();
   const bool quiet = getenv("GKL_HIP_QUIET") != nullptr;
   const bool one_device_engine = integer("GKL_HIP_DEVICE_ENGINES") == 1;
+  // the longest read of a region that takes the small-call path, for contexts made from here on: 511 when set to exactly
+  // that, 383 otherwise (gklhip_set_small_read_limit changes it per context)
+  const int small_read_limit = integer("GKL_HIP_SMALL_READ_LIMIT") == 511 ? 511 : 383;
 };
 const EnvSwitches g_env;
 }  // namespace
@@ -48,6 +51,7 @@ struct DevCtx {
   // general steps), GKLHIP_SPECULATE_FP64=1 (fp64 beside fp32 for a lone tiny call)
   int asm_general = 1;
   int speculate_fp64 = 0;
+  int small_read_limit = g_env.small_read_limit;   // 383 or 511 (gklhip_set_small_read_limit; a staging lane follows its parent)
   int lds_oob_zero = 1;   // dev_init's self-test: a DS read beyond the allocation returns 0 here (the fp32 programs' separator priors)
   hipStream_t stream = nullptr;
   // tables

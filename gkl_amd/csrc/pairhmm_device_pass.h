@@ -256,10 +256,12 @@ void launch_pair_policy_two_step(const FwdArgs<double>& d, const PairPolicyArgs&
   if (fma) {
     if (rows == 2)      hipLaunchKernelGGL((pairhmm_pair_recompute_kernel<2, true>), grid, block, 0, s, d, q, list);
     else if (rows == 4) hipLaunchKernelGGL((pairhmm_pair_recompute_kernel<4, true>), grid, block, 0, s, d, q, list);
+    else if (rows == kRplPair8) hipLaunchKernelGGL((pairhmm_pair_recompute_kernel<kRplPair8, true>), grid, block, 0, s, d, q, list);
     else                hipLaunchKernelGGL((pairhmm_pair_recompute_kernel<kRplF64, true>), grid, block, 0, s, d, q, list);
   } else {
     if (rows == 2)      hipLaunchKernelGGL((pairhmm_pair_recompute_kernel<2, false>), grid, block, 0, s, d, q, list);
     else if (rows == 4) hipLaunchKernelGGL((pairhmm_pair_recompute_kernel<4, false>), grid, block, 0, s, d, q, list);
+    else if (rows == kRplPair8) hipLaunchKernelGGL((pairhmm_pair_recompute_kernel<kRplPair8, false>), grid, block, 0, s, d, q, list);
     else                hipLaunchKernelGGL((pairhmm_pair_recompute_kernel<kRplF64, false>), grid, block, 0, s, d, q, list);
   }
 }
@@ -273,10 +275,12 @@ void launch_pair_policy(const FwdArgs<double>& d, const PairPolicyArgs& q, int r
   if (fma) {
     if (rows == 2)      hipLaunchKernelGGL((pairhmm_pair_policy_kernel<2, true>), grid, block, 0, s, d, q);
     else if (rows == 4) hipLaunchKernelGGL((pairhmm_pair_policy_kernel<4, true>), grid, block, 0, s, d, q);
+    else if (rows == kRplPair8) hipLaunchKernelGGL((pairhmm_pair_policy_kernel<kRplPair8, true>), grid, block, 0, s, d, q);
     else                hipLaunchKernelGGL((pairhmm_pair_policy_kernel<kRplF64, true>), grid, block, 0, s, d, q);
   } else {
     if (rows == 2)      hipLaunchKernelGGL((pairhmm_pair_policy_kernel<2, false>), grid, block, 0, s, d, q);
     else if (rows == 4) hipLaunchKernelGGL((pairhmm_pair_policy_kernel<4, false>), grid, block, 0, s, d, q);
+    else if (rows == kRplPair8) hipLaunchKernelGGL((pairhmm_pair_policy_kernel<kRplPair8, false>), grid, block, 0, s, d, q);
     else                hipLaunchKernelGGL((pairhmm_pair_policy_kernel<kRplF64, false>), grid, block, 0, s, d, q);
   }
 }
@@ -289,7 +293,7 @@ void launch_pair_fused(const FwdArgs<float>& f, const FwdArgs<double>& d, const 
   // Opt-in (GKLHIP_SPECULATE_FP64=1, read when the context is made, and only for a call that is alone on the device): it pays when a good share of the pairs fails the policy (100 x 10 with
   // 16 % failing: 0.151 -> 0.130 ms per call) and costs when none does (0.100 -> 0.130: the fp64 wavefront of a pair takes
   // twice as long as its fp32 one) -- and real active regions are mostly of the second kind.
-  if (speculate) {
+  if (speculate && rows != kRplPair8) {   // (the speculating kernel has no 8-row form)
     const dim3 grid((unsigned)n_pairs), block(128);
     if (fma) hipLaunchKernelGGL((pairhmm_pair_spec_kernel<kRplF64, true>), grid, block, 0, s, f, d, q);
     else     hipLaunchKernelGGL((pairhmm_pair_spec_kernel<kRplF64, false>), grid, block, 0, s, f, d, q);
@@ -301,17 +305,27 @@ void launch_pair_fused(const FwdArgs<float>& f, const FwdArgs<double>& d, const 
     else     hipLaunchKernelGGL((pairhmm_pair_fused_kernel<4, false>), grid, block, 0, s, f, d, q);
     return;
   }
+  if (rows == kRplPair8) {   // a read of 384 to 511 bases in the call: two wavefronts per SIMD
+    if (fma) hipLaunchKernelGGL((pairhmm_pair_fused_kernel<kRplPair8, true>), grid, block, 0, s, f, d, q);
+    else     hipLaunchKernelGGL((pairhmm_pair_fused_kernel<kRplPair8, false>), grid, block, 0, s, f, d, q);
+    return;
+  }
   if (fma) hipLaunchKernelGGL((pairhmm_pair_fused_kernel<kRplF64, true>), grid, block, 0, s, f, d, q);
   else     hipLaunchKernelGGL((pairhmm_pair_fused_kernel<kRplF64, false>), grid, block, 0, s, f, d, q);
 }
 
 // small calls of a double-precision context: every pair in fp64, ONE pair per wavefront (pairhmm_pair_f64_kernel); `rows`:
-// by the call's longest read -- up to 4: the four-wavefronts-per-SIMD variant
+// by the call's longest read -- up to 4: the four-wavefronts-per-SIMD variant; kRplPair8: reads of 384 to 511 bases, two
 void launch_pair_f64(const FwdArgs<double>& d, const PairPolicyArgs& q, int rows, int fma, int64_t n_pairs, hipStream_t s) {
   const dim3 grid((unsigned)n_pairs), block(64);
   if (rows <= 4) {
     if (fma) hipLaunchKernelGGL((pairhmm_pair_f64_kernel<4, true>), grid, block, 0, s, d, q);
     else     hipLaunchKernelGGL((pairhmm_pair_f64_kernel<4, false>), grid, block, 0, s, d, q);
+    return;
+  }
+  if (rows == kRplPair8) {
+    if (fma) hipLaunchKernelGGL((pairhmm_pair_f64_kernel<kRplPair8, true>), grid, block, 0, s, d, q);
+    else     hipLaunchKernelGGL((pairhmm_pair_f64_kernel<kRplPair8, false>), grid, block, 0, s, d, q);
     return;
   }
   if (fma) hipLaunchKernelGGL((pairhmm_pair_f64_kernel<kRplF64, true>), grid, block, 0, s, d, q);
@@ -354,7 +368,7 @@ struct CallPlan {
   PlanLayout L;
   bool pull;                     // the prep kernel pulls the block from pinned memory (plan_pulled)
   bool per_pair, fused;          // policy + fp64 of one pair per wavefront; ... with the fp32 recurrence in the same wavefront and launch
-  bool pair_double;              // a double-precision single-device context's call that fits the fp64 per-pair kernel (no read of 384 bases or more)
+  bool pair_double;              // a double-precision single-device context's call that fits the fp64 per-pair kernel (no read beyond small_read_len_max)
   int rows;                      // rows per lane of the per-pair kernels, by the longest read
   bool defers;                   // planned and staged, then handed to the small-call combiner (small_call_defers)
   int n_hist, chunk_stride, n_main_blocks, n_long_waves;   // grids and sizes that follow from the plan
@@ -369,8 +383,8 @@ struct CallPlan {
 bool deferral_offered(bool inline_host) { return g_env.combine && inline_host; }
 // ... and of a planned call that was offered it (plan_call, nowhere else): plan block pulled, per-pair call, no long
 // read, host-exact packed finalisation, no event recording, at most kTwoStepFrom pairs.  A double-precision context's
-// call (kSmallDouble) under the same conditions: its per-pair kernel holds reads of up to 383 bases (pair_double), and its
-// size limit has a name of its own (kSmallDoublePairs).
+// call (kSmallDouble) under the same conditions: its per-pair kernel holds reads of up to 383 bases, or 511 with the
+// context's small_read_limit (pair_double), and its size limit has a name of its own (kSmallDoublePairs).
 bool small_call_defers(const DevCtx* c, const CallPlan& P) {
   return deferral_offered(P.inline_host) && P.pull && c->cfg.record_events == 0 && (P.per_pair || P.pair_double) && c->plan.long_reads.empty() &&
          P.finalize_mode == kModePacked && c->plan.n_chunks > 0 && P.n_pairs <= (P.pair_double ? kSmallDoublePairs : kTwoStepFrom);
@@ -388,6 +402,15 @@ bool mid_call_shares(const DevCtx* c, const CallPlan& P) {
 bool double_mid_shares(const DevCtx* c, const CallPlan& P) {
   return deferral_offered(P.inline_host) && P.pull && c->cfg.record_events == 0 && P.use_double && !c->multi_device && c->plan.long_reads.empty() &&
          P.finalize_mode == kModePacked && c->plan.n_chunks > 0 && P.n_pairs > kTwoStepFrom && P.n_pairs <= kDirectPairs;
+}
+// The longest read of a call that may take the per-pair kernels: 383 bases (64 lanes x kRplF64 rows - 1), or 511 (x kRplPair8)
+// where the context's small_read_limit says so AND the call is one the small-call path is offered at all -- a host call
+// with its inputs inline, combining not switched off, a single-device context without event recording.  Everything else
+// (device-resident calls, multi-device contexts, record_events, GKL_HIP_COMBINE=0) keeps the general pass for such reads.
+static_assert(kRplPair8 == kRplF32 && kRplPair8 == kRplF64Wide, "the fourth tier: one wavefront at 8 rows per lane in both precisions");
+int small_read_len_max(const DevCtx* c, bool inline_host) {
+  const bool fourth_tier = c->small_read_limit == kLanes * kRplPair8 - 1 && deferral_offered(inline_host) && !c->multi_device && c->cfg.record_events == 0;
+  return kLanes * (fourth_tier ? kRplPair8 : kRplF64) - 1;
 }
 // `load` of pick_f32_rpl: 1 for a call that is not offered deferral.  (About half of the calls inside the library are on
 // the device at any moment, the others are being staged or finalised: 16 callers of 100 x 10 regions keep the 4-row
@@ -440,15 +463,17 @@ void plan_call(DevCtx* c, const gklhip_batch* db, int finalize_mode, bool inline
   P.rl = (size_t)db->read_off[n_reads]; P.hl = (size_t)db->hap_off[n_haps];
   P.L = layout_for(plan, n_reads, n_haps, long_lanes.size(), long_jobs.size(), inline_host ? P.rl : 0, inline_host ? P.hl : 0);
   P.pull = plan_pulled(P.L.total);
-  // policy + fp64 recomputation of one pair per wavefront (the kernel holds at most 64 x kRplF64 - 1 rows)
-  P.per_pair = !P.use_double && P.n_pairs <= kDirectPairs && P.n_long64 == 0 && plan.max_read_len <= kLanes * kRplF64 - 1;
+  // policy + fp64 recomputation of one pair per wavefront (the kernel holds at most 64 x kRplF64 - 1 rows, or 64 x
+  // kRplPair8 - 1 where the context's small_read_limit admits the fourth tier: small_read_len_max)
+  const int pair_len_max = small_read_len_max(c, inline_host);
+  P.per_pair = !P.use_double && P.n_pairs <= kDirectPairs && P.n_long64 == 0 && plan.max_read_len <= pair_len_max;
   // ... the tiny ones (one GATK active region) with the fp32 recurrence in the same wavefront and launch as the policy
   const int64_t fused_max = g_env.fused_max >= 0 ? g_env.fused_max : (int64_t)kTwoStepFrom;
   P.fused = P.per_pair && g_env.fused_pairs && P.n_pairs <= fused_max && P.n_long_main == 0 && c->cfg.rows_per_lane == 0;
-  P.rows = plan.max_read_len <= 2 * kLanes - 1 ? 2 : plan.max_read_len <= 4 * kLanes - 1 ? 4 : kRplF64;
+  P.rows = plan.max_read_len <= 2 * kLanes - 1 ? 2 : plan.max_read_len <= 4 * kLanes - 1 ? 4 : plan.max_read_len <= kLanes * kRplF64 - 1 ? kRplF64 : kRplPair8;
   // a double-precision context: every pair through the same fp64 per-pair code, when the call's reads fit it (the shards
   // of a multi-device context keep the general pass: that mode is as it was)
-  P.pair_double = P.use_double && !c->multi_device && plan.max_read_len <= kLanes * kRplF64 - 1;
+  P.pair_double = P.use_double && !c->multi_device && plan.max_read_len <= pair_len_max;
   P.defers = deferral && small_call_defers(c, P);
 
   P.n_hist = P.use_double ? 0 : 2 * (n_haps + 2);

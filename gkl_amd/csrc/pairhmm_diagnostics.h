@@ -23,6 +23,19 @@ int gklhip_small_call_counts(int device, int64_t out[3], int reset) {
   return GKLHIP_OK;
 }
 
+// The longest read of a region that takes the small-call path on this context, for the calls planned from here on: 383 or
+// 511 bases (small_read_len_max).  Every engine and staging lane of the context follows.
+int gklhip_set_small_read_limit(gklhip_ctx* ctx, int32_t max_read_len) {
+  if (!ctx) return fail(GKLHIP_ERR_INVALID_ARG, "context is NULL");
+  if (ctx->remote) return fail(GKLHIP_ERR_UNSUPPORTED, "gklhip_set_small_read_limit: not available on a client context of the PairHMM server (its contexts follow the server's GKL_HIP_SMALL_READ_LIMIT)");
+  if (max_read_len != kLanes * kRplF64 - 1 && max_read_len != kLanes * kRplPair8 - 1)
+    return fail(GKLHIP_ERR_INVALID_ARG, "gklhip_set_small_read_limit: %d (the limit is %d or %d bases)", (int)max_read_len, kLanes * kRplF64 - 1, kLanes * kRplPair8 - 1);
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  for (const std::vector<DevCtx*>* list : {&ctx->dev, &ctx->dev_alt, &ctx->twins, &ctx->lanes})
+    for (DevCtx* d : *list) d->small_read_limit = max_read_len;
+  return GKLHIP_OK;
+}
+
 // Diagnostics: the VALU issue ceiling of the recurrence's instruction mix on this device (issue_mix_*_kernel: 4 multiplies
 // + 4 FMAs per "cell", four wavefronts per SIMD, every CU) over about `ms_budget` milliseconds.  cells_per_s x 12 FLOP is
 // what roofline.issue_ceiling_tflops reports; clock_ghz = shader cycles the kernel counted / its HIP-event time, i.e. the

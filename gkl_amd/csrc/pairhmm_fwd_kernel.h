@@ -816,7 +816,15 @@ __device__ __forceinline__ void pair_policy_recompute(const FwdArgs<double>& a, 
   }
 }
 // One pair per wavefront.  MAXR rows per lane hold the longest read of the call; a pair whose read fits fewer rows per
-// lane takes the narrower variant (same number of steps, half the instructions per step).
+// lane takes the narrower variant (same number of steps, half the instructions per step): 2 rows up to 127 bases, 4 up to
+// 255, 6 up to 383, else MAXR.
+// kRplPair8: the fourth tier of the per-pair kernel families, reads of 384 to 511 bases (small_read_limit 511) -- what one
+// wavefront holds at 8 rows per lane in both precisions (fp32: pair_fp32_alone<8>, fp64: the f64r8 programs of the wide
+// long-read kernel).  Its kernels run two wavefronts per SIMD (pair_waves_per_eu).
+constexpr int kRplPair8 = 8;
+constexpr int pair_waves_per_eu(int maxr) { return maxr <= 4 ? 4 : maxr <= 6 ? 3 : 2; }
+// (the LDS maxima below name the 2-, 4- and MAXR-row tables; an 8-row kernel's ladder also takes the 6-row one)
+template <int MAXR, bool FMA> constexpr bool pair_lds_holds_6(int bytes) { return MAXR <= 6 || WaveJob<double, 6, FMA>::kLdsBytes <= bytes; }
 template <int MAXR, bool FMA>
 __device__ __forceinline__ void pair_policy_block(const FwdArgs<double>& a, const PairPolicyArgs& q, int64_t p, unsigned char* lds) {
   const int lane = threadIdx.x;
@@ -825,12 +833,14 @@ __device__ __forceinline__ void pair_policy_block(const FwdArgs<double>& a, cons
   const int R = (int)(a.b.read_off[r + 1] - a.b.read_off[r]);
   if (MAXR > 2 && R <= 2 * kLanes - 1)      pair_policy_recompute<2, FMA>(a, q, p, r, R, k, lds);
   else if (MAXR > 4 && R <= 4 * kLanes - 1) pair_policy_recompute<4, FMA>(a, q, p, r, R, k, lds);
+  else if (MAXR > 6 && R <= 6 * kLanes - 1) pair_policy_recompute<6, FMA>(a, q, p, r, R, k, lds);
   else                                      pair_policy_recompute<MAXR, FMA>(a, q, p, r, R, k, lds);
 }
 template <int RPL, bool FMA>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) void pairhmm_pair_policy_kernel(FwdArgs<double> a, PairPolicyArgs q) {
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(RPL <= 6 ? 3 : 2))) void pairhmm_pair_policy_kernel(FwdArgs<double> a, PairPolicyArgs q) {
   constexpr int kLds2 = WaveJob<double, 2, FMA>::kLdsBytes, kLds4 = WaveJob<double, 4, FMA>::kLdsBytes, kLdsR = WaveJob<double, RPL, FMA>::kLdsBytes;
   __shared__ __attribute__((aligned(16))) unsigned char lds[kLdsR > kLds4 ? (kLdsR > kLds2 ? kLdsR : kLds2) : (kLds4 > kLds2 ? kLds4 : kLds2)];
+  static_assert(pair_lds_holds_6<RPL, FMA>((int)sizeof lds), "LDS of the widest job");
   pair_policy_block<RPL, FMA>(a, q, (int64_t)blockIdx.x, lds);
 }
 
@@ -874,7 +884,7 @@ __device__ __forceinline__ void pair_fused_block(const FwdArgs<float>& f, const 
   float v;
   if (R <= 2 * kLanes - 1)                     v = pair_fp32_alone<2, FMA>(f, p, r, R, k, lds);
   else if (MAXR64 <= 4 || R <= 4 * kLanes - 1) v = pair_fp32_alone<4, FMA>(f, p, r, R, k, lds);
-  else                                         v = pair_fp32_alone<8, FMA>(f, p, r, R, k, lds);
+  else                                         v = pair_fp32_alone<8, FMA>(f, p, r, R, k, lds);   // (up to 511 bases: what MAXR64 == kRplPair8 admits)
   const bool fails = v < 1e-28f;  // NaN compares false and stays fp32, like the reference (IntelPairHmm.cc:159)
   if (lane == 0) {
     q.used64[p] = fails ? 1 : 0;
@@ -887,6 +897,7 @@ __device__ __forceinline__ void pair_fused_block(const FwdArgs<float>& f, const 
   __syncthreads();  // the fp32 table's readers are done: the fp64 table takes its place
   if (MAXR64 > 2 && R <= 2 * kLanes - 1)      pair_policy_recompute<2, FMA>(d, q, p, r, R, k, lds);
   else if (MAXR64 > 4 && R <= 4 * kLanes - 1) pair_policy_recompute<4, FMA>(d, q, p, r, R, k, lds);
+  else if (MAXR64 > 6 && R <= 6 * kLanes - 1) pair_policy_recompute<6, FMA>(d, q, p, r, R, k, lds);
   else                                        pair_policy_recompute<MAXR64, FMA>(d, q, p, r, R, k, lds);
 }
 template <int MAXR64, bool FMA>
@@ -894,9 +905,10 @@ struct PairFusedLds {
   static constexpr int a = WaveJob<float, (MAXR64 <= 4 ? 4 : 8), FMA>::kLdsBytes, b = WaveJob<double, 2, FMA>::kLdsBytes,
                        c = WaveJob<double, 4, FMA>::kLdsBytes, d = WaveJob<double, MAXR64, FMA>::kLdsBytes;
   static constexpr int ab = a > b ? a : b, cd = c > d ? c : d, bytes = ab > cd ? ab : cd;
+  static_assert(pair_lds_holds_6<MAXR64, FMA>(bytes), "LDS of the widest job");
 };
 template <int MAXR64, bool FMA>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MAXR64 <= 4 ? 4 : 3))) void pairhmm_pair_fused_kernel(FwdArgs<float> f, FwdArgs<double> d,
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(pair_waves_per_eu(MAXR64)))) void pairhmm_pair_fused_kernel(FwdArgs<float> f, FwdArgs<double> d,
                                                                                                        PairPolicyArgs q) {
   __shared__ __attribute__((aligned(16))) unsigned char lds[PairFusedLds<MAXR64, FMA>::bytes];
   pair_fused_block<MAXR64, FMA>(f, d, q, (int64_t)blockIdx.x, lds);
@@ -907,6 +919,7 @@ template <int MAXR, bool FMA>
 struct PairRecomputeLds {
   static constexpr int k2 = WaveJob<double, 2, FMA>::kLdsBytes, k4 = WaveJob<double, 4, FMA>::kLdsBytes, kR = WaveJob<double, MAXR, FMA>::kLdsBytes;
   static constexpr int bytes = kR > k4 ? (kR > k2 ? kR : k2) : (k4 > k2 ? k4 : k2);
+  static_assert(pair_lds_holds_6<MAXR, FMA>(bytes), "LDS of the widest job");
 };
 // Small calls of a double-precision context (gklhip_config.use_double; kSmallDouble): EVERY pair in double precision, one
 // pair per wavefront in one launch behind the preparation -- the fp64 recurrence of the fused kernel's failing pairs with
@@ -919,14 +932,15 @@ __device__ __forceinline__ void pair_f64_block(const FwdArgs<double>& d, const P
   const int R = (int)(d.b.read_off[r + 1] - d.b.read_off[r]);
   if (MAXR > 2 && R <= 2 * kLanes - 1)      pair_policy_recompute<2, FMA, true>(d, q, p, r, R, k, lds);
   else if (MAXR > 4 && R <= 4 * kLanes - 1) pair_policy_recompute<4, FMA, true>(d, q, p, r, R, k, lds);
+  else if (MAXR > 6 && R <= 6 * kLanes - 1) pair_policy_recompute<6, FMA, true>(d, q, p, r, R, k, lds);
   else                                      pair_policy_recompute<MAXR, FMA, true>(d, q, p, r, R, k, lds);
 }
 // MAXR = 4: the variant for calls whose reads have at most 255 bases (no kRplF64 code in the kernel: four wavefronts per
-// SIMD, as the narrow fused kernel); MAXR = kRplF64: reads of up to 383 bases, three.
+// SIMD, as the narrow fused kernel); MAXR = kRplF64: reads of up to 383 bases, three; MAXR = kRplPair8: up to 511, two.
 // A call only gets here deferred (small_call_defers: host finalisation of packed words; recompute_args: no packed output
 // of the forward kernels), said as constants: the device log10 of the other finalisation modes is not compiled in.
 template <int MAXR, bool FMA>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MAXR <= 4 ? 4 : 3))) void pairhmm_pair_f64_kernel(FwdArgs<double> d, PairPolicyArgs q) {
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(pair_waves_per_eu(MAXR)))) void pairhmm_pair_f64_kernel(FwdArgs<double> d, PairPolicyArgs q) {
   __shared__ __attribute__((aligned(16))) unsigned char lds[PairRecomputeLds<MAXR, FMA>::bytes];
   d.packed_out = nullptr;
   q.mode = kModePackedWords;
@@ -937,7 +951,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MAXR <= 4 ? 
 // fp64 one at the same time; the policy then picks.  Five times the fp64 work a call needs (16 % of the pairs fail) --
 // chosen only when the call is alone on the device (one HaplotypeCaller thread sending region after region: the usual
 // way GATK runs), where nothing else wants those SIMDs and the call's latency is its longest dependent chain:
-// max(fp32, fp64) instead of fp32 + fp64.
+// max(fp32, fp64) instead of fp32 + fp64.  (No 8-row form: a call with a read of 384 bases or more does not speculate.)
 template <int MAXR64, bool FMA>
 __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(3))) void pairhmm_pair_spec_kernel(FwdArgs<float> f, FwdArgs<double> d,
                                                                                                         PairPolicyArgs q) {
@@ -1023,12 +1037,13 @@ __device__ __forceinline__ void pair_recompute_block(const FwdArgs<double>& a, c
     const int R = (int)(a.b.read_off[r + 1] - a.b.read_off[r]);
     if (MAXR > 2 && R <= 2 * kLanes - 1)      pair_policy_recompute<2, FMA>(a, q, p, r, R, k, lds);
     else if (MAXR > 4 && R <= 4 * kLanes - 1) pair_policy_recompute<4, FMA>(a, q, p, r, R, k, lds);
+    else if (MAXR > 6 && R <= 6 * kLanes - 1) pair_policy_recompute<6, FMA>(a, q, p, r, R, k, lds);
     else                                      pair_policy_recompute<MAXR, FMA>(a, q, p, r, R, k, lds);
     __syncthreads();  // (a block that takes a second pair reuses the prior table)
   }
 }
 template <int MAXR, bool FMA>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) void pairhmm_pair_recompute_kernel(FwdArgs<double> a, PairPolicyArgs q,
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MAXR <= 6 ? 3 : 2))) void pairhmm_pair_recompute_kernel(FwdArgs<double> a, PairPolicyArgs q,
                                                                                                            const int32_t* list) {
   __shared__ __attribute__((aligned(16))) unsigned char lds[PairRecomputeLds<MAXR, FMA>::bytes];
   pair_recompute_block<MAXR, FMA>(a, q, list, (int)blockIdx.x, (int)gridDim.x, lds);

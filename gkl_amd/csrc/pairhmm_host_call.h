@@ -145,10 +145,12 @@ struct SmallCombiner {
       if (fma) {
         if (rows == 2)      hipLaunchKernelGGL((pair_recompute_multi_kernel<true, 2>), grid, block, 0, sl.stream, mr);
         else if (rows == 4) hipLaunchKernelGGL((pair_recompute_multi_kernel<true, 4>), grid, block, 0, sl.stream, mr);
+        else if (rows == kRplPair8) hipLaunchKernelGGL((pair_recompute_multi_kernel<true, kRplPair8>), grid, block, 0, sl.stream, mr);
         else                hipLaunchKernelGGL((pair_recompute_multi_kernel<true, kRplF64>), grid, block, 0, sl.stream, mr);
       } else {
         if (rows == 2)      hipLaunchKernelGGL((pair_recompute_multi_kernel<false, 2>), grid, block, 0, sl.stream, mr);
         else if (rows == 4) hipLaunchKernelGGL((pair_recompute_multi_kernel<false, 4>), grid, block, 0, sl.stream, mr);
+        else if (rows == kRplPair8) hipLaunchKernelGGL((pair_recompute_multi_kernel<false, kRplPair8>), grid, block, 0, sl.stream, mr);
         else                hipLaunchKernelGGL((pair_recompute_multi_kernel<false, kRplF64>), grid, block, 0, sl.stream, mr);
       }
     } else if (calls[0]->call.kind == kSmallDoubleStream) {   // mid-size regions of a double-precision context: the packed fp64 pass, then its packed words
@@ -158,27 +160,35 @@ struct SmallCombiner {
       else     hipLaunchKernelGGL((fwd_stream_f64_multi_kernel<false, kRplF64Jobs>), dim3((unsigned)mf.begin[n]), dim3(64), 0, sl.stream, mf);
       hipLaunchKernelGGL(finalize64_multi_kernel, dim3((unsigned)mq.begin[n]), dim3(kFlagBlock), 0, sl.stream, mq);
     } else if (calls[0]->call.kind == kSmallDouble) {   // calls of double-precision contexts: one launch, every pair in fp64
-      bool narrow = true;   // as below
-      for (int i = 0; i < n; i++) narrow = narrow && calls[i]->call.rows <= 4;
+      bool narrow = true, tier8 = false;   // as below
+      for (int i = 0; i < n; i++) { narrow = narrow && calls[i]->call.rows <= 4; tier8 = tier8 || calls[i]->call.rows == kRplPair8; }
       const dim3 grid((unsigned)mq.begin[n]), block(64);
-      if (narrow && fma)  hipLaunchKernelGGL((pair_f64_multi_kernel<true, 4>), grid, block, 0, sl.stream, mq);
+      if (tier8 && fma)   hipLaunchKernelGGL((pair_f64_multi_kernel<true, kRplPair8>), grid, block, 0, sl.stream, mq);
+      else if (tier8)     hipLaunchKernelGGL((pair_f64_multi_kernel<false, kRplPair8>), grid, block, 0, sl.stream, mq);
+      else if (narrow && fma)  hipLaunchKernelGGL((pair_f64_multi_kernel<true, 4>), grid, block, 0, sl.stream, mq);
       else if (narrow)    hipLaunchKernelGGL((pair_f64_multi_kernel<false, 4>), grid, block, 0, sl.stream, mq);
       else if (fma)       hipLaunchKernelGGL((pair_f64_multi_kernel<true, kRplF64>), grid, block, 0, sl.stream, mq);
       else                hipLaunchKernelGGL((pair_f64_multi_kernel<false, kRplF64>), grid, block, 0, sl.stream, mq);
     } else if (calls[0]->call.fused) {  // (every call of a set is of one kind: a leader only takes calls like its own, a multi call cuts its sets by kind)
-      bool narrow = true;   // reads of at most 255 bases in every call of the set: the four-wavefronts-per-SIMD variant
-      for (int i = 0; i < n; i++) narrow = narrow && calls[i]->call.rows <= 4;
+      bool narrow = true, tier8 = false;   // narrow: reads of at most 255 bases in every call of the set, the four-wavefronts-per-SIMD variant; tier8: a read of 384 to 511 bases in one of them, the 8-row form for the whole set
+      for (int i = 0; i < n; i++) { narrow = narrow && calls[i]->call.rows <= 4; tier8 = tier8 || calls[i]->call.rows == kRplPair8; }
       const dim3 grid((unsigned)mq.begin[n]), block(64);
-      if (narrow && fma)  hipLaunchKernelGGL((pair_fused_multi_kernel<true, 4>), grid, block, 0, sl.stream, mq);
+      if (tier8 && fma)   hipLaunchKernelGGL((pair_fused_multi_kernel<true, kRplPair8>), grid, block, 0, sl.stream, mq);
+      else if (tier8)     hipLaunchKernelGGL((pair_fused_multi_kernel<false, kRplPair8>), grid, block, 0, sl.stream, mq);
+      else if (narrow && fma)  hipLaunchKernelGGL((pair_fused_multi_kernel<true, 4>), grid, block, 0, sl.stream, mq);
       else if (narrow)    hipLaunchKernelGGL((pair_fused_multi_kernel<false, 4>), grid, block, 0, sl.stream, mq);
       else if (fma)       hipLaunchKernelGGL((pair_fused_multi_kernel<true, kRplF64>), grid, block, 0, sl.stream, mq);
       else                hipLaunchKernelGGL((pair_fused_multi_kernel<false, kRplF64>), grid, block, 0, sl.stream, mq);
-    } else if (fma) {
-      hipLaunchKernelGGL((fwd_stream_multi_kernel<true, kRplF32>), dim3((unsigned)mf.begin[n]), dim3(64), 0, sl.stream, mf);
-      hipLaunchKernelGGL((pair_policy_multi_kernel<true, kRplF64>), dim3((unsigned)mq.begin[n]), dim3(64), 0, sl.stream, mq);
-    } else {
-      hipLaunchKernelGGL((fwd_stream_multi_kernel<false, kRplF32>), dim3((unsigned)mf.begin[n]), dim3(64), 0, sl.stream, mf);
-      hipLaunchKernelGGL((pair_policy_multi_kernel<false, kRplF64>), dim3((unsigned)mq.begin[n]), dim3(64), 0, sl.stream, mq);
+    } else {   // the one-launch policy behind the packed fp32 pass: the 8-row form when a call of the set holds a read of 384 to 511 bases
+      bool tier8 = false;
+      for (int i = 0; i < n; i++) tier8 = tier8 || calls[i]->call.rows == kRplPair8;
+      const dim3 grid((unsigned)mq.begin[n]), block(64);
+      if (fma) hipLaunchKernelGGL((fwd_stream_multi_kernel<true, kRplF32>), dim3((unsigned)mf.begin[n]), dim3(64), 0, sl.stream, mf);
+      else     hipLaunchKernelGGL((fwd_stream_multi_kernel<false, kRplF32>), dim3((unsigned)mf.begin[n]), dim3(64), 0, sl.stream, mf);
+      if (tier8 && fma) hipLaunchKernelGGL((pair_policy_multi_kernel<true, kRplPair8>), grid, block, 0, sl.stream, mq);
+      else if (tier8)   hipLaunchKernelGGL((pair_policy_multi_kernel<false, kRplPair8>), grid, block, 0, sl.stream, mq);
+      else if (fma)     hipLaunchKernelGGL((pair_policy_multi_kernel<true, kRplF64>), grid, block, 0, sl.stream, mq);
+      else              hipLaunchKernelGGL((pair_policy_multi_kernel<false, kRplF64>), grid, block, 0, sl.stream, mq);
     }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(sl.ev, sl.stream));

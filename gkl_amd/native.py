@@ -109,6 +109,9 @@ def load_library(path: Optional[str] = None):
     lib.gklhip_fault_inject.argtypes = [C.c_char_p]
     lib.gklhip_fault_inject.restype = C.c_int
     lib.gklhip_small_call_counts.restype = C.c_int
+    if hasattr(lib, "gklhip_set_small_read_limit"):   # (absent from an older build loaded by path for an A/B)
+        lib.gklhip_set_small_read_limit.argtypes = [C.c_void_p, C.c_int32]
+        lib.gklhip_set_small_read_limit.restype = C.c_int
     lib.gklhip_gather_note.argtypes = [C.c_void_p]
     lib.gklhip_gather_note.restype = C.c_char_p
     lib.gklhip_partition_reads.argtypes = [C.c_int32, _i64p, C.c_int32, C.POINTER(C.c_int32)]
@@ -291,7 +294,8 @@ class PairHmmContext:
 
     def __init__(self, use_double: bool = False, max_threads: int = 0, device: int = -1,
                  fma_mode: int = 1, finalize: int = -1, record_events: bool = False,
-                 rows_per_lane: int = 0, lib_path: Optional[str] = None, devices=None, server: Optional[str] = None):
+                 rows_per_lane: int = 0, lib_path: Optional[str] = None, devices=None, server: Optional[str] = None,
+                 small_read_limit: Optional[int] = None):
         self.lib = load_library(lib_path)
         cfg = Config(ABI_VERSION, device, int(use_double), int(max_threads), int(fma_mode),
                      int(finalize), int(record_events), int(rows_per_lane))
@@ -309,6 +313,12 @@ class PairHmmContext:
             _raise(self.lib, st)
         self.handle = h
         self.use_double = bool(use_double)
+        if small_read_limit is not None:
+            try:
+                self.set_small_read_limit(small_read_limit)
+            except Exception:
+                self.close()
+                raise
 
     @property
     def n_devices(self) -> int:
@@ -324,6 +334,13 @@ class PairHmmContext:
         """none | peer | rccl (lazily created: before the first device-resident call, what it will try) |
         peer-after-rccl-failure (gather_note says why)"""
         return ("none", "peer", "rccl", "peer-after-rccl-failure")[self.lib.gklhip_gather_backend(self.handle)]
+
+    def set_small_read_limit(self, max_read_len: int) -> None:
+        """The longest read of a region that takes the small-call path (gklhip_set_small_read_limit): 383, the default,
+        or 511.  New contexts start from GKL_HIP_SMALL_READ_LIMIT; a client context of a server cannot set it."""
+        st = self.lib.gklhip_set_small_read_limit(self.handle, int(max_read_len))
+        if st != OK:
+            _raise(self.lib, st)
 
     def release_idle(self) -> int:
         """Give back the streams / twin engines the context holds only for speed, if it is idle (gklhip_release_idle);

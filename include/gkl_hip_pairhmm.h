@@ -161,7 +161,8 @@ int gklhip_compute(gklhip_ctx* ctx, const gklhip_batch* host_batch, double* out_
  * the rest still run.  A region with n_reads * n_haps == 0 succeeds and writes nothing.  A HIP failure of a shared set of
  * launches fails every region in that set (after its stream has been drained).
  * Which regions share a set: SMALL ones, those the single call hands to the small-call combiner (inputs of at most 1 MB,
- * at most 2048 pairs, no read of 384 bases or more, host finalisation, no record_events), and MID-SIZE
+ * at most 2048 pairs, no read beyond the small-read limit -- 383 bases, or 511 with GKL_HIP_SMALL_READ_LIMIT=511 /
+ * gklhip_set_small_read_limit --, host finalisation, no record_events), and MID-SIZE
  * ones, for which all of that holds except the size: 2049 to 65 536 pairs.  The two are cut apart.  The small regions,
  * in input order, are cut into sets of one kind (with rows_per_lane == 0: the fused per-pair kernel) of at most 64
  * regions.  Small calls come in kinds, and a set -- of a multi call or of concurrent callers -- holds one kind only: the
@@ -247,6 +248,20 @@ int gklhip_measure_issue_ceiling(gklhip_ctx* ctx, int use_double, double ms_budg
  * calls too and are counted like the fp32 ones (they used to take the general pass and count nothing). */
 int gklhip_small_call_counts(int device, int64_t out[3], int reset);
 
+/* The small-read limit: the longest read of a region that takes the small-call path (the fused per-pair kernel, the
+ * combiner of concurrent callers, the shared sets of gklhip_compute_multi, in single and in double precision): 383
+ * bases, or 511 with GKL_HIP_SMALL_READ_LIMIT=511 / gklhip_set_small_read_limit.  A region with a longer read takes the
+ * general pass and runs alone inside a multi call.  max_read_len must be exactly 383 (the default) or 511 -- what one
+ * wavefront holds at 6 and at 8 rows per lane; anything else is GKLHIP_ERR_INVALID_ARG.  Takes the context's lock and
+ * applies to the calls planned afterwards.  New contexts start from the process's environment, read once:
+ * GKL_HIP_SMALL_READ_LIMIT=511 means 511, unset or any other value 383 (how the JNI libraries and the PairHMM server get
+ * it).  With 511, what keeps the general pass for reads of 384 to 511 bases is what never takes the small-call path
+ * anyway: multi-device contexts, record_events != 0, device-resident calls, GKL_HIP_COMBINE=0; reads of 512 bases or
+ * more always do.  A call that holds a read of 384 bases or more does not speculate (GKLHIP_SPECULATE_FP64).  Results
+ * are bit for bit the same under both limits.  On a client context of the server: GKLHIP_ERR_UNSUPPORTED (the server's
+ * contexts follow the server process's environment). */
+int gklhip_set_small_read_limit(gklhip_ctx* ctx, int32_t max_read_len);
+
 /* Gives back what an IDLE context holds only for speed: the streams it made for big calls (every stream is a hardware
  * queue the device's scheduler rotates among all processes' -- an idle process should hold one or two, not seven), its
  * twin engines of big host-buffer calls and second engines of two-stream device-resident callers.  Nothing happens while a
@@ -267,7 +282,7 @@ int gklhip_fault_inject(const char* spec);
  * processes meet in one process's small-call combiner.  A client process makes no HIP call: batches travel through a
  * shared-memory arena (memfd) the server maps.  gklhip_init with GKL_HIP_SERVER=PATH in the environment is
  * gklhip_connect(PATH, cfg, out_ctx).  On a remote context gklhip_compute, gklhip_compute_multi (region by region), gklhip_get_stats, gklhip_release_idle (no-op)
- * and gklhip_done work; gklhip_compute_device, gklhip_get_raw, gklhip_get_raw_region, gklhip_get_step_times and gklhip_measure_issue_ceiling
+ * and gklhip_done work; gklhip_compute_device, gklhip_get_raw, gklhip_get_raw_region, gklhip_get_step_times, gklhip_set_small_read_limit and gklhip_measure_issue_ceiling
  * return GKLHIP_ERR_UNSUPPORTED, and so does gklhip_fault_inject in a process with GKL_HIP_SERVER set.  A server that
  * has gone away fails the call with GKLHIP_ERR_HIP and a message that names the socket. */
 #define GKLHIP_SERVER_PROTOCOL 1

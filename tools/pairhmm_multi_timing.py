@@ -5,9 +5,12 @@ two arms alternating in one process.  Both arms are made on prebuilt arguments: 
 both give the same bytes and reports how many sets of launches the multi call took (gklhip_small_call_counts: calls,
 combined calls, sets).  A mid-size shape (400x40, 250x128, 1000x50) measures the mid-size sets of docs/NOTES.md 69.
 --double: the same on a double-precision context (gklhip_config.use_double, GATK's --native-pair-hmm-use-double-precision):
-docs/NOTES.md 70; with a mid-size --region: the mid-size fp64 sets of docs/NOTES.md 71.  --lib FILE: development only -- another build of libgklhip_pairhmm.so (A/B against an earlier commit's, same process layout).
+docs/NOTES.md 70; with a mid-size --region: the mid-size fp64 sets of docs/NOTES.md 71.  --read-len LO-HI / --hap-len LO-HI:
+the length ranges of the regions' reads and haplotypes (default: make_batch's 50-250 / 100-500); --limit 383|511: the
+context's small-read limit (gklhip_set_small_read_limit) -- long-read regions under both limits: docs/NOTES.md 72.  --lib FILE: development only -- another build of libgklhip_pairhmm.so (A/B against an earlier commit's, same process layout).
 
-usage: tools/pairhmm_multi_timing.py [--double] [--region 100x10] [--counts 1,2,4,8,16,64] [--reps 30] [--warmup 10] [--lib FILE] [--out FILE]"""
+usage: tools/pairhmm_multi_timing.py [--double] [--region 100x10] [--read-len 384-511] [--hap-len 520-600] [--limit 511]
+                                      [--counts 1,2,4,8,16,64] [--reps 30] [--warmup 10] [--lib FILE] [--out FILE]"""
 import argparse
 import ctypes as C
 import json
@@ -30,7 +33,20 @@ def main():
     ap.add_argument("--out", default="")
     ap.add_argument("--double", action="store_true", help="a use_double context")
     ap.add_argument("--lib", default="", help="the libgklhip_pairhmm.so to load (default: the tree's)")
+    ap.add_argument("--read-len", default="", help="LO-HI: read lengths (default: make_batch's)")
+    ap.add_argument("--hap-len", default="", help="LO-HI: haplotype lengths (default: make_batch's)")
+    ap.add_argument("--limit", type=int, default=0, help="383 or 511: the context's small-read limit (default: the library's, not set)")
     a = ap.parse_args()
+    lens = {}
+    for key, val in (("read_len", a.read_len), ("hap_len", a.hap_len)):
+        if val:
+            try:
+                lo, hi = (int(x) for x in val.split("-"))
+            except ValueError:
+                raise SystemExit(f"--{key.replace('_', '-')} wants LO-HI, e.g. 384-511")
+            if not 1 <= lo <= hi:
+                raise SystemExit(f"--{key.replace('_', '-')} wants 1 <= LO <= HI")
+            lens[key] = (lo, hi)
     if a.reps < 30:
         raise SystemExit("at least 30 repetitions")
     try:
@@ -43,11 +59,12 @@ def main():
     from gkl_amd.synth import make_batch
     if a.lib:
         native.LIB_PATH = os.path.abspath(a.lib)   # (before the first load: the counters below come from the same library)
-    ctx = native.PairHmmContext(device=0, use_double=a.double)
+    ctx = native.PairHmmContext(device=0, use_double=a.double, small_read_limit=a.limit or None)
     lib, h = ctx.lib, ctx.handle
-    result = {"region": f"hc {n_reads} x {n_haps}", "use_double": bool(a.double), "lib": a.lib or "tree", "reps": a.reps, "warmup": a.warmup, "rows": []}
+    result = {"region": f"hc {n_reads} x {n_haps}", "read_len": a.read_len or "default", "hap_len": a.hap_len or "default", "limit": a.limit or "default",
+              "use_double": bool(a.double), "lib": a.lib or "tree", "reps": a.reps, "warmup": a.warmup, "rows": []}
     for K in (int(x) for x in a.counts.split(",")):
-        batches = [make_batch("hc", n_reads, n_haps, seed=1000 + k) for k in range(K)]
+        batches = [make_batch("hc", n_reads, n_haps, seed=1000 + k, **lens) for k in range(K)]
         keep, cbs = [], (native.CBatch * K)()
         for k, b in enumerate(batches):
             arrs = [np.ascontiguousarray(x, np.uint8) for x in (b.read_bases, b.read_quals, b.ins_gop, b.del_gop, b.gcp, b.hap_bases)]
