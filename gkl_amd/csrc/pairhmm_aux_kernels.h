@@ -159,11 +159,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void fw
   else               fwd_stream_block<float, kRplF32, FMA>(a, block, lds);
 }
 template <bool FMA, int kRplF64>   // kRplF64: rows per lane of the set's longest read (kRplF64, or kRplPair8 with a read of 384 bases or more)
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kRplF64 <= 6 ? 3 : 2))) void pair_policy_multi_kernel(MultiArgs m) {
-  __shared__ __attribute__((aligned(16))) unsigned char lds[WaveJob<double, kRplF64, FMA>::kLdsBytes];
-  static_assert(WaveJob<double, 2, FMA>::kLdsBytes <= WaveJob<double, kRplF64, FMA>::kLdsBytes &&
-                WaveJob<double, 4, FMA>::kLdsBytes <= WaveJob<double, kRplF64, FMA>::kLdsBytes &&
-                (kRplF64 <= 6 || WaveJob<double, 6, FMA>::kLdsBytes <= WaveJob<double, kRplF64, FMA>::kLdsBytes), "LDS of the widest job");
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(pair_policy_waves_per_eu(kRplF64)))) void pair_policy_multi_kernel(MultiArgs m) {
+  __shared__ __attribute__((aligned(16))) unsigned char lds[pair_lds_f64<kRplF64, FMA>()];
   const int r = multi_find(m, (int)blockIdx.x);
   const SmallCall* c = m.call[r];
   const int64_t p = multi_local(m.begin, r, (int)blockIdx.x);
@@ -174,7 +171,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kRplF64 <= 6
 
 template <bool FMA, int kRplF64>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(pair_waves_per_eu(kRplF64)))) void pair_fused_multi_kernel(MultiArgs m) {
-  __shared__ __attribute__((aligned(16))) unsigned char lds[PairFusedLds<kRplF64, FMA>::bytes];
+  __shared__ __attribute__((aligned(16))) unsigned char lds[pair_lds_fused<kRplF64, FMA>()];
   const int r = multi_find(m, (int)blockIdx.x);
   const SmallCall* c = m.call[r];
   const int64_t p = multi_local(m.begin, r, (int)blockIdx.x);
@@ -189,7 +186,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(pair_waves_p
 // set, the four-wavefronts-per-SIMD form; kRplF64 up to 383 bases; kRplPair8 up to 511).
 template <bool FMA, int MAXR>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(pair_waves_per_eu(MAXR)))) void pair_f64_multi_kernel(MultiArgs m) {
-  __shared__ __attribute__((aligned(16))) unsigned char lds[PairRecomputeLds<MAXR, FMA>::bytes];
+  __shared__ __attribute__((aligned(16))) unsigned char lds[pair_lds_f64<MAXR, FMA>()];
   const int r = multi_find(m, (int)blockIdx.x);
   const SmallCall* c = m.call[r];
   const int64_t p = multi_local(m.begin, r, (int)blockIdx.x);
@@ -213,8 +210,8 @@ __global__ __launch_bounds__(kPairFlagBlock) void pair_flag_multi_kernel(MultiAr
   pair_flag_block(q, c->n_pairs, c->list, multi_local(m.begin, r, (int)blockIdx.x));
 }
 template <bool FMA, int MAXR>  // MAXR: rows per lane of the set's longest read (2, 4, kRplF64 or kRplPair8); a pair takes the variant its own read needs
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MAXR <= 6 ? 3 : 2))) void pair_recompute_multi_kernel(MultiArgs m) {
-  __shared__ __attribute__((aligned(16))) unsigned char lds[PairRecomputeLds<MAXR, FMA>::bytes];
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(pair_policy_waves_per_eu(MAXR)))) void pair_recompute_multi_kernel(MultiArgs m) {
+  __shared__ __attribute__((aligned(16))) unsigned char lds[pair_lds_f64<MAXR, FMA>()];
   const int r = multi_find(m, (int)blockIdx.x);
   const SmallCall* c = m.call[r];
   // What every region of a set has in common is said here as constants (mid_call_shares: host finalisation of packed

@@ -249,87 +249,76 @@ int pick_f32_rpl(int forced, int n_reads, int n_haps, const int64_t* read_off, c
   return 2;
 }
 
-// the per-pair policy of a mid-size call in two launches (pairhmm_pair_flag_kernel): `list` holds n_pairs entries
-void launch_pair_policy_two_step(const FwdArgs<double>& d, const PairPolicyArgs& q, int rows, int fma, int64_t n_pairs, int32_t* list, hipStream_t s) {
-  hipLaunchKernelGGL(pairhmm_pair_flag_kernel, dim3((unsigned)multi_flag_blocks((int)n_pairs)), dim3(kFlagBlock), 0, s, q, (int32_t)n_pairs, list);
-  const dim3 grid((unsigned)multi_recompute_blocks((int)n_pairs)), block(64);
-  if (fma) {
-    if (rows == 2)      hipLaunchKernelGGL((pairhmm_pair_recompute_kernel<2, true>), grid, block, 0, s, d, q, list);
-    else if (rows == 4) hipLaunchKernelGGL((pairhmm_pair_recompute_kernel<4, true>), grid, block, 0, s, d, q, list);
-    else if (rows == kRplPair8) hipLaunchKernelGGL((pairhmm_pair_recompute_kernel<kRplPair8, true>), grid, block, 0, s, d, q, list);
-    else                hipLaunchKernelGGL((pairhmm_pair_recompute_kernel<kRplF64, true>), grid, block, 0, s, d, q, list);
-  } else {
-    if (rows == 2)      hipLaunchKernelGGL((pairhmm_pair_recompute_kernel<2, false>), grid, block, 0, s, d, q, list);
-    else if (rows == 4) hipLaunchKernelGGL((pairhmm_pair_recompute_kernel<4, false>), grid, block, 0, s, d, q, list);
-    else if (rows == kRplPair8) hipLaunchKernelGGL((pairhmm_pair_recompute_kernel<kRplPair8, false>), grid, block, 0, s, d, q, list);
-    else                hipLaunchKernelGGL((pairhmm_pair_recompute_kernel<kRplF64, false>), grid, block, 0, s, d, q, list);
-  }
-}
 void launch_main_f32(const FwdArgs<float>& a, int rpl_main, int fma, int n_blocks, hipStream_t s) {
   if (rpl_main == 2)      launch_stream<float, 2>(a, fma, n_blocks, s);
   else if (rpl_main == 4) launch_stream<float, 4>(a, fma, n_blocks, s);
   else                    launch_stream<float, kRplF32>(a, fma, n_blocks, s);
 }
-void launch_pair_policy(const FwdArgs<double>& d, const PairPolicyArgs& q, int rows, int fma, int64_t n_pairs, hipStream_t s) {
-  const dim3 grid((unsigned)n_pairs), block(64);
-  if (fma) {
-    if (rows == 2)      hipLaunchKernelGGL((pairhmm_pair_policy_kernel<2, true>), grid, block, 0, s, d, q);
-    else if (rows == 4) hipLaunchKernelGGL((pairhmm_pair_policy_kernel<4, true>), grid, block, 0, s, d, q);
-    else if (rows == kRplPair8) hipLaunchKernelGGL((pairhmm_pair_policy_kernel<kRplPair8, true>), grid, block, 0, s, d, q);
-    else                hipLaunchKernelGGL((pairhmm_pair_policy_kernel<kRplF64, true>), grid, block, 0, s, d, q);
-  } else {
-    if (rows == 2)      hipLaunchKernelGGL((pairhmm_pair_policy_kernel<2, false>), grid, block, 0, s, d, q);
-    else if (rows == 4) hipLaunchKernelGGL((pairhmm_pair_policy_kernel<4, false>), grid, block, 0, s, d, q);
-    else if (rows == kRplPair8) hipLaunchKernelGGL((pairhmm_pair_policy_kernel<kRplPair8, false>), grid, block, 0, s, d, q);
-    else                hipLaunchKernelGGL((pairhmm_pair_policy_kernel<kRplF64, false>), grid, block, 0, s, d, q);
-  }
-}
 
+// ---- the one-pair-per-wavefront kernels: a call of `rows` (by its longest read: pair_rows_for), or a set of calls whose
+// widest has them, launches the form pairhmm_pair_forms.h names.  Forms...: the instantiations the family has. ----
+static_assert(kRplF64 == kPairTiers[2] && kRplPair8 == kPairTiers[3], "the third and fourth tier by the names the kernels' comments use");
+template <int... Forms, typename F>
+int launch_pair_form(PairFamily family, bool is_set, int rows, int fma, F launch) {
+  if (dispatch_pair_form<Forms...>(pair_form(family, is_set, rows), fma != 0, launch)) return GKLHIP_OK;
+  return fail(GKLHIP_ERR_UNSUPPORTED, "no per-pair kernel of family %d for %d rows per lane", (int)family, rows);
+}
+// the policy on the fp32 sums + the fp64 recomputation of the pairs that fail it, one launch
+int launch_pair_policy(const FwdArgs<double>& d, const PairPolicyArgs& q, int rows, int fma, int64_t n_pairs, hipStream_t s) {
+  const dim3 grid((unsigned)n_pairs), block(64);
+  return launch_pair_form<2, 4, kRplF64, kRplPair8>(PairFamily::kPolicy, false, rows, fma, [&](auto maxr, auto fused_mul) { hipLaunchKernelGGL((pairhmm_pair_policy_kernel<maxr.value, fused_mul.value>), grid, block, 0, s, d, q); });
+}
+// the per-pair policy of a mid-size call in two launches (pairhmm_pair_flag_kernel): `list` holds n_pairs entries
+int launch_pair_policy_two_step(const FwdArgs<double>& d, const PairPolicyArgs& q, int rows, int fma, int64_t n_pairs, int32_t* list, hipStream_t s) {
+  hipLaunchKernelGGL(pairhmm_pair_flag_kernel, dim3((unsigned)multi_flag_blocks((int)n_pairs)), dim3(kFlagBlock), 0, s, q, (int32_t)n_pairs, list);
+  const dim3 grid((unsigned)multi_recompute_blocks((int)n_pairs)), block(64);
+  return launch_pair_form<2, 4, kRplF64, kRplPair8>(PairFamily::kRecompute, false, rows, fma, [&](auto maxr, auto fused_mul) { hipLaunchKernelGGL((pairhmm_pair_recompute_kernel<maxr.value, fused_mul.value>), grid, block, 0, s, d, q, list); });
+}
 // tiny calls: fp32 + policy + fp64 of ONE pair per wavefront in one launch (pairhmm_pair_fused_kernel)
-// `alone`: nothing else is on the device -- the fp64 recomputation of every pair runs beside its fp32 recurrence
+// `speculate`: nothing else is on the device -- the fp64 recomputation of every pair runs beside its fp32 recurrence
 // (pairhmm_pair_spec_kernel) and the call takes max(fp32, fp64) instead of fp32 + fp64
-void launch_pair_fused(const FwdArgs<float>& f, const FwdArgs<double>& d, const PairPolicyArgs& q, int rows, int fma, int64_t n_pairs,
-                       hipStream_t s, bool speculate = false) {
+int launch_pair_fused(const FwdArgs<float>& f, const FwdArgs<double>& d, const PairPolicyArgs& q, int rows, int fma, int64_t n_pairs,
+                      hipStream_t s, bool speculate = false) {
   // Opt-in (GKLHIP_SPECULATE_FP64=1, read when the context is made, and only for a call that is alone on the device): it pays when a good share of the pairs fails the policy (100 x 10 with
   // 16 % failing: 0.151 -> 0.130 ms per call) and costs when none does (0.100 -> 0.130: the fp64 wavefront of a pair takes
   // twice as long as its fp32 one) -- and real active regions are mostly of the second kind.
-  if (speculate && rows != kRplPair8) {   // (the speculating kernel has no 8-row form)
-    const dim3 grid((unsigned)n_pairs), block(128);
-    if (fma) hipLaunchKernelGGL((pairhmm_pair_spec_kernel<kRplF64, true>), grid, block, 0, s, f, d, q);
-    else     hipLaunchKernelGGL((pairhmm_pair_spec_kernel<kRplF64, false>), grid, block, 0, s, f, d, q);
-    return;
+  const dim3 grid((unsigned)n_pairs);
+  if (const int spec = speculate ? pair_spec_form(rows) : 0) {   // (0: the speculating kernel has no 8-row form)
+    const bool found = dispatch_pair_form<kRplF64>(spec, fma != 0, [&](auto maxr, auto fused_mul) { hipLaunchKernelGGL((pairhmm_pair_spec_kernel<maxr.value, fused_mul.value>), grid, dim3(128), 0, s, f, d, q); });
+    return found ? GKLHIP_OK : fail(GKLHIP_ERR_UNSUPPORTED, "no speculating per-pair kernel for %d rows per lane", rows);
   }
-  const dim3 grid((unsigned)n_pairs), block(64);
-  if (rows <= 4) {   // every read of the call has at most 255 bases: the four-wavefronts-per-SIMD variant
-    if (fma) hipLaunchKernelGGL((pairhmm_pair_fused_kernel<4, true>), grid, block, 0, s, f, d, q);
-    else     hipLaunchKernelGGL((pairhmm_pair_fused_kernel<4, false>), grid, block, 0, s, f, d, q);
-    return;
-  }
-  if (rows == kRplPair8) {   // a read of 384 to 511 bases in the call: two wavefronts per SIMD
-    if (fma) hipLaunchKernelGGL((pairhmm_pair_fused_kernel<kRplPair8, true>), grid, block, 0, s, f, d, q);
-    else     hipLaunchKernelGGL((pairhmm_pair_fused_kernel<kRplPair8, false>), grid, block, 0, s, f, d, q);
-    return;
-  }
-  if (fma) hipLaunchKernelGGL((pairhmm_pair_fused_kernel<kRplF64, true>), grid, block, 0, s, f, d, q);
-  else     hipLaunchKernelGGL((pairhmm_pair_fused_kernel<kRplF64, false>), grid, block, 0, s, f, d, q);
+  return launch_pair_form<4, kRplF64, kRplPair8>(PairFamily::kFused, false, rows, fma, [&](auto maxr, auto fused_mul) { hipLaunchKernelGGL((pairhmm_pair_fused_kernel<maxr.value, fused_mul.value>), grid, dim3(64), 0, s, f, d, q); });
 }
-
-// small calls of a double-precision context: every pair in fp64, ONE pair per wavefront (pairhmm_pair_f64_kernel); `rows`:
-// by the call's longest read -- up to 4: the four-wavefronts-per-SIMD variant; kRplPair8: reads of 384 to 511 bases, two
-void launch_pair_f64(const FwdArgs<double>& d, const PairPolicyArgs& q, int rows, int fma, int64_t n_pairs, hipStream_t s) {
+// small calls of a double-precision context: every pair in fp64, ONE pair per wavefront (pairhmm_pair_f64_kernel)
+int launch_pair_f64(const FwdArgs<double>& d, const PairPolicyArgs& q, int rows, int fma, int64_t n_pairs, hipStream_t s) {
   const dim3 grid((unsigned)n_pairs), block(64);
-  if (rows <= 4) {
-    if (fma) hipLaunchKernelGGL((pairhmm_pair_f64_kernel<4, true>), grid, block, 0, s, d, q);
-    else     hipLaunchKernelGGL((pairhmm_pair_f64_kernel<4, false>), grid, block, 0, s, d, q);
-    return;
+  return launch_pair_form<4, kRplF64, kRplPair8>(PairFamily::kF64, false, rows, fma, [&](auto maxr, auto fused_mul) { hipLaunchKernelGGL((pairhmm_pair_f64_kernel<maxr.value, fused_mul.value>), grid, block, 0, s, d, q); });
+}
+// ---- ... and the launches of a SET of small calls (SmallCombiner::launch_multi; pairhmm_aux_kernels.h: the *_multi_kernel
+// forms).  `m` holds the calls and where each call's blocks begin in this launch; `rows`: of the set's widest call. ----
+dim3 set_grid(const MultiArgs& m) { return dim3((unsigned)m.begin[m.n]); }
+int launch_pair_set(PairFamily family, const MultiArgs& m, int rows, int fma, hipStream_t s) {
+  const dim3 grid = set_grid(m), block(64);
+  switch (family) {
+    case PairFamily::kPolicy:
+      return launch_pair_form<kRplF64, kRplPair8>(family, true, rows, fma, [&](auto maxr, auto fused_mul) { hipLaunchKernelGGL((pair_policy_multi_kernel<fused_mul.value, maxr.value>), grid, block, 0, s, m); });
+    case PairFamily::kRecompute:
+      return launch_pair_form<2, 4, kRplF64, kRplPair8>(family, true, rows, fma, [&](auto maxr, auto fused_mul) { hipLaunchKernelGGL((pair_recompute_multi_kernel<fused_mul.value, maxr.value>), grid, block, 0, s, m); });
+    case PairFamily::kFused:
+      return launch_pair_form<4, kRplF64, kRplPair8>(family, true, rows, fma, [&](auto maxr, auto fused_mul) { hipLaunchKernelGGL((pair_fused_multi_kernel<fused_mul.value, maxr.value>), grid, block, 0, s, m); });
+    default:   // PairFamily::kF64
+      return launch_pair_form<4, kRplF64, kRplPair8>(family, true, rows, fma, [&](auto maxr, auto fused_mul) { hipLaunchKernelGGL((pair_f64_multi_kernel<fused_mul.value, maxr.value>), grid, block, 0, s, m); });
   }
-  if (rows == kRplPair8) {
-    if (fma) hipLaunchKernelGGL((pairhmm_pair_f64_kernel<kRplPair8, true>), grid, block, 0, s, d, q);
-    else     hipLaunchKernelGGL((pairhmm_pair_f64_kernel<kRplPair8, false>), grid, block, 0, s, d, q);
-    return;
-  }
-  if (fma) hipLaunchKernelGGL((pairhmm_pair_f64_kernel<kRplF64, true>), grid, block, 0, s, d, q);
-  else     hipLaunchKernelGGL((pairhmm_pair_f64_kernel<kRplF64, false>), grid, block, 0, s, d, q);
+}
+// the packed fp32 pass of a set (each call at its own rpl_main), and the packed fp64 pass of a set of mid-size regions of
+// double-precision contexts
+void launch_stream_f32_set(const MultiArgs& m, int fma, hipStream_t s) {
+  if (fma) hipLaunchKernelGGL((fwd_stream_multi_kernel<true, kRplF32>), set_grid(m), dim3(64), 0, s, m);
+  else     hipLaunchKernelGGL((fwd_stream_multi_kernel<false, kRplF32>), set_grid(m), dim3(64), 0, s, m);
+}
+void launch_stream_f64_set(const MultiArgs& m, int fma, hipStream_t s) {
+  if (fma) hipLaunchKernelGGL((fwd_stream_f64_multi_kernel<true, kRplF64Jobs>), set_grid(m), dim3(64), 0, s, m);
+  else     hipLaunchKernelGGL((fwd_stream_f64_multi_kernel<false, kRplF64Jobs>), set_grid(m), dim3(64), 0, s, m);
 }
 
 // A small plan (GATK-sized call) is PULLED from the pinned staging block by the prep kernel itself: no copy-engine hop at all.
@@ -409,8 +398,8 @@ bool double_mid_shares(const DevCtx* c, const CallPlan& P) {
 // (device-resident calls, multi-device contexts, record_events, GKL_HIP_COMBINE=0) keeps the general pass for such reads.
 static_assert(kRplPair8 == kRplF32 && kRplPair8 == kRplF64Wide, "the fourth tier: one wavefront at 8 rows per lane in both precisions");
 int small_read_len_max(const DevCtx* c, bool inline_host) {
-  const bool fourth_tier = c->small_read_limit == kLanes * kRplPair8 - 1 && deferral_offered(inline_host) && !c->multi_device && c->cfg.record_events == 0;
-  return kLanes * (fourth_tier ? kRplPair8 : kRplF64) - 1;
+  const bool fourth_tier = c->small_read_limit == pair_tier_len_max(kRplPair8) && deferral_offered(inline_host) && !c->multi_device && c->cfg.record_events == 0;
+  return pair_tier_len_max(fourth_tier ? kRplPair8 : kRplF64);
 }
 // `load` of pick_f32_rpl: 1 for a call that is not offered deferral.  (About half of the calls inside the library are on
 // the device at any moment, the others are being staged or finalised: 16 callers of 100 x 10 regions keep the 4-row
@@ -470,7 +459,7 @@ void plan_call(DevCtx* c, const gklhip_batch* db, int finalize_mode, bool inline
   // ... the tiny ones (one GATK active region) with the fp32 recurrence in the same wavefront and launch as the policy
   const int64_t fused_max = g_env.fused_max >= 0 ? g_env.fused_max : (int64_t)kTwoStepFrom;
   P.fused = P.per_pair && g_env.fused_pairs && P.n_pairs <= fused_max && P.n_long_main == 0 && c->cfg.rows_per_lane == 0;
-  P.rows = plan.max_read_len <= 2 * kLanes - 1 ? 2 : plan.max_read_len <= 4 * kLanes - 1 ? 4 : plan.max_read_len <= kLanes * kRplF64 - 1 ? kRplF64 : kRplPair8;
+  P.rows = pair_rows_for(plan.max_read_len);
   // a double-precision context: every pair through the same fp64 per-pair code, when the call's reads fit it (the shards
   // of a multi-device context keep the general pass: that mode is as it was)
   P.pair_double = P.use_double && !c->multi_device && plan.max_read_len <= pair_len_max;
@@ -852,12 +841,12 @@ int launch_per_pair(DevCtx* c, const CallPlan& P, const StagedCall& S, const Fwd
   const PairPolicyArgs q = pair_policy_args(c, P, S);
   if (ev) HIP_TRY(hipEventRecord(c->ev[3], s));
   if (P.fused) {
-    launch_pair_fused(a, d, q, P.rows, P.fma, P.n_pairs, s, c->speculate_fp64 && g_host_calls_in_flight.load(std::memory_order_relaxed) <= 1);
+    if (int rc = launch_pair_fused(a, d, q, P.rows, P.fma, P.n_pairs, s, c->speculate_fp64 && g_host_calls_in_flight.load(std::memory_order_relaxed) <= 1)) return rc;
   } else if (P.n_pairs > kTwoStepFrom) {
     if (int rc = c->fail_order.reserve((size_t)P.n_pairs * 4)) return rc;
-    launch_pair_policy_two_step(d, q, P.rows, P.fma, P.n_pairs, c->fail_order.as<int32_t>(), s);
+    if (int rc = launch_pair_policy_two_step(d, q, P.rows, P.fma, P.n_pairs, c->fail_order.as<int32_t>(), s)) return rc;
   } else {
-    launch_pair_policy(d, q, P.rows, P.fma, P.n_pairs, s);
+    if (int rc = launch_pair_policy(d, q, P.rows, P.fma, P.n_pairs, s)) return rc;
   }
   if (ev) HIP_TRY(hipEventRecord(c->ev[4], s));
   HIP_TRY(hipEventRecord(c->policy_done, s));

@@ -36,11 +36,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "pairhmm_pair_forms.h"
+
 namespace gklhip {
 
 constexpr uint32_t kEntIdle = 5u;           // stream entry: idle column (prior 0, no LDS row)
 constexpr uint32_t kEntSep = 0x80000000u;   // stream entry: separator | stream-order hap index
-constexpr int kLanes = 64;
+constexpr int kLanes = kPairLanes;           // 64: one wavefront
 // The haplotype stream is written by an earlier kernel and only read here: reading it through the constant address
 // space lets every (wave-uniform) entry load be a scalar s_load, also in the job-list kernel whose atomics make the
 // compiler treat plain global memory as clobbered (there the entries came through global_load_dwordx4 + vmcnt waits).
@@ -774,17 +776,19 @@ struct PairPolicyArgs {
 };
 constexpr int kModePackedWords = -2;
 
+// the result of a pair whose fp32 sum `v` passed the policy, as the call's finalisation mode wants it
+__device__ __forceinline__ void pair_store_fp32(const PairPolicyArgs& q, int64_t p, float v) {
+  if (q.mode == kModePackedWords) reinterpret_cast<uint64_t*>(q.out)[p] = kPackedF32Tag | (uint64_t)__float_as_uint(v);
+  else if (q.mode == 1) q.out[p] = log10((double)v) - q.log10_init32_as_f64;                        // GKLHIP_FINALIZE_DEVICE_F64
+  else if (q.mode == 2) q.out[p] = (double)((float)log10((double)v) - q.log10_init_f);             // GKLHIP_FINALIZE_DEVICE_REF32
+}
 // the policy's test on one pair; true: the pair must be recomputed in double precision
 __device__ __forceinline__ bool pair_policy_head(const PairPolicyArgs& q, int64_t p, int lane) {
   const float v = q.raw32[p];
   const bool fails = v < 1e-28f;  // NaN compares false and stays fp32, like the reference (IntelPairHmm.cc:159)
   if (lane == 0) q.used64[p] = fails ? 1 : 0;
   if (!fails) {
-    if (lane == 0) {
-      if (q.mode == kModePackedWords) reinterpret_cast<uint64_t*>(q.out)[p] = kPackedF32Tag | (uint64_t)__float_as_uint(v);
-      else if (q.mode == 1) q.out[p] = log10((double)v) - q.log10_init32_as_f64;                        // GKLHIP_FINALIZE_DEVICE_F64
-      else if (q.mode == 2) q.out[p] = (double)((float)log10((double)v) - q.log10_init_f);             // GKLHIP_FINALIZE_DEVICE_REF32
-    }
+    if (lane == 0) pair_store_fp32(q, p, v);
     return false;
   }
   if (lane == 0) atomicAdd(q.count, 1);
@@ -817,30 +821,43 @@ __device__ __forceinline__ void pair_policy_recompute(const FwdArgs<double>& a, 
 }
 // One pair per wavefront.  MAXR rows per lane hold the longest read of the call; a pair whose read fits fewer rows per
 // lane takes the narrower variant (same number of steps, half the instructions per step): 2 rows up to 127 bases, 4 up to
-// 255, 6 up to 383, else MAXR.
-// kRplPair8: the fourth tier of the per-pair kernel families, reads of 384 to 511 bases (small_read_limit 511) -- what one
-// wavefront holds at 8 rows per lane in both precisions (fp32: pair_fp32_alone<8>, fp64: the f64r8 programs of the wide
-// long-read kernel).  Its kernels run two wavefronts per SIMD (pair_waves_per_eu).
-constexpr int kRplPair8 = 8;
-constexpr int pair_waves_per_eu(int maxr) { return maxr <= 4 ? 4 : maxr <= 6 ? 3 : 2; }
-// (the LDS maxima below name the 2-, 4- and MAXR-row tables; an 8-row kernel's ladder also takes the 6-row one)
-template <int MAXR, bool FMA> constexpr bool pair_lds_holds_6(int bytes) { return MAXR <= 6 || WaveJob<double, 6, FMA>::kLdsBytes <= bytes; }
+// 255, 6 up to 383, else MAXR.  pairhmm_pair_forms.h states the tiers, which MAXR each kernel family is launched with, and
+// the occupancy of each form: a tier or a form is added there.
+constexpr int kPairLen2 = pair_tier_len_max(2), kPairLen4 = pair_tier_len_max(4), kPairLen6 = pair_tier_len_max(6);   // 127, 255, 383 bases
+template <int MAXR, bool FMA, bool MARK = false>
+__device__ __forceinline__ void pair_recompute_by_rows(const FwdArgs<double>& a, const PairPolicyArgs& q, int64_t p, int r, int R, int k,
+                                                       unsigned char* lds) {
+  if (MAXR > 2 && R <= kPairLen2)      pair_policy_recompute<2, FMA, MARK>(a, q, p, r, R, k, lds);
+  else if (MAXR > 4 && R <= kPairLen4) pair_policy_recompute<4, FMA, MARK>(a, q, p, r, R, k, lds);
+  else if (MAXR > 6 && R <= kPairLen6) pair_policy_recompute<6, FMA, MARK>(a, q, p, r, R, k, lds);
+  else                                 pair_policy_recompute<MAXR, FMA, MARK>(a, q, p, r, R, k, lds);
+}
+// LDS of a recomputing wavefront: the fp64 table of the widest variant that ladder may take (the 2-, 4- and MAXR-row tables;
+// an 8-row kernel's ladder also takes the 6-row one) ...
+template <int MAXR, bool FMA>
+constexpr int pair_lds_f64() {
+  constexpr int k2 = WaveJob<double, 2, FMA>::kLdsBytes, k4 = WaveJob<double, 4, FMA>::kLdsBytes, kR = WaveJob<double, MAXR, FMA>::kLdsBytes;
+  constexpr int bytes = kR > k4 ? (kR > k2 ? kR : k2) : (k4 > k2 ? k4 : k2);
+  static_assert(MAXR <= 6 || WaveJob<double, 6, FMA>::kLdsBytes <= bytes, "LDS of the widest job");
+  return bytes;
+}
+// ... and of a fused one, whose fp32 table (4 rows, or 8 from MAXR64 = 6 on: pair_fused_block) lies in the same bytes first
+template <int MAXR64, bool FMA>
+constexpr int pair_lds_fused() {
+  constexpr int k32 = WaveJob<float, (MAXR64 <= 4 ? 4 : 8), FMA>::kLdsBytes, k64 = pair_lds_f64<MAXR64, FMA>();
+  return k32 > k64 ? k32 : k64;
+}
 template <int MAXR, bool FMA>
 __device__ __forceinline__ void pair_policy_block(const FwdArgs<double>& a, const PairPolicyArgs& q, int64_t p, unsigned char* lds) {
   const int lane = threadIdx.x;
   if (!pair_policy_head(q, p, lane)) return;
   const int r = (int)(p / a.b.n_haps), k = q.hap_sidx[(int)(p - (int64_t)r * a.b.n_haps)];
   const int R = (int)(a.b.read_off[r + 1] - a.b.read_off[r]);
-  if (MAXR > 2 && R <= 2 * kLanes - 1)      pair_policy_recompute<2, FMA>(a, q, p, r, R, k, lds);
-  else if (MAXR > 4 && R <= 4 * kLanes - 1) pair_policy_recompute<4, FMA>(a, q, p, r, R, k, lds);
-  else if (MAXR > 6 && R <= 6 * kLanes - 1) pair_policy_recompute<6, FMA>(a, q, p, r, R, k, lds);
-  else                                      pair_policy_recompute<MAXR, FMA>(a, q, p, r, R, k, lds);
+  pair_recompute_by_rows<MAXR, FMA>(a, q, p, r, R, k, lds);
 }
 template <int RPL, bool FMA>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(RPL <= 6 ? 3 : 2))) void pairhmm_pair_policy_kernel(FwdArgs<double> a, PairPolicyArgs q) {
-  constexpr int kLds2 = WaveJob<double, 2, FMA>::kLdsBytes, kLds4 = WaveJob<double, 4, FMA>::kLdsBytes, kLdsR = WaveJob<double, RPL, FMA>::kLdsBytes;
-  __shared__ __attribute__((aligned(16))) unsigned char lds[kLdsR > kLds4 ? (kLdsR > kLds2 ? kLdsR : kLds2) : (kLds4 > kLds2 ? kLds4 : kLds2)];
-  static_assert(pair_lds_holds_6<RPL, FMA>((int)sizeof lds), "LDS of the widest job");
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(pair_policy_waves_per_eu(RPL)))) void pairhmm_pair_policy_kernel(FwdArgs<double> a, PairPolicyArgs q) {
+  __shared__ __attribute__((aligned(16))) unsigned char lds[pair_lds_f64<RPL, FMA>()];
   pair_policy_block<RPL, FMA>(a, q, (int64_t)blockIdx.x, lds);
 }
 
@@ -882,45 +899,26 @@ __device__ __forceinline__ void pair_fused_block(const FwdArgs<float>& f, const 
   //  kernel, 128 VGPRs, four wavefronts per SIMD instead of three: these wavefronts wait on their own dependent chains,
   //  so a SIMD's throughput under many concurrent callers is the number of wavefronts it holds)
   float v;
-  if (R <= 2 * kLanes - 1)                     v = pair_fp32_alone<2, FMA>(f, p, r, R, k, lds);
-  else if (MAXR64 <= 4 || R <= 4 * kLanes - 1) v = pair_fp32_alone<4, FMA>(f, p, r, R, k, lds);
-  else                                         v = pair_fp32_alone<8, FMA>(f, p, r, R, k, lds);   // (up to 511 bases: what MAXR64 == kRplPair8 admits)
+  if (R <= kPairLen2)                     v = pair_fp32_alone<2, FMA>(f, p, r, R, k, lds);
+  else if (MAXR64 <= 4 || R <= kPairLen4) v = pair_fp32_alone<4, FMA>(f, p, r, R, k, lds);
+  else                                    v = pair_fp32_alone<8, FMA>(f, p, r, R, k, lds);   // (up to 511 bases: what MAXR64 == kRplPair8 admits)
   const bool fails = v < 1e-28f;  // NaN compares false and stays fp32, like the reference (IntelPairHmm.cc:159)
   if (lane == 0) {
     q.used64[p] = fails ? 1 : 0;
     if (fails) atomicAdd(q.count, 1);
-    else if (q.mode == kModePackedWords) reinterpret_cast<uint64_t*>(q.out)[p] = kPackedF32Tag | (uint64_t)__float_as_uint(v);
-    else if (q.mode == 1) q.out[p] = log10((double)v) - q.log10_init32_as_f64;                        // GKLHIP_FINALIZE_DEVICE_F64
-    else if (q.mode == 2) q.out[p] = (double)((float)log10((double)v) - q.log10_init_f);             // GKLHIP_FINALIZE_DEVICE_REF32
+    else pair_store_fp32(q, p, v);
   }
   if (!fails) return;
   __syncthreads();  // the fp32 table's readers are done: the fp64 table takes its place
-  if (MAXR64 > 2 && R <= 2 * kLanes - 1)      pair_policy_recompute<2, FMA>(d, q, p, r, R, k, lds);
-  else if (MAXR64 > 4 && R <= 4 * kLanes - 1) pair_policy_recompute<4, FMA>(d, q, p, r, R, k, lds);
-  else if (MAXR64 > 6 && R <= 6 * kLanes - 1) pair_policy_recompute<6, FMA>(d, q, p, r, R, k, lds);
-  else                                        pair_policy_recompute<MAXR64, FMA>(d, q, p, r, R, k, lds);
+  pair_recompute_by_rows<MAXR64, FMA>(d, q, p, r, R, k, lds);
 }
-template <int MAXR64, bool FMA>
-struct PairFusedLds {
-  static constexpr int a = WaveJob<float, (MAXR64 <= 4 ? 4 : 8), FMA>::kLdsBytes, b = WaveJob<double, 2, FMA>::kLdsBytes,
-                       c = WaveJob<double, 4, FMA>::kLdsBytes, d = WaveJob<double, MAXR64, FMA>::kLdsBytes;
-  static constexpr int ab = a > b ? a : b, cd = c > d ? c : d, bytes = ab > cd ? ab : cd;
-  static_assert(pair_lds_holds_6<MAXR64, FMA>(bytes), "LDS of the widest job");
-};
 template <int MAXR64, bool FMA>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(pair_waves_per_eu(MAXR64)))) void pairhmm_pair_fused_kernel(FwdArgs<float> f, FwdArgs<double> d,
                                                                                                        PairPolicyArgs q) {
-  __shared__ __attribute__((aligned(16))) unsigned char lds[PairFusedLds<MAXR64, FMA>::bytes];
+  __shared__ __attribute__((aligned(16))) unsigned char lds[pair_lds_fused<MAXR64, FMA>()];
   pair_fused_block<MAXR64, FMA>(f, d, q, (int64_t)blockIdx.x, lds);
 }
 
-// LDS of a recomputing wavefront: the table of the widest variant it may take
-template <int MAXR, bool FMA>
-struct PairRecomputeLds {
-  static constexpr int k2 = WaveJob<double, 2, FMA>::kLdsBytes, k4 = WaveJob<double, 4, FMA>::kLdsBytes, kR = WaveJob<double, MAXR, FMA>::kLdsBytes;
-  static constexpr int bytes = kR > k4 ? (kR > k2 ? kR : k2) : (k4 > k2 ? k4 : k2);
-  static_assert(pair_lds_holds_6<MAXR, FMA>(bytes), "LDS of the widest job");
-};
 // Small calls of a double-precision context (gklhip_config.use_double; kSmallDouble): EVERY pair in double precision, one
 // pair per wavefront in one launch behind the preparation -- the fp64 recurrence of the fused kernel's failing pairs with
 // no fp32 recurrence and no policy in front.  The read is alone in the wavefront, rows per lane by its own length; the lane
@@ -930,10 +928,7 @@ template <int MAXR, bool FMA>
 __device__ __forceinline__ void pair_f64_block(const FwdArgs<double>& d, const PairPolicyArgs& q, int64_t p, unsigned char* lds) {
   const int r = (int)(p / d.b.n_haps), k = q.hap_sidx[(int)(p - (int64_t)r * d.b.n_haps)];
   const int R = (int)(d.b.read_off[r + 1] - d.b.read_off[r]);
-  if (MAXR > 2 && R <= 2 * kLanes - 1)      pair_policy_recompute<2, FMA, true>(d, q, p, r, R, k, lds);
-  else if (MAXR > 4 && R <= 4 * kLanes - 1) pair_policy_recompute<4, FMA, true>(d, q, p, r, R, k, lds);
-  else if (MAXR > 6 && R <= 6 * kLanes - 1) pair_policy_recompute<6, FMA, true>(d, q, p, r, R, k, lds);
-  else                                      pair_policy_recompute<MAXR, FMA, true>(d, q, p, r, R, k, lds);
+  pair_recompute_by_rows<MAXR, FMA, true>(d, q, p, r, R, k, lds);
 }
 // MAXR = 4: the variant for calls whose reads have at most 255 bases (no kRplF64 code in the kernel: four wavefronts per
 // SIMD, as the narrow fused kernel); MAXR = kRplF64: reads of up to 383 bases, three; MAXR = kRplPair8: up to 511, two.
@@ -941,7 +936,7 @@ __device__ __forceinline__ void pair_f64_block(const FwdArgs<double>& d, const P
 // of the forward kernels), said as constants: the device log10 of the other finalisation modes is not compiled in.
 template <int MAXR, bool FMA>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(pair_waves_per_eu(MAXR)))) void pairhmm_pair_f64_kernel(FwdArgs<double> d, PairPolicyArgs q) {
-  __shared__ __attribute__((aligned(16))) unsigned char lds[PairRecomputeLds<MAXR, FMA>::bytes];
+  __shared__ __attribute__((aligned(16))) unsigned char lds[pair_lds_f64<MAXR, FMA>()];
   d.packed_out = nullptr;
   q.mode = kModePackedWords;
   pair_f64_block<MAXR, FMA>(d, q, (int64_t)blockIdx.x, lds);
@@ -953,11 +948,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(pair_waves_p
 // way GATK runs), where nothing else wants those SIMDs and the call's latency is its longest dependent chain:
 // max(fp32, fp64) instead of fp32 + fp64.  (No 8-row form: a call with a read of 384 bases or more does not speculate.)
 template <int MAXR64, bool FMA>
-__global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(3))) void pairhmm_pair_spec_kernel(FwdArgs<float> f, FwdArgs<double> d,
+__global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(pair_waves_per_eu(MAXR64)))) void pairhmm_pair_spec_kernel(FwdArgs<float> f, FwdArgs<double> d,
                                                                                                         PairPolicyArgs q) {
-  constexpr int kL2 = WaveJob<double, 2, FMA>::kLdsBytes, kL4 = WaveJob<double, 4, FMA>::kLdsBytes, kLR = WaveJob<double, MAXR64, FMA>::kLdsBytes;
+  static_assert(pair_spec_form(MAXR64) == MAXR64, "the speculating kernel's one form");
   __shared__ __attribute__((aligned(16))) unsigned char lds32[WaveJob<float, 8, FMA>::kLdsBytes];
-  __shared__ __attribute__((aligned(16))) unsigned char lds64[kLR > kL4 ? (kLR > kL2 ? kLR : kL2) : (kL4 > kL2 ? kL4 : kL2)];
+  __shared__ __attribute__((aligned(16))) unsigned char lds64[pair_lds_f64<MAXR64, FMA>()];
   __shared__ float s_v;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int64_t p = blockIdx.x;
@@ -965,16 +960,14 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(3))) void p
   const int R = (int)(f.b.read_off[r + 1] - f.b.read_off[r]);
   if (wave == 0) {
     float v;
-    if (R <= 2 * kLanes - 1)      v = pair_fp32_alone<2, FMA>(f, p, r, R, k, lds32);
-    else if (R <= 4 * kLanes - 1) v = pair_fp32_alone<4, FMA>(f, p, r, R, k, lds32);
-    else                          v = pair_fp32_alone<8, FMA>(f, p, r, R, k, lds32);
+    if (R <= kPairLen2)      v = pair_fp32_alone<2, FMA>(f, p, r, R, k, lds32);
+    else if (R <= kPairLen4) v = pair_fp32_alone<4, FMA>(f, p, r, R, k, lds32);
+    else                     v = pair_fp32_alone<8, FMA>(f, p, r, R, k, lds32);
     if (lane == 0) s_v = v;
   } else {
     PairPolicyArgs none = q;
     none.mode = -1;   // the raw fp64 sum only: whether it is wanted is decided below
-    if (MAXR64 > 2 && R <= 2 * kLanes - 1)      pair_policy_recompute<2, FMA>(d, none, p, r, R, k, lds64);
-    else if (MAXR64 > 4 && R <= 4 * kLanes - 1) pair_policy_recompute<4, FMA>(d, none, p, r, R, k, lds64);
-    else                                        pair_policy_recompute<MAXR64, FMA>(d, none, p, r, R, k, lds64);
+    pair_recompute_by_rows<MAXR64, FMA>(d, none, p, r, R, k, lds64);
     __threadfence();  // the sum (a global store of this wavefront's last lane) before the barrier
   }
   __syncthreads();
@@ -987,9 +980,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(3))) void p
       const double sum = __hip_atomic_load(d.raw + p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       if (q.mode == kModePackedWords) reinterpret_cast<uint64_t*>(q.out)[p] = packed_word(sum);
       else if (q.mode >= 0) q.out[p] = log10(sum) - q.log10_init_d;
-    } else if (q.mode == kModePackedWords) reinterpret_cast<uint64_t*>(q.out)[p] = kPackedF32Tag | (uint64_t)__float_as_uint(v);
-    else if (q.mode == 1) q.out[p] = log10((double)v) - q.log10_init32_as_f64;                        // GKLHIP_FINALIZE_DEVICE_F64
-    else if (q.mode == 2) q.out[p] = (double)((float)log10((double)v) - q.log10_init_f);             // GKLHIP_FINALIZE_DEVICE_REF32
+    } else pair_store_fp32(q, p, v);
   }
 }
 
@@ -1008,11 +999,7 @@ __device__ __forceinline__ void pair_flag_block(const PairPolicyArgs& q, int32_t
     const float v = q.raw32[p];
     fails = v < 1e-28f;  // NaN compares false and stays fp32, like the reference (IntelPairHmm.cc:159)
     q.used64[p] = fails ? 1 : 0;
-    if (!fails) {
-      if (q.mode == kModePackedWords) reinterpret_cast<uint64_t*>(q.out)[p] = kPackedF32Tag | (uint64_t)__float_as_uint(v);
-      else if (q.mode == 1) q.out[p] = log10((double)v) - q.log10_init32_as_f64;                        // GKLHIP_FINALIZE_DEVICE_F64
-      else if (q.mode == 2) q.out[p] = (double)((float)log10((double)v) - q.log10_init_f);             // GKLHIP_FINALIZE_DEVICE_REF32
-    }
+    if (!fails) pair_store_fp32(q, p, v);
   }
   const uint64_t m = __ballot(fails);
   if (m) {
@@ -1035,17 +1022,14 @@ __device__ __forceinline__ void pair_recompute_block(const FwdArgs<double>& a, c
     const int64_t p = list[i];
     const int r = (int)(p / a.b.n_haps), k = q.hap_sidx[(int)(p - (int64_t)r * a.b.n_haps)];
     const int R = (int)(a.b.read_off[r + 1] - a.b.read_off[r]);
-    if (MAXR > 2 && R <= 2 * kLanes - 1)      pair_policy_recompute<2, FMA>(a, q, p, r, R, k, lds);
-    else if (MAXR > 4 && R <= 4 * kLanes - 1) pair_policy_recompute<4, FMA>(a, q, p, r, R, k, lds);
-    else if (MAXR > 6 && R <= 6 * kLanes - 1) pair_policy_recompute<6, FMA>(a, q, p, r, R, k, lds);
-    else                                      pair_policy_recompute<MAXR, FMA>(a, q, p, r, R, k, lds);
+    pair_recompute_by_rows<MAXR, FMA>(a, q, p, r, R, k, lds);
     __syncthreads();  // (a block that takes a second pair reuses the prior table)
   }
 }
 template <int MAXR, bool FMA>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MAXR <= 6 ? 3 : 2))) void pairhmm_pair_recompute_kernel(FwdArgs<double> a, PairPolicyArgs q,
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(pair_policy_waves_per_eu(MAXR)))) void pairhmm_pair_recompute_kernel(FwdArgs<double> a, PairPolicyArgs q,
                                                                                                            const int32_t* list) {
-  __shared__ __attribute__((aligned(16))) unsigned char lds[PairRecomputeLds<MAXR, FMA>::bytes];
+  __shared__ __attribute__((aligned(16))) unsigned char lds[pair_lds_f64<MAXR, FMA>()];
   pair_recompute_block<MAXR, FMA>(a, q, list, (int)blockIdx.x, (int)gridDim.x, lds);
 }
 

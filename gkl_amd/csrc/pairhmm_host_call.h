@@ -107,89 +107,61 @@ struct SmallCombiner {
 
   int launch_single(const SmallCall& k, hipStream_t s, bool alone) {
     hipLaunchKernelGGL(prep_kernel, dim3((unsigned)k.prep_grid), dim3(kPrepBlock), 0, s, k.prep);
+    int rc;
     if (k.kind == kSmallDouble) {
-      launch_pair_f64(k.d, k.q, k.rows, k.fma, k.n_pairs, s);
+      rc = launch_pair_f64(k.d, k.q, k.rows, k.fma, k.n_pairs, s);
     } else if (k.fused) {
-      launch_pair_fused(k.f, k.d, k.q, k.rows, k.fma, k.n_pairs, s, alone && k.speculate);
+      rc = launch_pair_fused(k.f, k.d, k.q, k.rows, k.fma, k.n_pairs, s, alone && k.speculate);
     } else {
       launch_main_f32(k.f, k.rpl_main, k.fma, k.main_blocks, s);
-      launch_pair_policy(k.d, k.q, k.rows, k.fma, k.n_pairs, s);
+      rc = launch_pair_policy(k.d, k.q, k.rows, k.fma, k.n_pairs, s);
     }
+    if (rc) return rc;
     HIP_TRY(hipGetLastError());
     return GKLHIP_OK;
   }
+  // One set of launches for calls[0 .. n) (every call of a set is of one kind: a leader only takes calls like its own, a
+  // multi call cuts its sets by kind).  The kernel forms are the launchers' business (pairhmm_device_pass.h).
   int launch_multi(const SmallLaunch* const* calls, int n, int fma, Slot& sl) {
-    const bool two_step = calls[0]->call.kind == kSmallTwoStep;   // a set of mid-size regions (gklhip_compute_multi only)
-    MultiArgs mp{}, mf{}, mq{};
-    mp.n = mf.n = mq.n = n;
-    int32_t prep_blocks[kMultiMax], main_blocks[kMultiMax], pair_blocks[kMultiMax];   // pair_blocks: the policy launch (two-step: the flag launch)
-    for (int i = 0; i < n; i++) {
-      const SmallLaunch& L = *calls[i];
-      mp.call[i] = L.desc_pinned; mf.call[i] = L.desc_dev; mq.call[i] = L.desc_dev;
-      prep_blocks[i] = L.call.prep_grid; main_blocks[i] = L.call.main_blocks; pair_blocks[i] = two_step ? L.call.flag_grid : L.call.n_pairs;
+    // a launch's table: each call's descriptor (prep reads the pinned one) and where its `blocks` blocks begin
+    auto set_of = [&](const SmallCall* SmallLaunch::*desc, int32_t SmallCall::*blocks) {
+      MultiArgs m{};
+      int32_t per_call[kMultiMax];
+      for (int i = 0; i < n; i++) { m.call[i] = calls[i]->*desc; per_call[i] = calls[i]->call.*blocks; }
+      m.n = n;
+      multi_begin(per_call, n, m.begin);
+      return m;
+    };
+    const auto dev = &SmallLaunch::desc_dev;
+    int rows = kPairTiers[0];   // of the set's widest call
+    for (int i = 0; i < n; i++) rows = std::max(rows, calls[i]->call.rows);
+    hipStream_t s = sl.stream;
+    const MultiArgs mp = set_of(&SmallLaunch::desc_pinned, &SmallCall::prep_grid);
+    hipLaunchKernelGGL(prep_multi_kernel, set_grid(mp), dim3(kPrepBlock), 0, s, mp);
+    int rc = GKLHIP_OK;
+    switch (calls[0]->call.kind) {
+      case kSmallTwoStep: {   // mid-size regions (gklhip_compute_multi only): the packed fp32 pass, then the policy in two launches
+        launch_stream_f32_set(set_of(dev, &SmallCall::main_blocks), fma, s);
+        const MultiArgs mg = set_of(dev, &SmallCall::flag_grid);
+        hipLaunchKernelGGL(pair_flag_multi_kernel, set_grid(mg), dim3(kFlagBlock), 0, s, mg);
+        rc = launch_pair_set(PairFamily::kRecompute, set_of(dev, &SmallCall::recompute_grid), rows, fma, s);
+      } break;
+      case kSmallDoubleStream: {   // mid-size regions of a double-precision context: the packed fp64 pass, then its packed words
+        launch_stream_f64_set(set_of(dev, &SmallCall::main_blocks), fma, s);
+        const MultiArgs mg = set_of(dev, &SmallCall::flag_grid);
+        hipLaunchKernelGGL(finalize64_multi_kernel, set_grid(mg), dim3(kFlagBlock), 0, s, mg);
+      } break;
+      case kSmallDouble:   // calls of double-precision contexts: one launch, a block per pair, every pair in fp64
+        rc = launch_pair_set(PairFamily::kF64, set_of(dev, &SmallCall::n_pairs), rows, fma, s);
+        break;
+      case kSmallFused:    // (exactly the calls with `fused` set: small_call_kind)
+        rc = launch_pair_set(PairFamily::kFused, set_of(dev, &SmallCall::n_pairs), rows, fma, s);
+        break;
+      default:             // kSmallOneLaunch: the one-launch policy behind the packed fp32 pass
+        launch_stream_f32_set(set_of(dev, &SmallCall::main_blocks), fma, s);
+        rc = launch_pair_set(PairFamily::kPolicy, set_of(dev, &SmallCall::n_pairs), rows, fma, s);
     }
-    multi_begin(prep_blocks, n, mp.begin);
-    multi_begin(main_blocks, n, mf.begin);
-    multi_begin(pair_blocks, n, mq.begin);
-    hipLaunchKernelGGL(prep_multi_kernel, dim3((unsigned)mp.begin[n]), dim3(kPrepBlock), 0, sl.stream, mp);
-    if (two_step) {   // the packed fp32 pass, then the policy in two launches
-      MultiArgs mr = mq;
-      int32_t rec_blocks[kMultiMax];
-      int rows = 2;   // of the set's longest read
-      for (int i = 0; i < n; i++) { rec_blocks[i] = calls[i]->call.recompute_grid; rows = std::max(rows, calls[i]->call.rows); }
-      multi_begin(rec_blocks, n, mr.begin);
-      const dim3 grid((unsigned)mr.begin[n]), block(64);
-      if (fma) hipLaunchKernelGGL((fwd_stream_multi_kernel<true, kRplF32>), dim3((unsigned)mf.begin[n]), dim3(64), 0, sl.stream, mf);
-      else     hipLaunchKernelGGL((fwd_stream_multi_kernel<false, kRplF32>), dim3((unsigned)mf.begin[n]), dim3(64), 0, sl.stream, mf);
-      hipLaunchKernelGGL(pair_flag_multi_kernel, dim3((unsigned)mq.begin[n]), dim3(kFlagBlock), 0, sl.stream, mq);
-      if (fma) {
-        if (rows == 2)      hipLaunchKernelGGL((pair_recompute_multi_kernel<true, 2>), grid, block, 0, sl.stream, mr);
-        else if (rows == 4) hipLaunchKernelGGL((pair_recompute_multi_kernel<true, 4>), grid, block, 0, sl.stream, mr);
-        else if (rows == kRplPair8) hipLaunchKernelGGL((pair_recompute_multi_kernel<true, kRplPair8>), grid, block, 0, sl.stream, mr);
-        else                hipLaunchKernelGGL((pair_recompute_multi_kernel<true, kRplF64>), grid, block, 0, sl.stream, mr);
-      } else {
-        if (rows == 2)      hipLaunchKernelGGL((pair_recompute_multi_kernel<false, 2>), grid, block, 0, sl.stream, mr);
-        else if (rows == 4) hipLaunchKernelGGL((pair_recompute_multi_kernel<false, 4>), grid, block, 0, sl.stream, mr);
-        else if (rows == kRplPair8) hipLaunchKernelGGL((pair_recompute_multi_kernel<false, kRplPair8>), grid, block, 0, sl.stream, mr);
-        else                hipLaunchKernelGGL((pair_recompute_multi_kernel<false, kRplF64>), grid, block, 0, sl.stream, mr);
-      }
-    } else if (calls[0]->call.kind == kSmallDoubleStream) {   // mid-size regions of a double-precision context: the packed fp64 pass, then its packed words
-      for (int i = 0; i < n; i++) pair_blocks[i] = calls[i]->call.flag_grid;
-      multi_begin(pair_blocks, n, mq.begin);
-      if (fma) hipLaunchKernelGGL((fwd_stream_f64_multi_kernel<true, kRplF64Jobs>), dim3((unsigned)mf.begin[n]), dim3(64), 0, sl.stream, mf);
-      else     hipLaunchKernelGGL((fwd_stream_f64_multi_kernel<false, kRplF64Jobs>), dim3((unsigned)mf.begin[n]), dim3(64), 0, sl.stream, mf);
-      hipLaunchKernelGGL(finalize64_multi_kernel, dim3((unsigned)mq.begin[n]), dim3(kFlagBlock), 0, sl.stream, mq);
-    } else if (calls[0]->call.kind == kSmallDouble) {   // calls of double-precision contexts: one launch, every pair in fp64
-      bool narrow = true, tier8 = false;   // as below
-      for (int i = 0; i < n; i++) { narrow = narrow && calls[i]->call.rows <= 4; tier8 = tier8 || calls[i]->call.rows == kRplPair8; }
-      const dim3 grid((unsigned)mq.begin[n]), block(64);
-      if (tier8 && fma)   hipLaunchKernelGGL((pair_f64_multi_kernel<true, kRplPair8>), grid, block, 0, sl.stream, mq);
-      else if (tier8)     hipLaunchKernelGGL((pair_f64_multi_kernel<false, kRplPair8>), grid, block, 0, sl.stream, mq);
-      else if (narrow && fma)  hipLaunchKernelGGL((pair_f64_multi_kernel<true, 4>), grid, block, 0, sl.stream, mq);
-      else if (narrow)    hipLaunchKernelGGL((pair_f64_multi_kernel<false, 4>), grid, block, 0, sl.stream, mq);
-      else if (fma)       hipLaunchKernelGGL((pair_f64_multi_kernel<true, kRplF64>), grid, block, 0, sl.stream, mq);
-      else                hipLaunchKernelGGL((pair_f64_multi_kernel<false, kRplF64>), grid, block, 0, sl.stream, mq);
-    } else if (calls[0]->call.fused) {  // (every call of a set is of one kind: a leader only takes calls like its own, a multi call cuts its sets by kind)
-      bool narrow = true, tier8 = false;   // narrow: reads of at most 255 bases in every call of the set, the four-wavefronts-per-SIMD variant; tier8: a read of 384 to 511 bases in one of them, the 8-row form for the whole set
-      for (int i = 0; i < n; i++) { narrow = narrow && calls[i]->call.rows <= 4; tier8 = tier8 || calls[i]->call.rows == kRplPair8; }
-      const dim3 grid((unsigned)mq.begin[n]), block(64);
-      if (tier8 && fma)   hipLaunchKernelGGL((pair_fused_multi_kernel<true, kRplPair8>), grid, block, 0, sl.stream, mq);
-      else if (tier8)     hipLaunchKernelGGL((pair_fused_multi_kernel<false, kRplPair8>), grid, block, 0, sl.stream, mq);
-      else if (narrow && fma)  hipLaunchKernelGGL((pair_fused_multi_kernel<true, 4>), grid, block, 0, sl.stream, mq);
-      else if (narrow)    hipLaunchKernelGGL((pair_fused_multi_kernel<false, 4>), grid, block, 0, sl.stream, mq);
-      else if (fma)       hipLaunchKernelGGL((pair_fused_multi_kernel<true, kRplF64>), grid, block, 0, sl.stream, mq);
-      else                hipLaunchKernelGGL((pair_fused_multi_kernel<false, kRplF64>), grid, block, 0, sl.stream, mq);
-    } else {   // the one-launch policy behind the packed fp32 pass: the 8-row form when a call of the set holds a read of 384 to 511 bases
-      bool tier8 = false;
-      for (int i = 0; i < n; i++) tier8 = tier8 || calls[i]->call.rows == kRplPair8;
-      const dim3 grid((unsigned)mq.begin[n]), block(64);
-      if (fma) hipLaunchKernelGGL((fwd_stream_multi_kernel<true, kRplF32>), dim3((unsigned)mf.begin[n]), dim3(64), 0, sl.stream, mf);
-      else     hipLaunchKernelGGL((fwd_stream_multi_kernel<false, kRplF32>), dim3((unsigned)mf.begin[n]), dim3(64), 0, sl.stream, mf);
-      if (tier8 && fma) hipLaunchKernelGGL((pair_policy_multi_kernel<true, kRplPair8>), grid, block, 0, sl.stream, mq);
-      else if (tier8)   hipLaunchKernelGGL((pair_policy_multi_kernel<false, kRplPair8>), grid, block, 0, sl.stream, mq);
-      else if (fma)     hipLaunchKernelGGL((pair_policy_multi_kernel<true, kRplF64>), grid, block, 0, sl.stream, mq);
-      else              hipLaunchKernelGGL((pair_policy_multi_kernel<false, kRplF64>), grid, block, 0, sl.stream, mq);
-    }
+    if (rc) return rc;
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(sl.ev, sl.stream));
     return GKLHIP_OK;
