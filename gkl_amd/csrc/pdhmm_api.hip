@@ -24,7 +24,8 @@
 #include "pdhmm_kernel.h"
 #include "pdhmm_remote.h"
 #include "pairhmm_plan.h"
-#include "hip_host_common.h"       // g_err / fail / guarded / HIP_TRY, DevBuf, PinBuf
+#include "pdhmm_job_layout.h"      // pd_up, PdInputLayout, PdJobOffsets / PdJobLayout, PdTabxLayout
+#include "hip_host_common.h"      // g_err / fail / guarded / HIP_TRY, DevBuf, PinBuf
 #include "pairhmm_host_finalize.h"   // gklhip::WorkerPool: persistent threads for the host log10
 
 using namespace gklhip;
@@ -380,23 +381,57 @@ constexpr size_t kPdStageBytes = (size_t)4 << 20;
 // misc: 64 int32 of flags and job counters (the first 256 bytes, cleared by every call), then the per-region input-error
 // flags of a multi-region call
 constexpr size_t kPdMiscBytes = 256 + 4 * (size_t)kPdMaxRegions;
-// Up to this many pairs (1 MB of sums) the kernels store the sums straight into pinned host memory (pd_run_locked:
+// Up to this many pairs (1 MB of sums) the kernels store the sums straight into pinned host memory (pd_plan_counts:
 // sums_direct).  A multi-region call has no other way to return them, so this is also the most pairs it takes: both
 // paths depend on the one constant.
 constexpr size_t kPdMultiMaxPairs = 131072;
-inline size_t pd_up(size_t x) { return (x + 255) / 256 * 256; }
-// The nine input arrays of a call (of a multi-region call: of all its regions, at the common row strides) in ONE block,
-// each 256-byte aligned: the layout of the device buffer `inputs` and of the pinned block `stage_in`, and the size that
-// decides whether a call is staged (kPdStageBytes) or fits a multi-region launch set.
-struct PdInputLayout {
-  size_t hap_bytes, read_bytes;
-  size_t o_hb, o_hp, o_rb, o_rq, o_ri, o_rd, o_gc, o_hl, o_rl, total;
-  PdInputLayout(size_t n_hap_items, size_t n_read_items, size_t max_hap_len, size_t max_read_len)
-      : hap_bytes(n_hap_items * max_hap_len), read_bytes(n_read_items * max_read_len),
-        o_hb(0), o_hp(pd_up(hap_bytes)), o_rb(o_hp + pd_up(hap_bytes)), o_rq(o_rb + pd_up(read_bytes)), o_ri(o_rq + pd_up(read_bytes)),
-        o_rd(o_ri + pd_up(read_bytes)), o_gc(o_rd + pd_up(read_bytes)), o_hl(o_gc + pd_up(read_bytes)),
-        o_rl(o_hl + pd_up(n_hap_items * 8)), total(o_rl + pd_up(n_read_items * 8)) {}
+// Padded input bytes (haplotype bases + the five read arrays) from which a paired call of 65 536 pairs or more is cut
+// into upload slices (pd_plan_slices), and from which a call too big to stage leaves its copies to a helper thread
+// (PdUploads::start).
+constexpr size_t kPdSliceMinBytes = (size_t)64 << 20, kPdHelperUploadBytes = (size_t)8 << 20;
+static_assert(kPdLaneRowBytes == kLanes * sizeof(PlanLane), "pdhmm_job_layout.h sizes a lane row for this wavefront");
+// The int32 words of `misc` that a call uses (the first 64 are cleared by every call; a GKL_PD_PROF build keeps its
+// cycle counts in words 32-63).  kPdMiscNext*: job counters of the persistent launches (PdArgs::next).
+enum PdMiscWord : int {
+  kPdMiscInputError = 0,     // single call: PDHMM_INPUT_DATA_ERROR (PdArgs::status)
+  kPdMiscNext = 1,           // the predicate launch that is not a slice's
+  kPdMiscNextTail = 2,
+  kPdMiscNextFull = 3,
+  kPdMiscNextTab = 4,        // cross layout's table launch
+  kPdMiscFullCount = 5,      // length of the full launch's job list (PdArgs::full_count)
+  kPdMiscHotCount = 6,       // paired table route: length of the closing predicate launch's list
+  kPdMiscNextSliceTab = 8,   // + k: paired layout, slice k's table launch
+  kPdMiscNextSliceHot = 16,  // + k: ... its predicate launch
+  kPdMiscRegionFlags = 64,   // + k: multi-region call, region k's input-error flag
 };
+constexpr int kPdMiscStatusWords = 8;   // what a single call reads back
+static_assert(kPdMiscNextSliceTab + gklhip_pdhmm_ctx::kMaxSlices <= kPdMiscNextSliceHot &&
+              kPdMiscNextSliceHot + gklhip_pdhmm_ctx::kMaxSlices <= 32, "the slices' job counters stay clear of each other");
+static_assert(kPdMiscHotCount < kPdMiscStatusWords && 4 * kPdMiscRegionFlags == 256, "status read-back; the flags follow the cleared words");
+
+// The nine input arrays of a problem, in the order they are sent.  The layout's rows are the problem's own in a single
+// call and the common, possibly longer ones in a multi-region call.
+struct PdInputArray {
+  size_t offset;            // of the array in the layout
+  const char* src;
+  size_t src_row, dst_row;  // bytes per item in the caller's array / in the layout
+  size_t n_items;
+  bool hap;                 // one item per haplotype item (else: per read item)
+};
+struct PdInputArrays {
+  PdInputArray v[9];
+  const PdInputArray* begin() const { return v; }
+  const PdInputArray* end() const { return v + 9; }
+};
+PdInputArrays pd_input_arrays(const PdInputLayout& in, const PdProblem& q) {
+  const size_t qh = (size_t)q.max_hap_len, qr = (size_t)q.max_read_len, nh = (size_t)q.n_hap_items, nr = (size_t)q.n_read_items;
+  auto bytes = [](const void* p) { return static_cast<const char*>(p); };
+  return {{{in.o_hl, bytes(q.hap_lengths), 8, 8, nh, true}, {in.o_rl, bytes(q.read_lengths), 8, 8, nr, false},
+           {in.o_hb, bytes(q.hap_bases), qh, in.hap_row, nh, true}, {in.o_hp, bytes(q.hap_pdbases), qh, in.hap_row, nh, true},
+           {in.o_rb, bytes(q.read_bases), qr, in.read_row, nr, false}, {in.o_rq, bytes(q.read_qual), qr, in.read_row, nr, false},
+           {in.o_ri, bytes(q.read_ins_qual), qr, in.read_row, nr, false}, {in.o_rd, bytes(q.read_del_qual), qr, in.read_row, nr, false},
+           {in.o_gc, bytes(q.gcp), qr, in.read_row, nr, false}}};
+}
 // Cross layout: reads are packed into 64-lane chunks by best fit within windows of this many reads.  The chunks are reused
 // for every haplotype, so a fuller chunk pays off nh times: 2048 fills 99.2 % of the lanes on the reference's fixture
 // (192, the paired layout's window: 97.7 %).
@@ -584,11 +619,9 @@ void pd_size_tab_groups(const size_t* n_tab_haps, int K, int64_t n_cross_tab, st
   start->push_back((int32_t)at);
 }
 
-// Where the job tables that both launch paths keep in the device buffer `jobs` start (each path lays its own block out).
-struct PdJobOffsets { size_t jl, jp, jn, js, cl, cs, cr, nc, cc, jf, fj, tg; };
-
 // The kernel arguments that a single call and a multi-region call set the same way: the input arrays, the tables, the
-// entry streams, the carry rows and the job tables of PdJobOffsets.  Everything else is 0 / NULL for the caller to set.
+// entry streams, the carry rows and the job tables of PdJobOffsets (but the tail jobs': pd_launch_tail).  Everything
+// else is 0 / NULL for the caller to set.
 PdArgs pd_common_args(gklhip_pdhmm_ctx* c, const PdInputLayout& in, const PdJobOffsets& o, size_t n_hap_items, int32_t max_hap,
                       int32_t max_read, int entry_stride, bool table_haps) {
   unsigned char *d = c->inputs.as<unsigned char>(), *dj = c->jobs.as<unsigned char>();
@@ -609,7 +642,7 @@ PdArgs pd_common_args(gklhip_pdhmm_ctx* c, const PdInputLayout& in, const PdJobO
   a.mm_prob = c->tables.as<double>() + pd_tables().q2err.size();
   a.entries = c->entries.as<uint32_t>();
   a.entry_stride = entry_stride;
-  a.next = c->misc.as<int32_t>() + 1;
+  a.next = c->misc.as<int32_t>() + kPdMiscNext;
   a.carry = c->carry.as<double>();
   a.carry_len = entry_stride;
   a.lanes = reinterpret_cast<const LaneSlot*>(dj + o.jl);
@@ -665,22 +698,10 @@ int pd_finalise(gklhip_pdhmm_ctx* c, const double* sums, const PdRegion* regions
   return GKLHIP_OK;
 }
 
-int pd_run_locked(gklhip_pdhmm_ctx* c, const PdProblem& q, double* out_host) {
-  static const bool timing = getenv("GKLHIP_TIMING") != nullptr;
-  const auto t_begin = std::chrono::steady_clock::now();
-  auto ms_since = [&](std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); };
-  HIP_TRY(hipSetDevice(c->device));
-  hipStream_t s = c->stream;
-  const size_t n = (size_t)q.n_pairs;
-  const size_t nh = (size_t)q.n_hap_items, nr = (size_t)q.n_read_items;
-  const PdInputLayout in(nh, nr, (size_t)q.max_hap_len, (size_t)q.max_read_len);
-  const size_t hap_bytes = in.hap_bytes, read_bytes = in.read_bytes;
-  int rc;
-  if ((rc = c->inputs.reserve(in.total))) return rc;
-  unsigned char* d = c->inputs.as<unsigned char>();
-  // The nine input copies (the paired layout of a big batch is hundreds of MB of padded [pair][maxLen] arrays: the
-  // calls alone -- pinning the caller's pages -- take milliseconds): a helper thread issues them while this one builds
-  // the jobs; both meet before anything else goes onto the stream.
+// ==== a single call (pd_run_locked, at the end): plan, uploads, job tables, launches, finish ====
+
+// ---- step 1: the plan.  Everything the call decides before anything of it touches the stream, on the caller's stack. ----
+struct PdCallPlan {
   // A big PAIRED call (computePDHMMNative: ~1.2 KB of padded input per pair -- the x32 fixture is 498 MB, 9.5 ms of PCIe
   // against 5 ms of kernels) is cut into slices of consecutive pairs, biggest first: the helper thread sends slice after
   // slice on the upload stream and records an event behind each; the kernels of a slice -- its pairs are packed among
@@ -688,186 +709,214 @@ int pd_run_locked(gklhip_pdhmm_ctx* c, const PdProblem& q, double* out_host) {
   // smallest slice leaves little to do once the bus is done.  Everything else about the call is one problem: one set of
   // device arrays, one job list (slice k = a range of listed jobs), the rare striped / odd-base / tail jobs at the end.
   int n_slices = 1;
-  size_t slice_lo[gklhip_pdhmm_ctx::kMaxSlices + 1] = {0, n};
-  if (!q.cross_haps && c->pipeline && n >= 65536 && hap_bytes + 5 * read_bytes >= ((size_t)64 << 20)) {
-    static const double kShare[] = {0.28, 0.24, 0.19, 0.13, 0.09, 0.05, 0.02};
-    n_slices = (int)(sizeof kShare / sizeof kShare[0]);
-    double acc = 0.0;
-    for (int k = 0; k < n_slices; k++) { slice_lo[k] = (size_t)(acc * (double)n) / 64 * 64; acc += kShare[k]; }
-    slice_lo[n_slices] = n;
-  }
-  struct Uploads {
-    hipError_t err = hipSuccess;
-    std::thread th;
-    std::atomic<int> recorded{0};   // slices whose upload event has been recorded (or given up on)
-    ~Uploads() { if (th.joinable()) th.join(); }
-  } up_th;
-  auto do_uploads = [&, d]() {
-    (void)hipSetDevice(c->device);
-    hipStream_t us = n_slices > 1 ? c->up_stream : s;
-    auto cp = [&](size_t off, const void* src, size_t bytes) {
-      if (up_th.err != hipSuccess || bytes == 0) return;
-      up_th.err = hipMemcpyAsync(d + off, src, bytes, hipMemcpyHostToDevice, us);
-    };
-    for (int k = 0; k < n_slices; k++) {
-      // (paired layout: item i of every array belongs to pair i; cross layout: one slice, all items)
-      const size_t h0 = n_slices > 1 ? slice_lo[k] : 0, h1 = n_slices > 1 ? slice_lo[k + 1] : nh;
-      const size_t r0 = n_slices > 1 ? slice_lo[k] : 0, r1 = n_slices > 1 ? slice_lo[k + 1] : nr;
-      const size_t mh = (size_t)q.max_hap_len, mr = (size_t)q.max_read_len;
-      cp(in.o_hl + h0 * 8, q.hap_lengths + h0, (h1 - h0) * 8); cp(in.o_rl + r0 * 8, q.read_lengths + r0, (r1 - r0) * 8);
-      cp(in.o_hb + h0 * mh, q.hap_bases + h0 * mh, (h1 - h0) * mh); cp(in.o_hp + h0 * mh, q.hap_pdbases + h0 * mh, (h1 - h0) * mh);
-      cp(in.o_rb + r0 * mr, q.read_bases + r0 * mr, (r1 - r0) * mr); cp(in.o_rq + r0 * mr, q.read_qual + r0 * mr, (r1 - r0) * mr);
-      cp(in.o_ri + r0 * mr, q.read_ins_qual + r0 * mr, (r1 - r0) * mr); cp(in.o_rd + r0 * mr, q.read_del_qual + r0 * mr, (r1 - r0) * mr);
-      cp(in.o_gc + r0 * mr, q.gcp + r0 * mr, (r1 - r0) * mr);
-      if (n_slices > 1) {
-        if (up_th.err == hipSuccess) up_th.err = hipEventRecord(c->up_ev[k], us);
-        up_th.recorded.store(k + 1, std::memory_order_release);
-      }
-    }
-  };
+  size_t slice_lo[gklhip_pdhmm_ctx::kMaxSlices + 1] = {};        // slice k = pairs [slice_lo[k], slice_lo[k + 1])
+  int32_t slice_chunk0[gklhip_pdhmm_ctx::kMaxSlices + 1] = {};   // ... = chunks [slice_chunk0[k], slice_chunk0[k + 1]) = listed jobs n_striped + those
   // A call of the fixture's size (276 reads x 48 haplotypes) spent half its time in two dozen small copies from
   // pageable memory (~10 us each): up to kPdStageBytes the arrays are gathered in a pinned block and travel in ONE copy.
-  const bool staged = in.total <= kPdStageBytes;
-  if (staged) {
-    if ((rc = c->stage_in.reserve(in.total))) return rc;
-    unsigned char* h = c->stage_in.as<unsigned char>();
-    memcpy(h + in.o_hb, q.hap_bases, hap_bytes); memcpy(h + in.o_hp, q.hap_pdbases, hap_bytes);
-    memcpy(h + in.o_rb, q.read_bases, read_bytes); memcpy(h + in.o_rq, q.read_qual, read_bytes); memcpy(h + in.o_ri, q.read_ins_qual, read_bytes);
-    memcpy(h + in.o_rd, q.read_del_qual, read_bytes); memcpy(h + in.o_gc, q.gcp, read_bytes);
-    memcpy(h + in.o_hl, q.hap_lengths, nh * 8); memcpy(h + in.o_rl, q.read_lengths, nr * 8);
-    HIP_TRY(hipMemcpyAsync(d, h, in.total, hipMemcpyHostToDevice, s));
-  } else if (n_slices > 1 || hap_bytes + 5 * read_bytes >= ((size_t)8 << 20)) {
-    up_th.th = std::thread(do_uploads);
-  } else {
-    do_uploads();
-  }
-  const double ms_uploads = ms_since(t_begin);
-  const int cross = q.cross_haps;
-  auto read_len_of = [&](size_t p) { return (int)q.read_lengths[cross ? p / (size_t)cross : p]; };
-  auto hap_len_of = [&](size_t p) { return (int)q.hap_lengths[cross ? p % (size_t)cross : p]; };
-
-  // ---- jobs ----
+  bool staged = false;
   std::vector<int32_t> place_chunk;            // paired layout: compact packing of the pairs (pack_reads_place)
   std::vector<uint8_t> place_lane, chunk_used;
-  size_t n_striped = 0;
-  PdCrossPlan plan;                            // (cross layout: filled by pd_plan_cross_jobs / _routing; paired layout: its listed and tail jobs)
-  auto &job_pair = plan.job_pair, &job_steps = plan.job_steps, &hap_order = plan.hap_order, &chunk_steps = plan.chunk_steps,
-       &chunk_rep = plan.chunk_rep, &tail_pair = plan.tail_pair, &tail_steps = plan.tail_steps;
-  auto &job_striped = plan.job_striped, &tail_striped = plan.tail_striped, &hap_ncls = plan.hap_ncls;
-  auto &cross_lanes = plan.cross_lanes, &tail_lanes = plan.tail_lanes;
-  auto& class_codes = plan.class_codes;
-  int32_t slice_chunk0[gklhip_pdhmm_ctx::kMaxSlices + 1] = {0, 0};   // paired layout: slice k = chunks [slice_chunk0[k], slice_chunk0[k + 1]) = listed jobs n_striped + those
-  size_t& n_tail = plan.n_tail;                // paired layout, tail mode: the last n_tail pairs
-  if (cross) {
-    pd_plan_cross_jobs(c, q, &plan);
-  } else {
-    // "Reference tail": GKL finishes the last `batch mod SIMD width` pairs of every vector batch with its SCALAR
-    // engine (pdhmm.h:1264-1270; 8 doubles per AVX-512 vector, 4 per AVX2 vector), whose arithmetic differs in the
-    // last bits (and, with deletions at a haplotype's end, by more).  In that mode those pairs get jobs of their own,
-    // run by the scalar-arithmetic instantiation of the kernel.
-    if (c->tail_mode == 1) n_tail = n % (size_t)(c->fma_mode ? 8 : 4);
-    const size_t n_vec = n - n_tail;
-    for (size_t i = n_vec; i < n; i++) pd_push_tail_job(&plan, (int32_t)i, read_len_of(i), hap_len_of(i));
-    // short pairs, ordered by haplotype length so that wavefront mates finish together, are packed best-fit
-    // into 64-lane chunks; a read that needs more than 64 lanes becomes a striped job
-    std::vector<int64_t> pair_off(n + 1, 0);  // pack_reads_windowed() addresses reads through offsets
-    for (size_t i = 0; i < n; i++) pair_off[i + 1] = pair_off[i] + read_len_of(i);
-    for (size_t i = 0; i < n_vec; i++) {
-      if (blocks_for(read_len_of(i), kPdRpl) <= kLanes) continue;
-      job_pair.push_back((int32_t)i); job_striped.push_back(1); job_steps.push_back(0);  // (a striped job's lane row stays unused)
-    }
-    // compact packing (5 bytes per pair); pdhmm_expand_kernel turns it into the lane rows on the device.  Slice by slice
-    // (one slice: the whole batch): the pairs of a slice share chunks among themselves only, chunk numbers run on.
-    n_striped = job_pair.size();
-    place_chunk.assign(n, -1);
-    place_lane.assign(n, 0);
-    std::vector<int32_t> shorts, cnt;
-    shorts.reserve(n);
-    for (int k = 0; k < n_slices; k++) {
-      const size_t lo = std::min(slice_lo[k], n_vec), hi = std::min(slice_lo[k + 1], n_vec);
-      slice_chunk0[k] = (int32_t)chunk_used.size();
-      // counting sort by haplotype length, longest first (the big jobs start first)
-      cnt.assign((size_t)q.max_hap_len + 2, 0);
-      size_t n_short = 0;
-      for (size_t i = lo; i < hi; i++)
-        if (blocks_for(read_len_of(i), kPdRpl) <= kLanes) { cnt[(size_t)hap_len_of(i)]++; n_short++; }
-      int32_t acc = 0;
-      for (int64_t h = q.max_hap_len; h >= 0; h--) { const int32_t m = cnt[(size_t)h]; cnt[(size_t)h] = acc; acc += m; }
-      shorts.resize(n_short);
-      for (size_t i = lo; i < hi; i++)
-        if (blocks_for(read_len_of(i), kPdRpl) <= kLanes) shorts[(size_t)cnt[(size_t)hap_len_of(i)]++] = (int32_t)i;
-      const int made = pack_reads_place(shorts.data(), (int)shorts.size(), pair_off.data(), kPdRpl, 192, place_chunk.data(),
-                                        place_lane.data(), &chunk_used, nullptr, &c->pack_scratch);
-      const size_t j0 = n_striped + (size_t)slice_chunk0[k];
-      job_pair.resize(j0 + (size_t)made, -1);
-      job_steps.resize(j0 + (size_t)made, 0);
-      job_striped.resize(j0 + (size_t)made, 0);
-      for (const int32_t i : shorts) {
-        const size_t j = n_striped + (size_t)place_chunk[(size_t)i];
-        if (job_pair[j] < 0) job_pair[j] = i;
-        job_steps[j] = std::max(job_steps[j], (int32_t)(hap_len_of((size_t)i) + blocks_for(read_len_of((size_t)i), kPdRpl) - 1));
-      }
-    }
-    slice_chunk0[n_slices] = (int32_t)chunk_used.size();
+  size_t n_striped = 0;                        // paired layout: the first listed jobs are the striped ones
+  PdCrossPlan x;                               // cross layout: pd_plan_cross_jobs / _routing; paired layout: its listed and tail jobs (pd_plan_paired_jobs)
+  std::vector<int32_t> tab_group_start;        // (table launch; see pd_size_tab_groups)
+  // the full launch's list of listed jobs: the striped ones (the first n_striped in the paired layout, all of them in
+  // the cross layout) from here, flagged packed jobs appended by pdhmm_collect_kernel; its length lives in misc[kPdMiscFullCount]
+  std::vector<int32_t> full_first;
+  int32_t n_striped_listed = 0;                // (lives, like the vectors, until the stream is drained)
+  // the counts (pd_plan_counts)
+  size_t n_clean_haps = 0, n_packed = 0;       // haplotypes without an odd base (paired: every item); paired layout's packed jobs
+  int n_chunks_cross = 0, n_general = 0, n_cross_jobs = 0, n_cross_tab = 0, n_tab_units = 0, n_cross_hot = 0, n_jobs = 0;
+  int entry_stride = 0, n_blocks = 0;
+  bool tab_paired = false, tab_paired_asm = false;
+  bool sums_direct = false;                    // the kernels store the sums straight into pinned host memory
+  bool paired_packed() const { return !chunk_used.empty(); }   // a paired call with at least one packed chunk: pd_launch_paired
+  PdJobCounts job_counts() const {
+    return PdJobCounts{(size_t)n_general, (size_t)n_chunks_cross, x.hap_order.size(), x.n_tail, place_chunk.size(), chunk_used.size(), tab_group_start.size()};
   }
-  const double ms_jobs = ms_since(t_begin);
-  // ---- routing: the hot launch (only the two in-place step loops, see pdhmm_fwd_kernel) takes every job without a
-  // striped read and without a haplotype that has a base outside ACGTN (such columns need the byte-comparing step);
-  // the rest -- rare -- go to a second launch of the full kernel.  Cross layout: the host looks at the (few)
-  // haplotypes and orders them by kernel.  Listed jobs (paired layout: every job): routed on the device
-  // (PdArgs::job_flags) -- a host scan of a haplotype per PAIR is ~100 MB for 400k pairs.
-  if (cross) pd_plan_cross_routing(c, q, &plan);
-  const size_t n_clean_haps = cross ? plan.n_clean_haps : nh, n_tab_haps = plan.n_tab_haps;
-  if (cross) {
-    c->last_routing[0] = (int32_t)n_tab_haps; c->last_routing[1] = (int32_t)(n_clean_haps - n_tab_haps); c->last_routing[2] = (int32_t)(nh - n_clean_haps);
-  } else {
-    c->last_routing[0] = c->last_routing[1] = c->last_routing[2] = 0;
+};
+
+void pd_plan_slices(const gklhip_pdhmm_ctx* c, const PdProblem& q, const PdInputLayout& in, PdCallPlan* p) {
+  const size_t n = (size_t)q.n_pairs;
+  p->staged = in.total <= kPdStageBytes;
+  p->n_slices = 1;
+  p->slice_lo[0] = 0; p->slice_lo[1] = n;
+  if (!q.cross_haps && c->pipeline && n >= 65536 && in.hap_bytes + 5 * in.read_bytes >= kPdSliceMinBytes) {
+    static const double kShare[] = {0.28, 0.24, 0.19, 0.13, 0.09, 0.05, 0.02};
+    p->n_slices = (int)(sizeof kShare / sizeof kShare[0]);
+    double acc = 0.0;
+    for (int k = 0; k < p->n_slices; k++) { p->slice_lo[k] = (size_t)(acc * (double)n) / 64 * 64; acc += kShare[k]; }
+    p->slice_lo[p->n_slices] = n;
   }
-  const double ms_routing = ms_since(t_begin);
-  const int n_chunks_cross = (int)chunk_steps.size();
-  const int64_t n_cross_jobs64 = (int64_t)n_chunks_cross * (int64_t)(cross ? nh : 0);
-  if (n_cross_jobs64 + (int64_t)job_pair.size() > 0x7fffffffLL) return fail(GKLHIP_ERR_INVALID_ARG, "too many jobs");
-  const int n_cross_jobs = (int)n_cross_jobs64;
-  const int n_cross_tab = cross ? (int)((int64_t)n_chunks_cross * (int64_t)n_tab_haps) : 0;
-  std::vector<int32_t> tab_group_start;   // (table launch; see pd_size_tab_groups)
-  if (n_cross_tab > 0) pd_size_tab_groups(&n_tab_haps, 1, n_cross_tab, &tab_group_start, nullptr);
-  const int n_tab_units = tab_group_start.empty() ? 0 : (int)((int64_t)n_chunks_cross * (int64_t)(tab_group_start.size() - 1));
-  const int n_cross_hot = cross ? (int)((int64_t)n_chunks_cross * (int64_t)(n_clean_haps - n_tab_haps)) : 0;
-  const int n_general = (int)job_pair.size();
-  const int n_jobs = n_cross_jobs + n_general;
-  const int entry_stride = (q.max_hap_len + 2 * kLanes + 4 + 63) / 64 * 64;   // 64 idle, the columns, 63 skew + 4 look-ahead
-  const int n_blocks = std::max(1, std::min(std::max(n_jobs, (int)n_tail), 256 * 8));
+}
+
+// The paired layout's jobs: the tail pairs, the striped pairs, then the packed chunks slice by slice.
+void pd_plan_paired_jobs(gklhip_pdhmm_ctx* c, const PdProblem& q, PdCallPlan* p) {
+  const size_t n = (size_t)q.n_pairs;
+  auto read_len_of = [&](size_t i) { return (int)q.read_lengths[i]; };
+  auto hap_len_of = [&](size_t i) { return (int)q.hap_lengths[i]; };
+  PdCrossPlan& x = p->x;
+  // "Reference tail": GKL finishes the last `batch mod SIMD width` pairs of every vector batch with its SCALAR
+  // engine (pdhmm.h:1264-1270; 8 doubles per AVX-512 vector, 4 per AVX2 vector), whose arithmetic differs in the
+  // last bits (and, with deletions at a haplotype's end, by more).  In that mode those pairs get jobs of their own,
+  // run by the scalar-arithmetic instantiation of the kernel.
+  const size_t n_vec = n - (c->tail_mode == 1 ? n % (size_t)(c->fma_mode ? 8 : 4) : 0);
+  for (size_t i = n_vec; i < n; i++) pd_push_tail_job(&x, (int32_t)i, read_len_of(i), hap_len_of(i));
+  // short pairs, ordered by haplotype length so that wavefront mates finish together, are packed best-fit
+  // into 64-lane chunks; a read that needs more than 64 lanes becomes a striped job
+  std::vector<int64_t> pair_off(n + 1, 0);  // pack_reads_windowed() addresses reads through offsets
+  for (size_t i = 0; i < n; i++) pair_off[i + 1] = pair_off[i] + read_len_of(i);
+  for (size_t i = 0; i < n_vec; i++) {
+    if (blocks_for(read_len_of(i), kPdRpl) <= kLanes) continue;
+    x.job_pair.push_back((int32_t)i); x.job_striped.push_back(1); x.job_steps.push_back(0);  // (a striped job's lane row stays unused)
+  }
+  // compact packing (5 bytes per pair); pdhmm_expand_kernel turns it into the lane rows on the device.  Slice by slice
+  // (one slice: the whole batch): the pairs of a slice share chunks among themselves only, chunk numbers run on.
+  const size_t n_striped = p->n_striped = x.job_pair.size();
+  p->place_chunk.assign(n, -1);
+  p->place_lane.assign(n, 0);
+  std::vector<int32_t> shorts, cnt;
+  shorts.reserve(n);
+  for (int k = 0; k < p->n_slices; k++) {
+    const size_t lo = std::min(p->slice_lo[k], n_vec), hi = std::min(p->slice_lo[k + 1], n_vec);
+    p->slice_chunk0[k] = (int32_t)p->chunk_used.size();
+    // counting sort by haplotype length, longest first (the big jobs start first)
+    cnt.assign((size_t)q.max_hap_len + 2, 0);
+    size_t n_short = 0;
+    for (size_t i = lo; i < hi; i++)
+      if (blocks_for(read_len_of(i), kPdRpl) <= kLanes) { cnt[(size_t)hap_len_of(i)]++; n_short++; }
+    int32_t acc = 0;
+    for (int64_t h = q.max_hap_len; h >= 0; h--) { const int32_t m = cnt[(size_t)h]; cnt[(size_t)h] = acc; acc += m; }
+    shorts.resize(n_short);
+    for (size_t i = lo; i < hi; i++)
+      if (blocks_for(read_len_of(i), kPdRpl) <= kLanes) shorts[(size_t)cnt[(size_t)hap_len_of(i)]++] = (int32_t)i;
+    const int made = pack_reads_place(shorts.data(), (int)shorts.size(), pair_off.data(), kPdRpl, 192, p->place_chunk.data(),
+                                      p->place_lane.data(), &p->chunk_used, nullptr, &c->pack_scratch);
+    const size_t j0 = n_striped + (size_t)p->slice_chunk0[k];
+    x.job_pair.resize(j0 + (size_t)made, -1);
+    x.job_steps.resize(j0 + (size_t)made, 0);
+    x.job_striped.resize(j0 + (size_t)made, 0);
+    for (const int32_t i : shorts) {
+      const size_t j = n_striped + (size_t)p->place_chunk[(size_t)i];
+      if (x.job_pair[j] < 0) x.job_pair[j] = i;
+      x.job_steps[j] = std::max(x.job_steps[j], (int32_t)(hap_len_of((size_t)i) + blocks_for(read_len_of((size_t)i), kPdRpl) - 1));
+    }
+  }
+  p->slice_chunk0[p->n_slices] = (int32_t)p->chunk_used.size();
+}
+
+// The figures that follow from the jobs and the routing: what every launch is sized by.
+int pd_plan_counts(gklhip_pdhmm_ctx* c, const PdProblem& q, PdCallPlan* p) {
+  const int cross = q.cross_haps;
+  const size_t n = (size_t)q.n_pairs, nh = (size_t)q.n_hap_items, n_tab_haps = p->x.n_tab_haps;
+  p->n_clean_haps = cross ? p->x.n_clean_haps : nh;
+  p->n_chunks_cross = (int)p->x.chunk_steps.size();
+  const int64_t n_cross_jobs64 = (int64_t)p->n_chunks_cross * (int64_t)(cross ? nh : 0);
+  if (n_cross_jobs64 + (int64_t)p->x.job_pair.size() > 0x7fffffffLL) return fail(GKLHIP_ERR_INVALID_ARG, "too many jobs");
+  p->n_cross_jobs = (int)n_cross_jobs64;
+  p->n_cross_tab = cross ? (int)((int64_t)p->n_chunks_cross * (int64_t)n_tab_haps) : 0;
+  if (p->n_cross_tab > 0) pd_size_tab_groups(&n_tab_haps, 1, p->n_cross_tab, &p->tab_group_start, nullptr);
+  p->n_tab_units = p->tab_group_start.empty() ? 0 : (int)((int64_t)p->n_chunks_cross * (int64_t)(p->tab_group_start.size() - 1));
+  p->n_cross_hot = cross ? (int)((int64_t)p->n_chunks_cross * (int64_t)(p->n_clean_haps - n_tab_haps)) : 0;
+  p->n_general = (int)p->x.job_pair.size();
+  p->n_jobs = p->n_cross_jobs + p->n_general;
+  p->entry_stride = (q.max_hap_len + 2 * kLanes + 4 + 63) / 64 * 64;   // 64 idle, the columns, 63 skew + 4 look-ahead
+  p->n_blocks = std::max(1, std::min(std::max(p->n_jobs, (int)p->x.n_tail), 256 * 8));
   // Paired layout through the table kernel (pdhmm_fwd_tab_paired_kernel): classes, special columns and the routing of the
   // jobs are found on the device.  Needs the program's 32-bit entry offsets to reach every item's stream and the step
   // marks of a job to fit the special kernel's LDS.
-  const size_t n_packed = cross ? 0 : (size_t)n_general - n_striped;
-  const bool tab_paired = !cross && c->use_table && n_packed > 0 && nh * (size_t)entry_stride * 4 < ((size_t)1 << 32) && entry_stride <= 12 * 1024;
-  const bool tab_paired_asm = tab_paired && c->fma_mode == 1 && GKL_PD_ASM == 2;   // (the C++ step loops ballot on the lanes' own entries)
-  const int sb_stride = entry_stride / 64, ns_stride = entry_stride;
-  const size_t x_nc = 0, x_cc = pd_up(nh), x_sb = x_cc + pd_up(nh * 32), x_nt = x_sb + pd_up(nh * (size_t)sb_stride * 8), x_hj = x_nt + pd_up((size_t)n_general),
-               x_ns = x_hj + pd_up((size_t)n_general * 4), x_total = x_ns + (tab_paired_asm ? pd_up((size_t)n_general * (size_t)ns_stride * 4) : 0);
-  if ((rc = c->entries.reserve(nh * (size_t)entry_stride * 4))) return rc;
-  if (n_tab_haps && (rc = c->entries_tab.reserve(2 * nh * (size_t)entry_stride * 4))) return rc;   // + the next-special-column table
-  if (tab_paired && ((rc = c->entries_tab.reserve(nh * (size_t)entry_stride * 4)) || (rc = c->tabx.reserve(x_total)))) return rc;
-  if ((rc = c->sums.reserve(n * 8))) return rc;
-  if ((rc = c->misc.reserve(kPdMiscBytes))) return rc;
-  if ((rc = c->carry.reserve((size_t)n_blocks * 2 * (6 * (size_t)entry_stride + 64) * 8))) return rc;   // (carry_len = entry_stride)
-  const size_t o_jl = 0, o_jp = pd_up((size_t)n_general * kLanes * sizeof(PlanLane)), o_jn = o_jp + pd_up((size_t)n_general * 4),
-               o_js = o_jn + pd_up((size_t)n_general * 4), o_cl = o_js + pd_up((size_t)n_general),
-               o_ho = o_cl + pd_up(cross_lanes.size() * sizeof(PlanLane)), o_cs = o_ho + pd_up(hap_order.size() * 4),
-               o_cr = o_cs + pd_up(chunk_steps.size() * 4), o_tl = o_cr + pd_up(chunk_rep.size() * 4),
-               o_tp = o_tl + pd_up(tail_lanes.size() * sizeof(PlanLane)), o_tn = o_tp + pd_up(n_tail * 4), o_ts = o_tn + pd_up(n_tail * 4),
-               o_nc = o_ts + pd_up(n_tail), o_cc = o_nc + pd_up(hap_ncls.size()), o_jf = o_cc + pd_up(class_codes.size() * 4),
-               o_pc = o_jf + pd_up((size_t)n_general), o_pl = o_pc + pd_up(place_chunk.size() * 4), o_cu = o_pl + pd_up(place_lane.size()),
-               o_fj = o_cu + pd_up(chunk_used.size()), o_tg = o_fj + pd_up((size_t)n_general * 4), jobs_total = o_tg + pd_up(tab_group_start.size() * 4);
-  if (n_slices == 1) {   // (sliced call: the kernels of slice k wait for slice k's upload event, see below)
-    if (up_th.th.joinable()) up_th.th.join();
-    HIP_TRY(up_th.err);
+  p->n_packed = cross ? 0 : (size_t)p->n_general - p->n_striped;
+  p->tab_paired = !cross && c->use_table && p->n_packed > 0 && nh * (size_t)p->entry_stride * 4 < ((size_t)1 << 32) && p->entry_stride <= 12 * 1024;
+  p->tab_paired_asm = p->tab_paired && c->fma_mode == 1 && GKL_PD_ASM == 2;   // (the C++ step loops ballot on the lanes' own entries)
+  // A region-sized call (up to kPdMultiMaxPairs = 1 MB of sums): the kernels store the sums -- write-only, one store per pair --
+  // straight into the pinned host block (posted writes over PCIe) instead of a device array that a copy then fetches: one
+  // copy launch (~15 us of a 0.28 ms call) less.
+  p->sums_direct = n <= kPdMultiMaxPairs;
+  p->n_striped_listed = cross ? p->n_general : (int32_t)p->n_striped;
+  p->full_first.resize((size_t)p->n_striped_listed);
+  for (int32_t k = 0; k < p->n_striped_listed; k++) p->full_first[(size_t)k] = k;
+  return GKLHIP_OK;
+}
+
+// ---- step 2: the nine input arrays go to the device ----
+// The nine input copies (the paired layout of a big batch is hundreds of MB of padded [pair][maxLen] arrays: the
+// calls alone -- pinning the caller's pages -- take milliseconds): a helper thread issues them while the caller builds
+// the jobs; both meet before anything else goes onto the stream (a sliced call: slice by slice, see PdCallPlan).
+struct PdUploads {
+  hipError_t err = hipSuccess;
+  std::thread th;
+  std::atomic<int> recorded{0};   // slices whose upload event has been recorded (or given up on)
+  ~PdUploads() { if (th.joinable()) th.join(); }   // (an early error return of the call)
+
+  // one pinned block and one copy (staged), the copies inline, or the helper thread
+  int start(gklhip_pdhmm_ctx* c, const PdProblem& q, const PdInputLayout& in, const PdCallPlan& p) {
+    int rc;
+    if ((rc = c->inputs.reserve(in.total))) return rc;
+    if (p.staged) {
+      if ((rc = c->stage_in.reserve(in.total))) return rc;
+      unsigned char* h = c->stage_in.as<unsigned char>();
+      for (const PdInputArray& v : pd_input_arrays(in, q)) memcpy(h + v.offset, v.src, v.n_items * v.src_row);
+      HIP_TRY(hipMemcpyAsync(c->inputs.p, h, in.total, hipMemcpyHostToDevice, c->stream));
+    } else if (p.n_slices > 1 || in.hap_bytes + 5 * in.read_bytes >= kPdHelperUploadBytes) {
+      th = std::thread([this, c, &q, &in, &p] { send(c, q, in, p); });
+    } else {
+      send(c, q, in, p);
+    }
+    return GKLHIP_OK;
   }
-  if ((rc = c->jobs.reserve(jobs_total + 256))) return rc;
+  int wait_all() {
+    if (th.joinable()) th.join();
+    HIP_TRY(err);
+    return GKLHIP_OK;
+  }
+  int wait_slice(int k) {   // until slice k's upload event is recorded: the stream can then be told to wait for it
+    while (recorded.load(std::memory_order_acquire) <= k) std::this_thread::yield();
+    HIP_TRY(err);
+    return GKLHIP_OK;
+  }
+
+ private:
+  void send(gklhip_pdhmm_ctx* c, const PdProblem& q, const PdInputLayout& in, const PdCallPlan& p) {
+    (void)hipSetDevice(c->device);
+    unsigned char* const d = c->inputs.as<unsigned char>();
+    const hipStream_t us = p.n_slices > 1 ? c->up_stream : c->stream;
+    for (int k = 0; k < p.n_slices; k++) {
+      // (paired layout: item i of every array belongs to pair i; cross layout: one slice, all items)
+      for (const PdInputArray& v : pd_input_arrays(in, q)) {
+        const size_t i0 = p.n_slices > 1 ? p.slice_lo[k] : 0, i1 = p.n_slices > 1 ? p.slice_lo[k + 1] : v.n_items;
+        if (err != hipSuccess || i1 == i0) continue;
+        err = hipMemcpyAsync(d + v.offset + i0 * v.src_row, v.src + i0 * v.src_row, (i1 - i0) * v.src_row, hipMemcpyHostToDevice, us);
+      }
+      if (p.n_slices > 1) {
+        if (err == hipSuccess) err = hipEventRecord(c->up_ev[k], us);
+        recorded.store(k + 1, std::memory_order_release);
+      }
+    }
+  }
+};
+
+// ---- step 3: the device buffers and the job tables ----
+int pd_reserve_buffers(gklhip_pdhmm_ctx* c, const PdProblem& q, const PdCallPlan& p, const PdTabxLayout& X) {
+  const size_t stream_bytes = (size_t)q.n_hap_items * (size_t)p.entry_stride * 4;   // one entry stream per haplotype item
+  int rc;
+  if ((rc = c->entries.reserve(stream_bytes))) return rc;
+  if (p.x.n_tab_haps && (rc = c->entries_tab.reserve(2 * stream_bytes))) return rc;   // + the next-special-column table
+  if (p.tab_paired && ((rc = c->entries_tab.reserve(stream_bytes)) || (rc = c->tabx.reserve(X.total)))) return rc;
+  if ((rc = c->sums.reserve((size_t)q.n_pairs * 8))) return rc;
+  if ((rc = c->misc.reserve(kPdMiscBytes))) return rc;
+  return c->carry.reserve((size_t)p.n_blocks * 2 * (6 * (size_t)p.entry_stride + 64) * 8);   // (carry_len = entry_stride)
+}
+
+// The single call's job tables, laid out by PdJobLayout: through the pinned block in one copy while they fit it, else
+// table by table.  Clears the status words and sets the full launch's list up.
+int pd_stage_tables(gklhip_pdhmm_ctx* c, const PdCallPlan& p, const PdJobLayout& L) {
+  const hipStream_t s = c->stream;
+  const PdCrossPlan& x = p.x;
+  const size_t n_general = (size_t)p.n_general;
+  int rc;
+  if ((rc = c->jobs.reserve(L.total + 256))) return rc;
   unsigned char* dj = c->jobs.as<unsigned char>();
-  const bool staged_jobs = jobs_total <= kPdStageBytes;
-  if (staged_jobs && (rc = c->stage_jobs.reserve(jobs_total + 256))) return rc;
+  const bool staged_jobs = L.total <= kPdStageBytes;
+  if (staged_jobs && (rc = c->stage_jobs.reserve(L.total + 256))) return rc;
   unsigned char* hj = c->stage_jobs.as<unsigned char>();
   size_t staged_hi = 0;  // bytes of the staging block in use
   auto put = [&](size_t off, const void* src, size_t bytes) {
@@ -875,207 +924,255 @@ int pd_run_locked(gklhip_pdhmm_ctx* c, const PdProblem& q, double* out_host) {
     if (staged_jobs) { memcpy(hj + off, src, bytes); staged_hi = std::max(staged_hi, off + bytes); return hipSuccess; }
     return hipMemcpyAsync(dj + off, src, bytes, hipMemcpyHostToDevice, s);
   };
-  HIP_TRY(put(o_jp, job_pair.data(), (size_t)n_general * 4));
-  HIP_TRY(put(o_jn, job_steps.data(), (size_t)n_general * 4));
-  HIP_TRY(put(o_js, job_striped.data(), (size_t)n_general));
-  HIP_TRY(put(o_cl, cross_lanes.data(), cross_lanes.size() * sizeof(PlanLane)));
-  HIP_TRY(put(o_ho, hap_order.data(), hap_order.size() * 4));
-  HIP_TRY(put(o_cs, chunk_steps.data(), chunk_steps.size() * 4));
-  HIP_TRY(put(o_cr, chunk_rep.data(), chunk_rep.size() * 4));
-  HIP_TRY(put(o_tl, tail_lanes.data(), tail_lanes.size() * sizeof(PlanLane)));
-  HIP_TRY(put(o_tp, tail_pair.data(), n_tail * 4));
-  HIP_TRY(put(o_tn, tail_steps.data(), n_tail * 4));
-  HIP_TRY(put(o_ts, tail_striped.data(), n_tail));
-  HIP_TRY(put(o_nc, hap_ncls.data(), hap_ncls.size()));
-  HIP_TRY(put(o_cc, class_codes.data(), class_codes.size() * 4));
-  HIP_TRY(put(o_pc, place_chunk.data(), place_chunk.size() * 4));
-  HIP_TRY(put(o_pl, place_lane.data(), place_lane.size()));
-  HIP_TRY(put(o_cu, chunk_used.data(), chunk_used.size()));
-  HIP_TRY(put(o_tg, tab_group_start.data(), tab_group_start.size() * 4));
+  HIP_TRY(put(L.jp, x.job_pair.data(), n_general * 4));
+  HIP_TRY(put(L.jn, x.job_steps.data(), n_general * 4));
+  HIP_TRY(put(L.js, x.job_striped.data(), n_general));
+  HIP_TRY(put(L.cl, x.cross_lanes.data(), x.cross_lanes.size() * sizeof(PlanLane)));
+  HIP_TRY(put(L.ho, x.hap_order.data(), x.hap_order.size() * 4));
+  HIP_TRY(put(L.cs, x.chunk_steps.data(), x.chunk_steps.size() * 4));
+  HIP_TRY(put(L.cr, x.chunk_rep.data(), x.chunk_rep.size() * 4));
+  HIP_TRY(put(L.tl, x.tail_lanes.data(), x.tail_lanes.size() * sizeof(PlanLane)));
+  HIP_TRY(put(L.tp, x.tail_pair.data(), x.n_tail * 4));
+  HIP_TRY(put(L.tn, x.tail_steps.data(), x.n_tail * 4));
+  HIP_TRY(put(L.ts, x.tail_striped.data(), x.n_tail));
+  HIP_TRY(put(L.nc, x.hap_ncls.data(), x.hap_ncls.size()));
+  HIP_TRY(put(L.cc, x.class_codes.data(), x.class_codes.size() * 4));
+  HIP_TRY(put(L.pc, p.place_chunk.data(), p.place_chunk.size() * 4));
+  HIP_TRY(put(L.pl, p.place_lane.data(), p.place_lane.size()));
+  HIP_TRY(put(L.cu, p.chunk_used.data(), p.chunk_used.size()));
+  HIP_TRY(put(L.tg, p.tab_group_start.data(), p.tab_group_start.size() * 4));
   if (n_general > 0) {
-    if (staged_jobs) { memset(hj + o_jf, 0, (size_t)n_general); staged_hi = std::max(staged_hi, o_jf + (size_t)n_general); }
-    else HIP_TRY(hipMemsetAsync(dj + o_jf, 0, (size_t)n_general, s));
+    if (staged_jobs) { memset(hj + L.jf, 0, n_general); staged_hi = std::max(staged_hi, L.jf + n_general); }
+    else HIP_TRY(hipMemsetAsync(dj + L.jf, 0, n_general, s));
   }
-  // the full launch's list of listed jobs: the striped ones (the first n_striped in the paired layout, all of them in
-  // the cross layout) from here, flagged packed jobs appended by pdhmm_collect_kernel; its length lives in misc[5]
-  const int32_t n_striped_listed = cross ? n_general : (int32_t)n_striped;   // (lives, like the vectors, until the stream is drained below)
-  std::vector<int32_t> full_first((size_t)n_striped_listed);
-  for (int32_t k = 0; k < n_striped_listed; k++) full_first[(size_t)k] = k;
   HIP_TRY(hipMemsetAsync(c->misc.p, 0, 256, s));
 #ifdef GKL_PD_PROF
   HIP_TRY(hipMemsetAsync(c->misc.as<char>() + 128 + 13 * 8, 0xff, 8, s));
   HIP_TRY(hipMemsetAsync(c->misc.as<char>() + 128 + 15 * 8, 0xff, 8, s));
 #endif
-  HIP_TRY(put(o_fj, full_first.data(), full_first.size() * 4));
+  HIP_TRY(put(L.fj, p.full_first.data(), p.full_first.size() * 4));
   if (staged_jobs && staged_hi > 0) HIP_TRY(hipMemcpyAsync(dj, hj, staged_hi, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(c->misc.as<int32_t>() + 5, &n_striped_listed, 4, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(c->misc.as<int32_t>() + kPdMiscFullCount, &p.n_striped_listed, 4, hipMemcpyHostToDevice, s));
+  return GKLHIP_OK;
+}
 
-  PdArgs a = pd_common_args(c, in, PdJobOffsets{o_jl, o_jp, o_jn, o_js, o_cl, o_cs, o_cr, o_nc, o_cc, o_jf, o_fj, o_tg}, nh, q.max_hap_len,
-                            q.max_read_len, entry_stride, n_tab_haps != 0);
+// What every launch of the call is given; the launches below copy it and change what is theirs.
+int pd_call_args(gklhip_pdhmm_ctx* c, const PdProblem& q, const PdInputLayout& in, const PdCallPlan& p, const PdJobLayout& L,
+                 const PdTabxLayout& X, PdArgs* out) {
+  const size_t n = (size_t)q.n_pairs;
+  PdArgs a = pd_common_args(c, in, L, (size_t)q.n_hap_items, q.max_hap_len, q.max_read_len, p.entry_stride, p.x.n_tab_haps != 0);
   a.batch = (int32_t)n;
-  a.cross_haps = cross;
+  a.cross_haps = q.cross_haps;
   a.sums = c->sums.as<double>();
-  // A region-sized call (up to kPdMultiMaxPairs = 1 MB of sums): the kernels store the sums -- write-only, one store per pair --
-  // straight into the pinned host block (posted writes over PCIe) instead of a device array that a copy then fetches: one
-  // copy launch (~15 us of a 0.28 ms call) less.
-  const bool sums_direct = n <= kPdMultiMaxPairs;
+  int rc;
   if ((rc = c->sums_pin.reserve(n * 8 + 64))) return rc;
-  if (sums_direct) {
+  if (p.sums_direct) {
     void* dp = nullptr;
     HIP_TRY(hipHostGetDevicePointer(&dp, c->sums_pin.p, 0));
     a.sums = static_cast<double*>(dp);
   }
-  a.status = c->misc.as<int32_t>();
-  a.n_jobs = n_jobs;
-  a.n_cross_jobs = n_cross_jobs; a.n_chunks_cross = std::max(n_chunks_cross, 1);
-  a.hap_order = reinterpret_cast<const int32_t*>(dj + o_ho);
-  a.full_count = c->misc.as<int32_t>() + 5;
-  unsigned char* dx = c->tabx.as<unsigned char>();
-  if (tab_paired) {
-    a.hap_ncls_out = dx + x_nc;
-    a.class_codes_out = reinterpret_cast<uint32_t*>(dx + x_cc);
-    a.special_bits = tab_paired_asm ? reinterpret_cast<uint64_t*>(dx + x_sb) : nullptr;
-    a.job_notab = dx + x_nt;
-    a.job_ns = reinterpret_cast<const int32_t*>(dx + x_ns);
-    HIP_TRY(hipMemsetAsync(dx + x_nt, 0, (size_t)n_general, s));
+  a.status = c->misc.as<int32_t>() + kPdMiscInputError;
+  a.n_jobs = p.n_jobs;
+  a.n_cross_jobs = p.n_cross_jobs; a.n_chunks_cross = std::max(p.n_chunks_cross, 1);
+  a.hap_order = reinterpret_cast<const int32_t*>(c->jobs.as<unsigned char>() + L.ho);
+  a.full_count = c->misc.as<int32_t>() + kPdMiscFullCount;
+  if (p.tab_paired) {
+    unsigned char* dx = c->tabx.as<unsigned char>();
+    a.hap_ncls_out = dx + X.nc;
+    a.class_codes_out = reinterpret_cast<uint32_t*>(dx + X.cc);
+    a.special_bits = p.tab_paired_asm ? reinterpret_cast<uint64_t*>(dx + X.sb) : nullptr;
+    a.job_notab = dx + X.nt;
+    a.job_ns = reinterpret_cast<const int32_t*>(dx + X.ns);
+    HIP_TRY(hipMemsetAsync(dx + X.nt, 0, (size_t)p.n_general, c->stream));
   }
+  *out = a;
+  return GKLHIP_OK;
+}
 
-  const bool paired_packed = !cross && !chunk_used.empty();
-  if (!paired_packed && n_slices > 1) {
-    // A sliced call without one packed chunk (every read striped): nothing below waits slice by slice, and the helper
-    // thread may still be sending -- meet ALL the uploads before the first kernel of the other branch reads the arrays.
-    if (up_th.th.joinable()) up_th.th.join();
-    HIP_TRY(up_th.err);
-    for (int k = 0; k < n_slices; k++) HIP_TRY(hipStreamWaitEvent(s, c->up_ev[k], 0));
-  }
-  if (paired_packed) {
-    // ---- paired layout: slice by slice (one slice unless the call is big, see above) ----
-    PdExpandArgs x;
-    x.place_chunk = reinterpret_cast<const int32_t*>(dj + o_pc);
-    x.place_lane = dj + o_pl;
-    x.chunk_used = dj + o_cu;
-    x.read_len = a.read_len;
-    x.entries = a.entries; x.entry_stride = entry_stride;
-    x.lanes = reinterpret_cast<LaneSlot*>(dj + o_jl);
-    x.job_flags = dj + o_jf;
-    x.hap_ncls = tab_paired ? dx + x_nc : nullptr;
-    x.job_notab = tab_paired ? dx + x_nt : nullptr;
-    x.n_striped = (int32_t)n_striped; x.rpl = kPdRpl;
-    for (int k = 0; k < n_slices; k++) {
-      const size_t lo = slice_lo[k], hi = slice_lo[k + 1];
-      const int c0 = slice_chunk0[k], c1 = slice_chunk0[k + 1];
-      const int j0 = (int)n_striped + c0, j1 = (int)n_striped + c1;
-      if (n_slices > 1) {
-        while (up_th.recorded.load(std::memory_order_acquire) <= k) std::this_thread::yield();
-        HIP_TRY(up_th.err);
-        HIP_TRY(hipStreamWaitEvent(s, c->up_ev[k], 0));
-      }
-      PdArgs ae = a;
-      ae.item_base = (int32_t)lo;
-      hipLaunchKernelGGL(pdhmm_entries_kernel, dim3((unsigned)(hi - lo)), dim3(kLanes), 0, s, ae);   // one wavefront per haplotype item
-      x.pair_base = (int32_t)lo; x.n_pairs = (int32_t)hi; x.chunk_base = c0; x.n_chunks = c1;
-      hipLaunchKernelGGL(pdhmm_expand_kernel, dim3((unsigned)((std::max<size_t>(hi - lo, (size_t)(c1 - c0)) + 255) / 256)), dim3(256), 0, s, x);
-      if (j1 > j0)
-        hipLaunchKernelGGL(pdhmm_collect_kernel, dim3((unsigned)((j1 - j0 + 255) / 256)), dim3(256), 0, s, dj + o_jf, dj + o_js, j1,
-                           reinterpret_cast<int32_t*>(dj + o_fj), c->misc.as<int32_t>() + 5, tab_paired ? dx + x_nt : nullptr,
-                           reinterpret_cast<int32_t*>(dx + x_hj), c->misc.as<int32_t>() + 6, j0);
-      HIP_TRY(hipEventRecord(n_slices > 1 ? c->sl_ev0[k] : c->ev0, s));
-      if (j1 <= j0) { if (n_slices > 1) HIP_TRY(hipEventRecord(c->sl_ev1[k], s)); continue; }
-      if (tab_paired) {
-        // table launch: the jobs' next-special-step tables first (part of the timed region: work only this route does),
-        // then every listed job of the slice that is clean and whose haplotypes all have at most kPdTabClasses classes
-        if (tab_paired_asm) {
-          PdJobNsArgs na;
-          na.lanes = a.lanes; na.job_steps = a.job_steps; na.job_striped = a.job_striped; na.job_flags = a.job_flags; na.job_notab = a.job_notab;
-          na.read_len = a.read_len; na.hap_len = a.hap_len; na.special_bits = a.special_bits; na.sb_stride = sb_stride;
-          na.job_ns = reinterpret_cast<int32_t*>(dx + x_ns); na.ns_stride = ns_stride; na.rpl = kPdRpl; na.job_base = j0; na.job_end = j1;
-          hipLaunchKernelGGL(pdhmm_job_special_kernel, dim3((unsigned)((j1 - j0 + kPdNsJobsPerBlock - 1) / kPdNsJobsPerBlock)), dim3(kLanes * kPdNsJobsPerBlock),
-                             (size_t)ns_stride * kPdNsJobsPerBlock, s, na);
-        }
-        PdArgs at = a;
-        at.n_cross_jobs = 0; at.job_base = j0; at.n_jobs = j1;
-        at.class_codes = a.class_codes_out;
-        at.next = c->misc.as<int32_t>() + 8 + k;
-        pd_launch_fwd(c, pdhmm_fwd_tab_paired_kernel<true>, pdhmm_fwd_tab_paired_kernel<false>, std::min(j1 - j0, n_blocks), s, at);
-      } else {
-        // predicate launch: walks the slice's listed jobs and skips the flagged ones
-        PdArgs ah = a;
-        ah.n_cross_jobs = 0; ah.job_base = j0; ah.n_jobs = j1;
-        ah.full_jobs = nullptr;
-        ah.next = c->misc.as<int32_t>() + 16 + k;
-        pd_launch_fwd(c, pdhmm_fwd_kernel<true, false, true>, pdhmm_fwd_kernel<false, false, true>, std::min(j1 - j0, n_blocks), s, ah);
-      }
-      if (n_slices > 1) HIP_TRY(hipEventRecord(c->sl_ev1[k], s));
+// ---- step 4: the launches ----
+// Paired layout with packed chunks: slice by slice (one slice unless the call is big, see PdCallPlan), then the closing
+// launches over the lists that pdhmm_collect_kernel made.
+int pd_launch_paired(gklhip_pdhmm_ctx* c, const PdCallPlan& p, const PdJobLayout& L, const PdTabxLayout& X, const PdArgs& a, PdUploads* up) {
+  const hipStream_t s = c->stream;
+  unsigned char *dj = c->jobs.as<unsigned char>(), *dx = c->tabx.as<unsigned char>();
+  int32_t* const misc = c->misc.as<int32_t>();
+  const int n_slices = p.n_slices, n_blocks = p.n_blocks;
+  PdExpandArgs x;
+  x.place_chunk = reinterpret_cast<const int32_t*>(dj + L.pc);
+  x.place_lane = dj + L.pl;
+  x.chunk_used = dj + L.cu;
+  x.read_len = a.read_len;
+  x.entries = a.entries; x.entry_stride = p.entry_stride;
+  x.lanes = reinterpret_cast<LaneSlot*>(dj + L.jl);
+  x.job_flags = dj + L.jf;
+  x.hap_ncls = p.tab_paired ? dx + X.nc : nullptr;
+  x.job_notab = p.tab_paired ? dx + X.nt : nullptr;
+  x.n_striped = (int32_t)p.n_striped; x.rpl = kPdRpl;
+  for (int k = 0; k < n_slices; k++) {
+    const size_t lo = p.slice_lo[k], hi = p.slice_lo[k + 1];
+    const int c0 = p.slice_chunk0[k], c1 = p.slice_chunk0[k + 1];
+    const int j0 = (int)p.n_striped + c0, j1 = (int)p.n_striped + c1;
+    if (n_slices > 1) {
+      if (int rc = up->wait_slice(k)) return rc;
+      HIP_TRY(hipStreamWaitEvent(s, c->up_ev[k], 0));
     }
-    if (n_slices > 1) HIP_TRY(hipEventRecord(c->ev0, s));
-    if (tab_paired) {
-      // predicate launch: the (rare) clean packed jobs with an ineligible haplotype, from the list pdhmm_collect_kernel made
-      PdArgs ah = a;
-      ah.n_cross_jobs = 0; ah.n_jobs = 0;
-      ah.full_jobs = reinterpret_cast<const int32_t*>(dx + x_hj);
-      ah.full_count = c->misc.as<int32_t>() + 6;
-      pd_launch_fwd(c, pdhmm_fwd_kernel<true, false, true>, pdhmm_fwd_kernel<false, false, true>, std::min((int)n_packed, n_blocks), s, ah);
-    }
-    PdArgs af = a;   // full launch: striped reads and haplotypes with odd bases (the list: striped jobs from the host, flagged ones from pdhmm_collect_kernel)
-    af.n_cross_jobs = 0; af.n_jobs = n_general;
-    af.next = c->misc.as<int32_t>() + 3;
-    pd_launch_fwd(c, pdhmm_fwd_kernel<true>, pdhmm_fwd_kernel<false>, std::min(n_general, n_blocks), s, af);
-  } else {
-    // ---- cross layout (and a paired call that holds striped reads only) ----
-    hipLaunchKernelGGL(pdhmm_entries_kernel, dim3((unsigned)nh), dim3(kLanes), 0, s, a);   // one wavefront per haplotype item
-    HIP_TRY(hipEventRecord(c->ev0, s));
-    // table launch: cross jobs over the haplotypes with few column classes
-    if (n_cross_tab > 0) {
+    PdArgs ae = a;
+    ae.item_base = (int32_t)lo;
+    hipLaunchKernelGGL(pdhmm_entries_kernel, dim3((unsigned)(hi - lo)), dim3(kLanes), 0, s, ae);   // one wavefront per haplotype item
+    x.pair_base = (int32_t)lo; x.n_pairs = (int32_t)hi; x.chunk_base = c0; x.n_chunks = c1;
+    hipLaunchKernelGGL(pdhmm_expand_kernel, dim3((unsigned)((std::max<size_t>(hi - lo, (size_t)(c1 - c0)) + 255) / 256)), dim3(256), 0, s, x);
+    if (j1 > j0)
+      hipLaunchKernelGGL(pdhmm_collect_kernel, dim3((unsigned)((j1 - j0 + 255) / 256)), dim3(256), 0, s, dj + L.jf, dj + L.js, j1,
+                         reinterpret_cast<int32_t*>(dj + L.fj), misc + kPdMiscFullCount, p.tab_paired ? dx + X.nt : nullptr,
+                         reinterpret_cast<int32_t*>(dx + X.hj), misc + kPdMiscHotCount, j0);
+    HIP_TRY(hipEventRecord(n_slices > 1 ? c->sl_ev0[k] : c->ev0, s));
+    if (j1 <= j0) { if (n_slices > 1) HIP_TRY(hipEventRecord(c->sl_ev1[k], s)); continue; }
+    if (p.tab_paired) {
+      // table launch: the jobs' next-special-step tables first (part of the timed region: work only this route does),
+      // then every listed job of the slice that is clean and whose haplotypes all have at most kPdTabClasses classes
+      if (p.tab_paired_asm) {
+        PdJobNsArgs na;
+        na.lanes = a.lanes; na.job_steps = a.job_steps; na.job_striped = a.job_striped; na.job_flags = a.job_flags; na.job_notab = a.job_notab;
+        na.read_len = a.read_len; na.hap_len = a.hap_len; na.special_bits = a.special_bits; na.sb_stride = p.entry_stride / 64;
+        na.job_ns = reinterpret_cast<int32_t*>(dx + X.ns); na.ns_stride = p.entry_stride; na.rpl = kPdRpl; na.job_base = j0; na.job_end = j1;
+        hipLaunchKernelGGL(pdhmm_job_special_kernel, dim3((unsigned)((j1 - j0 + kPdNsJobsPerBlock - 1) / kPdNsJobsPerBlock)), dim3(kLanes * kPdNsJobsPerBlock),
+                           (size_t)p.entry_stride * kPdNsJobsPerBlock, s, na);
+      }
       PdArgs at = a;
-      at.n_cross_jobs = at.n_jobs = n_tab_units;   // (units: haplotype group x chunk)
-      at.next = c->misc.as<int32_t>() + 4;
-      pd_launch_fwd(c, pdhmm_fwd_tab_kernel<true>, pdhmm_fwd_tab_kernel<false>, std::min(n_tab_units, n_blocks), s, at);
+      at.n_cross_jobs = 0; at.job_base = j0; at.n_jobs = j1;
+      at.class_codes = a.class_codes_out;
+      at.next = misc + kPdMiscNextSliceTab + k;
+      pd_launch_fwd(c, pdhmm_fwd_tab_paired_kernel<true>, pdhmm_fwd_tab_paired_kernel<false>, std::min(j1 - j0, n_blocks), s, at);
+    } else {
+      // predicate launch: walks the slice's listed jobs and skips the flagged ones
+      PdArgs ah = a;
+      ah.n_cross_jobs = 0; ah.job_base = j0; ah.n_jobs = j1;
+      ah.full_jobs = nullptr;
+      ah.next = misc + kPdMiscNextSliceHot + k;
+      pd_launch_fwd(c, pdhmm_fwd_kernel<true, false, true>, pdhmm_fwd_kernel<false, false, true>, std::min(j1 - j0, n_blocks), s, ah);
     }
-    // hot launch: cross jobs over the other clean haplotypes + the listed jobs the device routes to it
+    if (n_slices > 1) HIP_TRY(hipEventRecord(c->sl_ev1[k], s));
+  }
+  if (n_slices > 1) HIP_TRY(hipEventRecord(c->ev0, s));
+  if (p.tab_paired) {
+    // predicate launch: the (rare) clean packed jobs with an ineligible haplotype, from the list pdhmm_collect_kernel made
     PdArgs ah = a;
-    ah.hap_order = a.hap_order + n_tab_haps;
-    ah.n_cross_jobs = n_cross_hot;
-    ah.n_jobs = n_cross_hot + (cross ? 0 : n_general);   // (cross layout: the listed jobs are striped reads, all the full kernel's)
-    ah.full_jobs = nullptr;   // walks every listed job and skips the flagged ones
-    if (ah.n_jobs > 0) {
-      pd_launch_fwd(c, pdhmm_fwd_kernel<true, false, true>, pdhmm_fwd_kernel<false, false, true>, std::min(ah.n_jobs, n_blocks), s, ah);
-    }
-    // full launch: cross jobs over the haplotypes with odd bases + the listed jobs with a striped read or an odd haplotype
-    PdArgs af = a;
-    af.hap_order = a.hap_order + n_clean_haps;
-    af.n_cross_jobs = n_cross_jobs - n_cross_hot - n_cross_tab;
-    af.n_jobs = af.n_cross_jobs + n_general;
-    af.next = c->misc.as<int32_t>() + 3;
-    if (af.n_jobs > 0) {
-      pd_launch_fwd(c, pdhmm_fwd_kernel<true>, pdhmm_fwd_kernel<false>, std::min(af.n_jobs, n_blocks), s, af);
-    }
+    ah.n_cross_jobs = 0; ah.n_jobs = 0;
+    ah.full_jobs = reinterpret_cast<const int32_t*>(dx + X.hj);
+    ah.full_count = misc + kPdMiscHotCount;
+    pd_launch_fwd(c, pdhmm_fwd_kernel<true, false, true>, pdhmm_fwd_kernel<false, false, true>, std::min((int)p.n_packed, n_blocks), s, ah);
   }
-  if (n_tail > 0) {
-    PdArgs at = a;  // the tail pairs: jobs of their own, scalar-engine arithmetic (same stream: the carry rows are free again)
-    at.lanes = reinterpret_cast<const LaneSlot*>(dj + o_tl);
-    at.job_pair = reinterpret_cast<const int32_t*>(dj + o_tp);
-    at.job_steps = reinterpret_cast<const int32_t*>(dj + o_tn);
-    at.job_striped = dj + o_ts;
-    at.n_jobs = (int32_t)n_tail;
-    at.n_cross_jobs = 0;
-    at.job_flags = nullptr;   // every tail job is this launch's
-    at.full_jobs = nullptr;
-    at.next = c->misc.as<int32_t>() + 2;
-    hipLaunchKernelGGL((pdhmm_fwd_kernel<false, true>), dim3((unsigned)std::min<size_t>(n_tail, (size_t)n_blocks)), dim3(64), 0, s, at, pd_tables().initial_condition);  // persistent: one carry slab per block
+  PdArgs af = a;   // full launch: striped reads and haplotypes with odd bases (the list: striped jobs from the host, flagged ones from pdhmm_collect_kernel)
+  af.n_cross_jobs = 0; af.n_jobs = p.n_general;
+  af.next = misc + kPdMiscNextFull;
+  pd_launch_fwd(c, pdhmm_fwd_kernel<true>, pdhmm_fwd_kernel<false>, std::min(p.n_general, n_blocks), s, af);
+  return GKLHIP_OK;
+}
+
+// The three launches over cross jobs (a chunk of reads x a haplotype, or a group of table haplotypes), of a single call
+// and of a multi-region call: the same walk with the kernels' single-region or multi-region instantiations.
+struct PdCrossLaunches {
+  PdFwdKernel tab[2], hot[2], full[2];     // {FMA, plain}
+  bool multi;                              // the kernels find their region through PdArgs::multi_launch
+  const int32_t* hap_order;                // [the table launch's haplotypes | the predicate launch's | the full launch's]
+  size_t n_tab_haps, n_hot_haps;
+  int tab_units, hot_units, full_units;    // cross jobs (table launch: haplotype group x chunk)
+  int hot_listed, full_listed;             // listed jobs that the launch walks on top
+};
+void pd_launch_cross_jobs(gklhip_pdhmm_ctx* c, const PdCrossLaunches& l, const PdArgs& a, int n_blocks) {
+  const hipStream_t s = c->stream;
+  // table launch: cross jobs over the haplotypes with few column classes
+  if (l.tab_units > 0) {
+    PdArgs at = a;
+    at.hap_order = l.hap_order;
+    at.n_cross_jobs = at.n_jobs = l.tab_units;
+    if (l.multi) at.multi_launch = kPdLaunchTab;
+    at.next = c->misc.as<int32_t>() + kPdMiscNextTab;
+    pd_launch_fwd(c, l.tab[0], l.tab[1], std::min(l.tab_units, n_blocks), s, at);
   }
+  // predicate ("hot") launch: cross jobs over the other clean haplotypes + the listed jobs the device routes to it
+  PdArgs ah = a;
+  ah.hap_order = l.hap_order + l.n_tab_haps;
+  ah.n_cross_jobs = l.hot_units;
+  ah.n_jobs = l.hot_units + l.hot_listed;
+  if (l.multi) ah.multi_launch = kPdLaunchHot;
+  ah.full_jobs = nullptr;   // walks every listed job and skips the flagged ones
+  if (ah.n_jobs > 0) pd_launch_fwd(c, l.hot[0], l.hot[1], std::min(ah.n_jobs, n_blocks), s, ah);
+  // full launch: cross jobs over the haplotypes with odd bases + the listed jobs with a striped read or an odd haplotype
+  PdArgs af = a;
+  af.hap_order = l.hap_order + l.n_tab_haps + l.n_hot_haps;
+  af.n_cross_jobs = l.full_units;
+  af.n_jobs = l.full_units + l.full_listed;
+  if (l.multi) af.multi_launch = kPdLaunchFull;
+  af.next = c->misc.as<int32_t>() + kPdMiscNextFull;
+  if (af.n_jobs > 0) pd_launch_fwd(c, l.full[0], l.full[1], std::min(af.n_jobs, n_blocks), s, af);
+}
+
+// Cross layout (and a paired call that holds striped reads only).
+int pd_launch_cross(gklhip_pdhmm_ctx* c, const PdProblem& q, const PdCallPlan& p, const PdArgs& a, PdUploads* up) {
+  const hipStream_t s = c->stream;
+  if (p.n_slices > 1) {
+    // A sliced call without one packed chunk (every read striped): nothing here waits slice by slice, and the helper
+    // thread may still be sending -- meet ALL the uploads before the first kernel reads the arrays.
+    if (int rc = up->wait_all()) return rc;
+    for (int k = 0; k < p.n_slices; k++) HIP_TRY(hipStreamWaitEvent(s, c->up_ev[k], 0));
+  }
+  hipLaunchKernelGGL(pdhmm_entries_kernel, dim3((unsigned)q.n_hap_items), dim3(kLanes), 0, s, a);   // one wavefront per haplotype item
+  HIP_TRY(hipEventRecord(c->ev0, s));
+  const PdCrossLaunches l{{pdhmm_fwd_tab_kernel<true>, pdhmm_fwd_tab_kernel<false>},
+                          {pdhmm_fwd_kernel<true, false, true>, pdhmm_fwd_kernel<false, false, true>},
+                          {pdhmm_fwd_kernel<true>, pdhmm_fwd_kernel<false>},
+                          false, a.hap_order, p.x.n_tab_haps, p.n_clean_haps - p.x.n_tab_haps,
+                          p.n_tab_units, p.n_cross_hot, p.n_cross_jobs - p.n_cross_hot - p.n_cross_tab,
+                          q.cross_haps ? 0 : p.n_general,   // (cross layout: the listed jobs are striped reads, all the full kernel's)
+                          p.n_general};
+  pd_launch_cross_jobs(c, l, a, p.n_blocks);
+  return GKLHIP_OK;
+}
+
+// The tail pairs: jobs of their own, scalar-engine arithmetic (same stream: the carry rows are free again).  `tail`: the
+// scalar-arithmetic instantiation of pdhmm_fwd_kernel for the call (single or multi-region); persistent: one carry slab per block.
+void pd_launch_tail(gklhip_pdhmm_ctx* c, PdFwdKernel tail, const PdArgs& a, const PdJobOffsets& o, size_t n_tail, int n_blocks) {
+  unsigned char* dj = c->jobs.as<unsigned char>();
+  PdArgs at = a;
+  at.lanes = reinterpret_cast<const LaneSlot*>(dj + o.tl);
+  at.job_pair = reinterpret_cast<const int32_t*>(dj + o.tp);
+  at.job_steps = reinterpret_cast<const int32_t*>(dj + o.tn);
+  at.job_striped = dj + o.ts;
+  at.n_jobs = (int32_t)n_tail;
+  at.n_cross_jobs = 0;
+  at.job_flags = nullptr;   // every tail job is this launch's
+  at.full_jobs = nullptr;
+  at.next = c->misc.as<int32_t>() + kPdMiscNextTail;
+  hipLaunchKernelGGL(tail, dim3((unsigned)std::min<size_t>(n_tail, (size_t)n_blocks)), dim3(64), 0, c->stream, at, pd_tables().initial_condition);
+}
+
+// ---- step 5: finish ----
+// The call's clock (GKLHIP_TIMING): milliseconds since it began, at four points on the way.
+struct PdCallClock {
+  const std::chrono::steady_clock::time_point t_begin = std::chrono::steady_clock::now();
+  double uploads = 0, jobs = 0, routing = 0, launched = 0;
+  double ms() const { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count(); }
+};
+
+// Behind the last launch: the sums and the status words come back, the stream drains, the helper thread is met, the
+// kernel time and the paired routing counts are read, the sums become the caller's log10 values.
+int pd_finish(gklhip_pdhmm_ctx* c, const PdProblem& q, const PdCallPlan& p, PdUploads* up, PdCallClock* clock, double* out_host) {
+  static const bool timing = getenv("GKLHIP_TIMING") != nullptr;
+  const hipStream_t s = c->stream;
+  const size_t n = (size_t)q.n_pairs;
   HIP_TRY(hipEventRecord(c->ev1, s));
   HIP_TRY(hipGetLastError());
   double* sums = c->sums_pin.as<double>();
   int32_t* status = reinterpret_cast<int32_t*>(sums + n);
-  if (!sums_direct) HIP_TRY(hipMemcpyAsync(sums, c->sums.p, n * 8, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipMemcpyAsync(status, c->misc.p, 32, hipMemcpyDeviceToHost, s));
-  const double ms_launched = ms_since(t_begin);
+  if (!p.sums_direct) HIP_TRY(hipMemcpyAsync(sums, c->sums.p, n * 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(status, c->misc.p, 4 * kPdMiscStatusWords, hipMemcpyDeviceToHost, s));
+  clock->launched = clock->ms();
   HIP_TRY(hipStreamSynchronize(s));
-  if (up_th.th.joinable()) up_th.th.join();   // (a sliced call: the stream has waited for every upload event by now)
-  HIP_TRY(up_th.err);
+  if (int rc = up->wait_all()) return rc;   // (a sliced call: the stream has waited for every upload event by now)
   HIP_TRY(hipEventElapsedTime(&c->last_ms, c->ev0, c->ev1));
-  if (paired_packed && n_slices > 1)   // kernel time of a sliced call: its slices' launches plus the closing ones (the waits for the bus lie between them)
-    for (int k = 0; k < n_slices; k++) {
+  if (p.paired_packed() && p.n_slices > 1)   // kernel time of a sliced call: its slices' launches plus the closing ones (the waits for the bus lie between them)
+    for (int k = 0; k < p.n_slices; k++) {
       float ms = 0.f;
       HIP_TRY(hipEventElapsedTime(&ms, c->sl_ev0[k], c->sl_ev1[k]));
       c->last_ms += ms;
@@ -1091,18 +1188,54 @@ int pd_run_locked(gklhip_pdhmm_ctx* c, const PdProblem& q, double* out_host) {
 #endif
   if (timing)
     fprintf(stderr, "[gklhip] pdhmm call: uploads enqueued %.2f ms, jobs built %.2f, routed %.2f, launched %.2f, synchronised %.2f (kernels %.2f ms), %zu pairs\n",
-            ms_uploads, ms_jobs, ms_routing, ms_launched, ms_since(t_begin), (double)c->last_ms, n);
-  if (!cross) {   // paired layout: packed jobs by kernel (status[5] = the full launch's list, the striped jobs included; [6] = the predicate launch's)
-    const int32_t n_full_packed = status[5] - (int32_t)n_striped, n_hot = tab_paired ? status[6] : (int32_t)n_packed - n_full_packed;
-    c->last_routing[0] = tab_paired ? (int32_t)n_packed - n_hot - n_full_packed : 0;
+            clock->uploads, clock->jobs, clock->routing, clock->launched, clock->ms(), (double)c->last_ms, n);
+  if (!q.cross_haps) {   // paired layout: packed jobs by kernel (the full launch's list, the striped jobs included; the predicate launch's)
+    const int32_t n_full_packed = status[kPdMiscFullCount] - (int32_t)p.n_striped,
+                  n_hot = p.tab_paired ? status[kPdMiscHotCount] : (int32_t)p.n_packed - n_full_packed;
+    c->last_routing[0] = p.tab_paired ? (int32_t)p.n_packed - n_hot - n_full_packed : 0;
     c->last_routing[1] = n_hot;
     c->last_routing[2] = n_full_packed;
   }
-  if (status[0] != 0)  // PDHMM_INPUT_DATA_ERROR (pdhmm-serial.cc:183-199): negative ins / del / gcp quality
+  if (status[kPdMiscInputError] != 0)  // PDHMM_INPUT_DATA_ERROR (pdhmm-serial.cc:183-199): negative ins / del / gcp quality
     return fail(GKLHIP_ERR_INVALID_ARG, "Error while calculating pdhmm. Input arrays aren't valid.");
   PdRegion one[2] = {};   // the call as ONE region of n pairs
   one[1].pair_base = (int32_t)n;
   return pd_finalise(c, sums, one, 1, &out_host, status);   // (status[0] == 0 here)
+}
+
+int pd_run_locked(gklhip_pdhmm_ctx* c, const PdProblem& q, double* out_host) {
+  PdCallClock clock;
+  HIP_TRY(hipSetDevice(c->device));
+  const int cross = q.cross_haps;
+  const PdInputLayout in((size_t)q.n_hap_items, (size_t)q.n_read_items, (size_t)q.max_hap_len, (size_t)q.max_read_len);
+  PdCallPlan plan;
+  pd_plan_slices(c, q, in, &plan);
+  PdUploads up;
+  int rc;
+  if ((rc = up.start(c, q, in, plan))) return rc;
+  clock.uploads = clock.ms();
+  if (cross) pd_plan_cross_jobs(c, q, &plan.x); else pd_plan_paired_jobs(c, q, &plan);
+  clock.jobs = clock.ms();
+  // ---- routing: the hot launch (only the two in-place step loops, see pdhmm_fwd_kernel) takes every job without a
+  // striped read and without a haplotype that has a base outside ACGTN (such columns need the byte-comparing step);
+  // the rest -- rare -- go to a second launch of the full kernel.  Cross layout: the host looks at the (few)
+  // haplotypes and orders them by kernel.  Listed jobs (paired layout: every job): routed on the device
+  // (PdArgs::job_flags) -- a host scan of a haplotype per PAIR is ~100 MB for 400k pairs.
+  if (cross) pd_plan_cross_routing(c, q, &plan.x);
+  const int32_t n_haps = q.n_hap_items, n_tab = (int32_t)plan.x.n_tab_haps, n_clean = (int32_t)plan.x.n_clean_haps;
+  c->last_routing[0] = cross ? n_tab : 0; c->last_routing[1] = cross ? n_clean - n_tab : 0; c->last_routing[2] = cross ? n_haps - n_clean : 0;
+  clock.routing = clock.ms();
+  if ((rc = pd_plan_counts(c, q, &plan))) return rc;
+  const PdJobLayout L(plan.job_counts());
+  const PdTabxLayout X((size_t)n_haps, (size_t)plan.n_general, (size_t)plan.entry_stride, plan.tab_paired_asm);
+  if ((rc = pd_reserve_buffers(c, q, plan, X))) return rc;
+  if (plan.n_slices == 1 && (rc = up.wait_all())) return rc;   // (sliced call: the kernels of slice k wait for slice k's upload event)
+  if ((rc = pd_stage_tables(c, plan, L))) return rc;
+  PdArgs a;
+  if ((rc = pd_call_args(c, q, in, plan, L, X, &a))) return rc;
+  if ((rc = plan.paired_packed() ? pd_launch_paired(c, plan, L, X, a, &up) : pd_launch_cross(c, q, plan, a, &up))) return rc;
+  if (plan.x.n_tail > 0) pd_launch_tail(c, pdhmm_fwd_kernel<false, true>, a, L, plan.x.n_tail, plan.n_blocks);
+  return pd_finish(c, q, plan, &up, &clock, out_host);
 }
 
 // ---- several region calls in one set of launches (gklhip_pdhmm_compute_cross_multi) ----
@@ -1172,19 +1305,14 @@ int pd_run_multi_locked(gklhip_pdhmm_ctx* c, std::vector<PdMultiRegion>& R) {
   unsigned char* d = c->inputs.as<unsigned char>();
   {
     unsigned char* h = c->stage_in.as<unsigned char>();
-    auto rows = [](unsigned char* dst, size_t dst_stride, const int8_t* src, size_t src_stride, size_t n_rows) {
-      if (dst_stride == src_stride) { memcpy(dst, src, n_rows * src_stride); return; }
-      for (size_t i = 0; i < n_rows; i++) memcpy(dst + i * dst_stride, src + i * src_stride, src_stride);
-    };
     for (int k = 0; k < K; k++) {
       const PdProblem& q = R[(size_t)k].q;
-      const size_t h0 = (size_t)regions[(size_t)k].hap_base, r0 = (size_t)regions[(size_t)k].read_base;
-      const size_t nh = (size_t)q.n_hap_items, nr = (size_t)q.n_read_items, qh = (size_t)q.max_hap_len, qr = (size_t)q.max_read_len;
-      rows(h + in.o_hb + h0 * mh, mh, q.hap_bases, qh, nh); rows(h + in.o_hp + h0 * mh, mh, q.hap_pdbases, qh, nh);
-      rows(h + in.o_rb + r0 * mr, mr, q.read_bases, qr, nr); rows(h + in.o_rq + r0 * mr, mr, q.read_qual, qr, nr);
-      rows(h + in.o_ri + r0 * mr, mr, q.read_ins_qual, qr, nr); rows(h + in.o_rd + r0 * mr, mr, q.read_del_qual, qr, nr);
-      rows(h + in.o_gc + r0 * mr, mr, q.gcp, qr, nr);
-      memcpy(h + in.o_hl + h0 * 8, q.hap_lengths, nh * 8); memcpy(h + in.o_rl + r0 * 8, q.read_lengths, nr * 8);
+      const PdRegion& rg = regions[(size_t)k];
+      for (const PdInputArray& v : pd_input_arrays(in, q)) {   // the region's rows at the common strides
+        unsigned char* dst = h + v.offset + (size_t)(v.hap ? rg.hap_base : rg.read_base) * v.dst_row;
+        if (v.dst_row == v.src_row) { memcpy(dst, v.src, v.n_items * v.src_row); continue; }
+        for (size_t i = 0; i < v.n_items; i++) memcpy(dst + i * v.dst_row, v.src + i * v.src_row, v.src_row);
+      }
     }
     HIP_TRY(hipMemcpyAsync(d, h, in.total, hipMemcpyHostToDevice, s));
   }
@@ -1197,7 +1325,7 @@ int pd_run_multi_locked(gklhip_pdhmm_ctx* c, std::vector<PdMultiRegion>& R) {
   if (n_tab_haps && (rc = c->entries_tab.reserve(2 * NH * (size_t)entry_stride * 4))) return rc;
   if ((rc = c->misc.reserve(kPdMiscBytes))) return rc;
   if ((rc = c->carry.reserve((size_t)n_blocks * 2 * (6 * (size_t)entry_stride + 64) * 8))) return rc;   // (carry_len = entry_stride)
-  if ((rc = c->sums_pin.reserve(NP * 8 + 4 * (64 + (size_t)kPdMaxRegions)))) return rc;
+  if ((rc = c->sums_pin.reserve(NP * 8 + 4 * ((size_t)kPdMiscRegionFlags + (size_t)kPdMaxRegions)))) return rc;
   const size_t o_rg = 0, o_cl = o_rg + pd_up(((size_t)K + 1) * sizeof(PdRegion)), o_cs = o_cl + pd_up(n_chunks * kLanes * sizeof(PlanLane)),
                o_cr = o_cs + pd_up(n_chunks * 4), o_ho = o_cr + pd_up(n_chunks * 4), o_tg = o_ho + pd_up(NH * 4),
                o_nc = o_tg + pd_up(tab_group_start.size() * 4), o_cc = o_nc + pd_up(NH), o_jp = o_cc + pd_up(NH * 32), o_jn = o_jp + pd_up(n_general * 4),
@@ -1249,8 +1377,8 @@ int pd_run_multi_locked(gklhip_pdhmm_ctx* c, std::vector<PdMultiRegion>& R) {
   }
   HIP_TRY(hipMemsetAsync(c->misc.p, 0, kPdMiscBytes, s));
 
-  PdArgs a = pd_common_args(c, in, PdJobOffsets{o_jl, o_jp, o_jn, o_js, o_cl, o_cs, o_cr, o_nc, o_cc, o_jf, o_fj, o_tg}, NH, (int32_t)mh,
-                            (int32_t)mr, entry_stride, n_tab_haps != 0);
+  const PdJobOffsets o{o_jl, o_jp, o_jn, o_js, o_cl, o_cs, o_cr, o_nc, o_cc, o_jf, o_fj, o_tg, o_tl, o_tp, o_tn, o_ts};
+  PdArgs a = pd_common_args(c, in, o, NH, (int32_t)mh, (int32_t)mr, entry_stride, n_tab_haps != 0);
   a.batch = (int32_t)NP;
   a.cross_haps = 1;   // (cross layout; the pair index comes from the region table)
   {
@@ -1258,7 +1386,7 @@ int pd_run_multi_locked(gklhip_pdhmm_ctx* c, std::vector<PdMultiRegion>& R) {
     HIP_TRY(hipHostGetDevicePointer(&dp, c->sums_pin.p, 0));
     a.sums = static_cast<double*>(dp);
   }
-  a.status = c->misc.as<int32_t>() + 64;   // one flag per region
+  a.status = c->misc.as<int32_t>() + kPdMiscRegionFlags;   // one flag per region
   a.n_chunks_cross = 1;
   a.full_count = reinterpret_cast<const int32_t*>(dj + o_fc);
   a.regions = reinterpret_cast<const PdRegion*>(dj + o_rg);
@@ -1267,62 +1395,31 @@ int pd_run_multi_locked(gklhip_pdhmm_ctx* c, std::vector<PdMultiRegion>& R) {
 
   hipLaunchKernelGGL(pdhmm_entries_kernel, dim3((unsigned)NH), dim3(kLanes), 0, s, a);   // one wavefront per haplotype item
   HIP_TRY(hipEventRecord(c->ev0, s));
-  if (n_tab_units > 0) {
-    PdArgs at = a;
-    at.hap_order = d_ho;
-    at.n_cross_jobs = at.n_jobs = n_tab_units;
-    at.multi_launch = kPdLaunchTab;
-    at.next = c->misc.as<int32_t>() + 4;
-    pd_launch_fwd(c, pdhmm_fwd_tab_kernel<true, true>, pdhmm_fwd_tab_kernel<false, true>, std::min(n_tab_units, n_blocks), s, at);
-  }
-  if (n_hot_units > 0) {
-    PdArgs ah = a;
-    ah.hap_order = d_ho + n_tab_haps;
-    ah.n_cross_jobs = ah.n_jobs = n_hot_units;
-    ah.multi_launch = kPdLaunchHot;
-    ah.full_jobs = nullptr;
-    pd_launch_fwd(c, pdhmm_fwd_kernel<true, false, true, true>, pdhmm_fwd_kernel<false, false, true, true>, std::min(n_hot_units, n_blocks), s, ah);
-  }
-  if (n_full_units + (int)n_general > 0) {   // the listed jobs: the striped reads, all from the host's list
-    PdArgs af = a;
-    af.hap_order = d_ho + n_tab_haps + n_hot_haps;
-    af.n_cross_jobs = n_full_units;
-    af.n_jobs = n_full_units + (int)n_general;
-    af.multi_launch = kPdLaunchFull;
-    af.next = c->misc.as<int32_t>() + 3;
-    pd_launch_fwd(c, pdhmm_fwd_kernel<true, false, false, true>, pdhmm_fwd_kernel<false, false, false, true>, std::min(af.n_jobs, n_blocks), s, af);
-  }
-  if (n_tail > 0) {   // every region's tail pairs, scalar-engine arithmetic (same stream: the carry rows are free again)
-    PdArgs at = a;
-    at.lanes = reinterpret_cast<const LaneSlot*>(dj + o_tl);
-    at.job_pair = reinterpret_cast<const int32_t*>(dj + o_tp);
-    at.job_steps = reinterpret_cast<const int32_t*>(dj + o_tn);
-    at.job_striped = dj + o_ts;
-    at.n_jobs = (int32_t)n_tail;
-    at.n_cross_jobs = 0;
-    at.job_flags = nullptr;
-    at.full_jobs = nullptr;
-    at.next = c->misc.as<int32_t>() + 2;
-    hipLaunchKernelGGL((pdhmm_fwd_kernel<false, true, false, true>), dim3((unsigned)std::min<size_t>(n_tail, (size_t)n_blocks)), dim3(64), 0, s, at, pd_tables().initial_condition);
-  }
+  const PdCrossLaunches l{{pdhmm_fwd_tab_kernel<true, true>, pdhmm_fwd_tab_kernel<false, true>},
+                          {pdhmm_fwd_kernel<true, false, true, true>, pdhmm_fwd_kernel<false, false, true, true>},
+                          {pdhmm_fwd_kernel<true, false, false, true>, pdhmm_fwd_kernel<false, false, false, true>},
+                          true, d_ho, n_tab_haps, n_hot_haps, n_tab_units, n_hot_units, n_full_units,
+                          0, (int)n_general};   // the listed jobs: the striped reads, all from the host's list
+  pd_launch_cross_jobs(c, l, a, n_blocks);
+  if (n_tail > 0) pd_launch_tail(c, pdhmm_fwd_kernel<false, true, false, true>, a, o, n_tail, n_blocks);   // every region's tail pairs
   HIP_TRY(hipEventRecord(c->ev1, s));
   HIP_TRY(hipGetLastError());
   double* sums = c->sums_pin.as<double>();
   int32_t* status = reinterpret_cast<int32_t*>(sums + NP);
-  HIP_TRY(hipMemcpyAsync(status, c->misc.p, 4 * (64 + (size_t)K), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(status, c->misc.p, 4 * ((size_t)kPdMiscRegionFlags + (size_t)K), hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
   HIP_TRY(hipEventElapsedTime(&c->last_ms, c->ev0, c->ev1));
   c->last_routing[0] = (int32_t)n_tab_haps; c->last_routing[1] = (int32_t)n_hot_haps; c->last_routing[2] = (int32_t)n_full_haps;
   for (int k = 0; k < K; k++) {
     PdMultiRegion& r = R[(size_t)k];
-    r.flag = status[64 + k];
+    r.flag = status[kPdMiscRegionFlags + k];
     r.routing[0] = (int32_t)plans[(size_t)k].n_tab_haps; r.routing[1] = (int32_t)(plans[(size_t)k].n_clean_haps - plans[(size_t)k].n_tab_haps);
     r.routing[2] = (int32_t)((size_t)r.q.n_hap_items - plans[(size_t)k].n_clean_haps);
   }
   // one finalisation over all pairs; a region with an input error keeps its output untouched
   double* out[kPdMaxRegions];
   for (int k = 0; k < K; k++) out[k] = R[(size_t)k].out;
-  return pd_finalise(c, sums, regions.data(), K, out, status + 64);
+  return pd_finalise(c, sums, regions.data(), K, out, status + kPdMiscRegionFlags);
 }
 
 // process-wide, per device (gklhip_pdhmm_combine_counts): region calls computed, region calls that shared a launch set
