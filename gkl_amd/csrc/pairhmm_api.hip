@@ -317,6 +317,7 @@ static int compute_device_impl(gklhip_ctx* c, const gklhip_batch* dev_batch, dou
         DevCtx* twin = nullptr;
         if (dev_init(d->cfg, d->device, ndev, &twin) != GKLHIP_OK) break;   // e.g. out of memory: stay with one set
         twin->small_read_limit = d->small_read_limit;
+        twin->mid_combine = d->mid_combine;
         made.push_back(twin);
       }
       bool ok = made.size() == c->dev.size();
@@ -389,6 +390,7 @@ static int compute_locked(gklhip_ctx* c, const gklhip_batch* hb, double* out_hos
       HIP_TRY(hipGetDeviceCount(&ndev));
       if ((rc = dev_init(c->dev[0]->cfg, c->dev[0]->device, ndev, &twin))) { c->host_shards = (int)c->host_dev.size(); break; }  // e.g. out of memory: stay whole
       twin->small_read_limit = c->dev[0]->small_read_limit;
+      twin->mid_combine = c->dev[0]->mid_combine;
       c->twins.push_back(twin);
       c->host_dev.push_back(twin);
     }

@@ -26,6 +26,9 @@ struct EnvSwitches {
   const int finalize_threads = integer("GKL_HIP_FINALIZE_THREADS");
   const int finalize_min = integer("GKL_HIP_FINALIZE_MIN");   // one-pass host log10: pairs from which it is spread over the workers (0: the built-in 8192)
   const bool combine = [] { const char* v = getenv("GKL_HIP_COMBINE"); return !(v && v[0] == '0'); }();
+  // concurrent callers' mid-size calls (2049 - 65 536 pairs) enter the small-call combiner, for contexts made from here
+  // on: off unless set to a non-zero number (gklhip_set_mid_combine changes it per context)
+  const bool combine_mid = integer("GKL_HIP_COMBINE_MID") != 0;
   const bool quiet = getenv("GKL_HIP_QUIET") != nullptr;
   const bool one_device_engine = integer("GKL_HIP_DEVICE_ENGINES") == 1;
   // the longest read of a region that takes the small-call path, for contexts made from here on: 511 when set to exactly
@@ -52,6 +55,7 @@ struct DevCtx {
   int asm_general = 1;
   int speculate_fp64 = 0;
   int small_read_limit = g_env.small_read_limit;   // 383 or 511 (gklhip_set_small_read_limit; a staging lane follows its parent)
+  int mid_combine = g_env.combine_mid ? 1 : 0;     // gklhip_set_mid_combine (mid_call_combines; twins and staging lanes follow their parent)
   int lds_oob_zero = 1;   // dev_init's self-test: a DS read beyond the allocation returns 0 here (the fp32 programs' separator priors)
   hipStream_t stream = nullptr;
   // tables

@@ -197,6 +197,7 @@ int lane_init(DevCtx* parent, DevCtx** out) {
   c->asm_general = parent->asm_general;
   c->speculate_fp64 = parent->speculate_fp64;
   c->small_read_limit = parent->small_read_limit;
+  c->mid_combine = parent->mid_combine;
   c->lds_oob_zero = parent->lds_oob_zero;
   c->dt32 = parent->dt32;   // (the parent's tab32 / tab64 own the memory)
   c->dt64 = parent->dt64;

@@ -380,7 +380,7 @@ bool small_call_defers(const DevCtx* c, const CallPlan& P) {
 }
 // A mid-size region of a gklhip_compute_multi call shares a set with others of its kind (dev_compute_host_multi) when
 // everything above holds except the size: kTwoStepFrom < pairs <= kDirectPairs (per_pair says so), its policy in two
-// launches (not fused).  Asked of a plan that small_call_defers turned down; a SINGLE call never asks.
+// launches (not fused).  Asked of a plan that small_call_defers turned down; a SINGLE call asks through mid_call_combines only.
 bool mid_call_shares(const DevCtx* c, const CallPlan& P) {
   return deferral_offered(P.inline_host) && P.pull && c->cfg.record_events == 0 && P.per_pair && !P.fused && c->plan.long_reads.empty() &&
          P.finalize_mode == kModePacked && c->plan.n_chunks > 0 && P.n_pairs > kTwoStepFrom && P.n_pairs <= kDirectPairs;
@@ -391,6 +391,13 @@ bool mid_call_shares(const DevCtx* c, const CallPlan& P) {
 bool double_mid_shares(const DevCtx* c, const CallPlan& P) {
   return deferral_offered(P.inline_host) && P.pull && c->cfg.record_events == 0 && P.use_double && !c->multi_device && c->plan.long_reads.empty() &&
          P.finalize_mode == kModePacked && c->plan.n_chunks > 0 && P.n_pairs > kTwoStepFrom && P.n_pairs <= kDirectPairs;
+}
+// A SINGLE call's mid-size region enters the combiner -- staged as a multi call stages one, launched in a set with the
+// like regions of concurrent callers or as a set of one -- where the context's switch says so (gklhip_set_mid_combine /
+// GKL_HIP_COMBINE_MID; off by default) and one of the two rules above holds.  Asked by dev_compute_host_impl of a plan that
+// was offered deferral and that small_call_defers turned down; the shards of a multi-device context keep the general pass.
+bool mid_call_combines(const DevCtx* c, const CallPlan& P) {
+  return c->mid_combine != 0 && !c->multi_device && (mid_call_shares(c, P) || double_mid_shares(c, P));
 }
 // The longest read of a call that may take the per-pair kernels: 383 bases (64 lanes x kRplF64 rows - 1), or 511 (x kRplPair8)
 // where the context's small_read_limit says so AND the call is one the small-call path is offered at all -- a host call
@@ -957,6 +964,8 @@ int32_t small_call_kind(const CallPlan& P) {
   if (P.use_double && P.n_pairs > kSmallDoublePairs) return kSmallDoubleStream;
   return P.pair_double ? kSmallDouble : P.fused ? kSmallFused : P.n_pairs > kTwoStepFrom ? kSmallTwoStep : kSmallOneLaunch;
 }
+// ... the two kinds of mid-size regions (the combiner's caps on their sets: pairhmm_multi_sets.h)
+bool small_kind_is_mid(int32_t kind) { return kind == kSmallTwoStep || kind == kSmallDoubleStream; }
 
 // ---- step 5: the deferred exit.  Nothing is launched: the call's descriptor, from the same builders, goes into the
 // staging block (still ours to write) and to the combiner. ----

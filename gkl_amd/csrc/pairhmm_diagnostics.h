@@ -36,6 +36,17 @@ int gklhip_set_small_read_limit(gklhip_ctx* ctx, int32_t max_read_len) {
   return GKLHIP_OK;
 }
 
+// Whether this context's mid-size single calls (2049 - 65 536 pairs; mid_call_combines) enter the small-call combiner, for
+// the calls planned from here on.  Every engine, twin and staging lane of the context follows.
+int gklhip_set_mid_combine(gklhip_ctx* ctx, int on) {
+  if (!ctx) return fail(GKLHIP_ERR_INVALID_ARG, "context is NULL");
+  if (ctx->remote) return fail(GKLHIP_ERR_UNSUPPORTED, "gklhip_set_mid_combine: not available on a client context of the PairHMM server (its contexts follow the server's GKL_HIP_COMBINE_MID)");
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  for (const std::vector<DevCtx*>* list : {&ctx->dev, &ctx->dev_alt, &ctx->twins, &ctx->lanes})
+    for (DevCtx* d : *list) d->mid_combine = on ? 1 : 0;
+  return GKLHIP_OK;
+}
+
 // Diagnostics: the VALU issue ceiling of the recurrence's instruction mix on this device (issue_mix_*_kernel: 4 multiplies
 // + 4 FMAs per "cell", four wavefronts per SIMD, every CU) over about `ms_budget` milliseconds.  cells_per_s x 12 FLOP is
 // what roofline.issue_ceiling_tflops reports; clock_ghz = shader cycles the kernel counted / its HIP-event time, i.e. the

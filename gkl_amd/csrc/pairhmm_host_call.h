@@ -56,6 +56,7 @@ struct SmallCombiner {
   int device = 0;
   bool streams_made = false;       // the flight streams are created by the first COMBINED launch (make_streams)
   int flights = 0;
+  int mid_flights = 0;             // ... of which sets of mid-size calls (at most kMidFlights from the queue: combine_admits)
   int max_flights = 4;   // (r05, alternating on one box: 4 callers 698-723 -> 740-757 GCUPS, 16 callers 1941-2010 -> 2127-2133 with four instead of three)
   int min_batch = 0;               // 0: by load (see run())
   int64_t batch_wait_ns = 50000;
@@ -121,8 +122,9 @@ struct SmallCombiner {
     return GKLHIP_OK;
   }
   // One set of launches for calls[0 .. n) (every call of a set is of one kind: a leader only takes calls like its own, a
-  // multi call cuts its sets by kind).  The kernel forms are the launchers' business (pairhmm_device_pass.h).
-  int launch_multi(const SmallLaunch* const* calls, int n, int fma, Slot& sl) {
+  // multi call cuts its sets by kind).  The kernel forms are the launchers' business (pairhmm_device_pass.h).  On stream `s`;
+  // `done` (may be NULL) is recorded behind the last launch.
+  int launch_multi(const SmallLaunch* const* calls, int n, int fma, hipStream_t s, hipEvent_t done) {
     // a launch's table: each call's descriptor (prep reads the pinned one) and where its `blocks` blocks begin
     auto set_of = [&](const SmallCall* SmallLaunch::*desc, int32_t SmallCall::*blocks) {
       MultiArgs m{};
@@ -135,12 +137,11 @@ struct SmallCombiner {
     const auto dev = &SmallLaunch::desc_dev;
     int rows = kPairTiers[0];   // of the set's widest call
     for (int i = 0; i < n; i++) rows = std::max(rows, calls[i]->call.rows);
-    hipStream_t s = sl.stream;
     const MultiArgs mp = set_of(&SmallLaunch::desc_pinned, &SmallCall::prep_grid);
     hipLaunchKernelGGL(prep_multi_kernel, set_grid(mp), dim3(kPrepBlock), 0, s, mp);
     int rc = GKLHIP_OK;
     switch (calls[0]->call.kind) {
-      case kSmallTwoStep: {   // mid-size regions (gklhip_compute_multi only): the packed fp32 pass, then the policy in two launches
+      case kSmallTwoStep: {   // mid-size regions (of a multi call, or of concurrent callers with the mid-size switch on): the packed fp32 pass, then the policy in two launches
         launch_stream_f32_set(set_of(dev, &SmallCall::main_blocks), fma, s);
         const MultiArgs mg = set_of(dev, &SmallCall::flag_grid);
         hipLaunchKernelGGL(pair_flag_multi_kernel, set_grid(mg), dim3(kFlagBlock), 0, s, mg);
@@ -163,7 +164,7 @@ struct SmallCombiner {
     }
     if (rc) return rc;
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(sl.ev, sl.stream));
+    if (done) HIP_TRY(hipEventRecord(done, s));
     return GKLHIP_OK;
   }
 
@@ -171,26 +172,35 @@ struct SmallCombiner {
   // launches calls[0 .. n) -- one call on the caller's own stream exactly as a lone call always went, several in one set of
   // launches on the slot's stream --, reports the launch to the owners of calls[1 ..] (`others`; NULL: all n are the
   // caller's own, the regions of a multi call) and waits for the end.  Returns with the lock released.
+  // ONE mid-size call has no single-call launch form here: it leaves as a set of one through launch_multi, on the caller's
+  // own stream like any lone call -- on the slot's stream it made the four flight streams at a lone caller's first call, which
+  // a one-caller process should never hold (make_streams), and 100 x 10 callers that came later ran a quarter slower
+  // (docs/NOTES.md 75).
   int fly(std::unique_lock<std::mutex>& l, const SmallLaunch* const* calls, int n, hipStream_t own_stream, Ticket* const* others, int64_t t_lead) {
     int si = 0;
     while (slot[si].busy) si++;
     Slot& sl = slot[si];
     sl.busy = true;
     const bool alone = flights == 0 && queue.empty() && n == 1;   // no other small call on the device or waiting for it
+    const bool mid = small_kind_is_mid(calls[0]->call.kind);
+    const bool own = n == 1;                                      // on the caller's own stream
     flights++;
+    if (mid) mid_flights++;
     n_launch_sets++;
     if (n > 1) n_combined += n;
     int rc = GKLHIP_OK;
-    if (n > 1) make_streams();
-    if (n > 1 && !sl.stream) rc = fail(GKLHIP_ERR_HIP, "no stream for combined small calls");
+    if (!own) make_streams();
+    if (!own && !sl.stream) rc = fail(GKLHIP_ERR_HIP, "no stream for combined small calls");
     l.unlock();
-    if (rc == GKLHIP_OK) rc = n == 1 ? launch_single(calls[0]->call, own_stream, alone) : launch_multi(calls, n, calls[0]->call.fma, sl);
+    if (rc == GKLHIP_OK)
+      rc = !own ? launch_multi(calls, n, calls[0]->call.fma, sl.stream, sl.ev)
+           : mid ? launch_multi(calls, 1, calls[0]->call.fma, own_stream, nullptr) : launch_single(calls[0]->call, own_stream, alone);
     const std::string err = rc == GKLHIP_OK ? std::string() : g_err;
     const int64_t t_launched = now_ns();
     // a launch that failed part-way may have left kernels on the stream that still read the calls' staging blocks and
     // write their result buffers: drain it BEFORE any of the calls is told about the failure (and returns to a caller
     // that is free to reuse those buffers)
-    if (rc != GKLHIP_OK) { (void)(n == 1 ? hipStreamSynchronize(own_stream) : hipStreamSynchronize(sl.stream)); (void)hipGetLastError(); }
+    if (rc != GKLHIP_OK) { (void)(own ? hipStreamSynchronize(own_stream) : hipStreamSynchronize(sl.stream)); (void)hipGetLastError(); }
     if (n > 1 && others) {
       l.lock();
       // (the others wait on the set's event themselves; letting them sleep until this thread has seen the end
@@ -204,7 +214,7 @@ struct SmallCombiner {
       l.unlock();
     }
     hipError_t e = hipSuccess;
-    if (rc == GKLHIP_OK) e = n == 1 ? hipStreamSynchronize(own_stream) : hipEventSynchronize(sl.ev);
+    if (rc == GKLHIP_OK) e = own ? hipStreamSynchronize(own_stream) : hipEventSynchronize(sl.ev);
     l.lock();
     {
       const int64_t t_end = now_ns();
@@ -212,6 +222,7 @@ struct SmallCombiner {
     }
     sl.busy = false;  // (the event is recorded again only from here on: a late waiter of this flight then waits a little longer)
     flights--;
+    if (mid) mid_flights--;
     cv.notify_all();
     l.unlock();
     if (rc != GKLHIP_OK) { g_err = err; return rc; }
@@ -238,17 +249,23 @@ struct SmallCombiner {
     Ticket t;
     t.sl = &mine;
     const int64_t t_in = t.t_in = now_ns();
+    const auto as_combine_call = [](const SmallLaunch& x) { return CombineCall{x.call.kind, x.call.fma, (int64_t)x.call.n_pairs}; };
+    const bool mid = small_kind_is_mid(mine.call.kind);
     std::unique_lock<std::mutex> l(mu);
     n_calls++;
     queue.push_back(&t);
     while (t.state == 0 || t.state == 4) {
-      if (t.state == 4 || flights >= max_flights) { cv.wait(l); continue; }
+      // (a mid-size call also waits while kMidFlights mid-size sets are in the air, whatever slots are free)
+      if (t.state == 4 || !combine_admits(mid, flights, mid_flights, max_flights)) { cv.wait(l); continue; }
       // Under load (other sets are in the air) a set is worth more the more calls it carries -- its kernels take as long
       // as their slowest pair whatever their size -- so a would-be leader that finds fewer than `min_batch` calls waiting
       // gives the others `batch_wait_ns` to arrive (GKL_HIP_COMBINE_MIN / GKL_HIP_COMBINE_WAIT_US; 1 / 0 = lead at once).
       // The number to wait for follows the load: a quarter of the host calls inside the library right now, at most 4
       // (16 callers: 4, 8: 2, up to 7: none -- with few callers the wait only adds latency; measured with 50 us: 16 callers
       // 1.42 -> 2.14 TCUPS, while a fixed minimum of 4 cost 4 callers 0.90 -> 0.71).
+      // `queue.size()` counts every waiting call, of whatever kind: with the mid-size switch on, the mid-size tickets
+      // that combine_admits holds back count too, so a small would-be leader may then leave with less company of its own
+      // kind than without them (not measured apart; the mixed run of docs/NOTES.md 75 has both kinds waiting).
       {
         const int want = min_batch > 0 ? min_batch : std::min(4, g_host_calls_in_flight.load(std::memory_order_relaxed) / 4);
         if (flights > 0 && (int)queue.size() < want && now_ns() - t_in < batch_wait_ns) {
@@ -257,25 +274,31 @@ struct SmallCombiner {
         }
       }
       // lead: this call first, then the waiting calls of the same arithmetic mode and kind (a set never mixes the fused
-      // and the one-launch fp32 calls, nor either with the calls of a double-precision context)
+      // and the one-launch fp32 calls, nor either with the calls of a double-precision context, nor small calls with
+      // mid-size ones), a set of mid-size calls within its pair cap: the rule is CombinePick's (pairhmm_multi_sets.h)
       const int64_t t_lead = now_ns();
       ns_queued += t_lead - t_in;
       const SmallLaunch* calls[kCombineMax];
       Ticket* others[kCombineMax];   // the owners of calls[1 ..]
-      int n = 0;
-      calls[n++] = &mine;
-      for (auto it = queue.begin(); it != queue.end();) {
-        if (*it == &t) { it = queue.erase(it); continue; }
-        if (n < kCombineMax && (*it)->sl->call.fma == mine.call.fma && (*it)->sl->call.kind == mine.call.kind) {
-          (*it)->state = 4;  // taken: its owner keeps sleeping until this thread reports the launch (or the end)
-          ns_queued += t_lead - (*it)->t_in;
-          others[n - 1] = *it;
-          calls[n++] = (*it)->sl;
-          it = queue.erase(it);
-          continue;
-        }
-        ++it;
+      static thread_local std::vector<CombineCall> waiting;   // (what the rule reads of the queue, in arrival order)
+      waiting.clear();
+      int me = 0;
+      for (Ticket* o : queue) {
+        if (o == &t) me = (int)waiting.size();
+        waiting.push_back(as_combine_call(*o->sl));
       }
+      int32_t picked[kCombineMax];
+      const int n = combine_pick(waiting.data(), (int)waiting.size(), me, mid, picked);
+      calls[0] = &mine;
+      for (int i = 1; i < n; i++) {
+        Ticket* o = queue[(size_t)picked[i]];
+        o->state = 4;  // taken: its owner keeps sleeping until this thread reports the launch (or the end)
+        ns_queued += t_lead - o->t_in;
+        others[i - 1] = o;
+        calls[i] = o->sl;
+      }
+      // (this call and the taken ones leave the queue; the rest keep their order)
+      queue.erase(std::remove_if(queue.begin(), queue.end(), [&](const Ticket* o) { return o == &t || o->state == 4; }), queue.end());
       return fly(l, calls, n, own_stream, others, t_lead);
     }
     l.unlock();
@@ -346,10 +369,15 @@ int dev_compute_host_impl(DevCtx* c, const gklhip_batch* hb, double* out_host) {
   const int64_t t_call = SmallCombiner::now_ns();
   CallPlan P;
   plan_call(c, &db, kModePacked, inline_inputs, may_defer, call_load(may_defer), &P);
+  // a mid-size region of a context with the mid-size switch on: staged as dev_compute_host_multi stages one, and into the
+  // combiner with the like regions of whoever else is calling right now
+  const bool mid = !P.defers && may_defer && mid_call_combines(c, P);
+  if (mid) P.defers = true;
   if (P.defers) {   // staged and described here, launched by the combiner
     StagedCall S;
     SmallLaunch small;
     if ((rc = stage_call(c, &db, P, pin_out, s, &S))) return rc;
+    if (mid && !P.use_double && (rc = c->fail_order.reserve((size_t)P.n_pairs * 4))) return rc;   // the list of its flagged pairs
     describe_small_call(c, P, S, &small);
     SmallCombiner* k = small_combiner(c->device);
     const int64_t t_staged = SmallCombiner::now_ns();

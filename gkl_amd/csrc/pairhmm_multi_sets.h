@@ -6,7 +6,8 @@
 // local block (block - begin[k]) exactly as its single-call kernel would.  begin[] is a prefix sum of n + 1 values, so a
 // block finds its call by a binary search over it -- uniform over the wavefront, once per block.
 //
-// Plain C++ (tests/native/pairhmm_multi_sets_check.cpp compiles it for the host alone, under the sanitizers).
+// Plain C++ (tests/native/pairhmm_multi_sets_check.cpp and pairhmm_mid_combine_check.cpp compile it for the host alone,
+// under the sanitizers).
 #pragma once
 #include <stdint.h>
 
@@ -45,6 +46,62 @@ inline int multi_cut_sets(const uint8_t* qualifies, const uint8_t* kind, int n, 
     k = end;
   }
   return n_sets;
+}
+
+// ---- which waiting calls a leader of concurrent callers takes (SmallCombiner::run) ----
+// A leader takes itself first, then the waiting calls of its own kind and arithmetic mode in arrival order, at most
+// kCombineMax in all.  A set of MID-SIZE calls (2049 - 65 536 pairs; concurrent callers' only enter with the context's
+// mid-size switch on: gklhip_set_mid_combine) has two limits more, both conditions and not measurements:
+//   kCombineMidPairs  the pairs of one set, twice the largest region.  A set ends when its slowest member does: the cap
+//                     bounds how long a 2049-pair call can be held by its company to about two largest regions' work.
+//                     A waiting call that does not fit is PASSED OVER, not a stop: later, smaller ones are still
+//                     considered (first fit in arrival order).  The passed-over call loses nothing by it -- its own thread
+//                     leads it as soon as it is admitted.  The leader always goes, whatever its size.
+//   kMidFlights       mid-size sets in the air at a time, of the combiner's four flight slots.  A mid-size set holds its
+//                     slot for milliseconds, a GATK-sized one for tens of microseconds: those must always find a slot.  A
+//                     mid-size call that finds kMidFlights mid-size sets in the air waits in the queue -- where it gains
+//                     company -- even when a slot is free.  With fewer slots than four (GKL_HIP_COMBINE_FLIGHTS) mid-size
+//                     sets leave one of them to the small calls: at most min(kMidFlights, slots - 1), combine_mid_flights.
+//                     ONE slot is shared by whoever comes first: the promise to the small calls does not hold there.
+constexpr int64_t kCombineMidPairs = 131072;
+constexpr int kMidFlights = 2;
+constexpr int combine_mid_flights(int max_flights) {
+  return max_flights <= 1 ? 1 : (kMidFlights < max_flights - 1 ? kMidFlights : max_flights - 1);
+}
+
+// What the rule reads of a call.
+struct CombineCall {
+  int32_t kind, fma;
+  int64_t pairs;
+};
+// The set of one leader, filled call by call in arrival order: takes(c) says whether waiting call c rides along (and
+// counts it in).  `mid`: the leader's kind is a mid-size one.
+struct CombinePick {
+  CombineCall lead;
+  bool mid;
+  int n = 1;
+  int64_t pairs;
+  CombinePick(const CombineCall& leader, bool leader_is_mid) : lead(leader), mid(leader_is_mid), pairs(leader.pairs) {}
+  bool takes(const CombineCall& c) {
+    if (n >= kCombineMax || c.fma != lead.fma || c.kind != lead.kind) return false;
+    if (mid && pairs + c.pairs > kCombineMidPairs) return false;
+    n++;
+    pairs += c.pairs;
+    return true;
+  }
+};
+// ... over a whole queue, as SmallCombiner::run calls it: picked[0] = leader, then the queue positions that ride along,
+// ascending; returns their number (picked holds kCombineMax entries).
+inline int combine_pick(const CombineCall* queue, int n_queue, int leader, bool mid, int32_t* picked) {
+  CombinePick pick(queue[leader], mid);
+  picked[0] = leader;
+  for (int i = 0; i < n_queue; i++)
+    if (i != leader && pick.takes(queue[i])) picked[pick.n - 1] = i;
+  return pick.n;
+}
+// May a waiting call lead now?  `flights` sets are in the air, `mid_flights` of them mid-size.
+inline bool combine_admits(bool mid, int flights, int mid_flights, int max_flights) {
+  return flights < max_flights && (!mid || mid_flights < combine_mid_flights(max_flights));
 }
 
 // Mid-size regions (two-launch per-pair policy: more than kTwoStepFrom pairs, pairhmm_device_pass.h) share sets of their

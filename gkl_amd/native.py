@@ -112,6 +112,9 @@ def load_library(path: Optional[str] = None):
     if hasattr(lib, "gklhip_set_small_read_limit"):   # (absent from an older build loaded by path for an A/B)
         lib.gklhip_set_small_read_limit.argtypes = [C.c_void_p, C.c_int32]
         lib.gklhip_set_small_read_limit.restype = C.c_int
+    if hasattr(lib, "gklhip_set_mid_combine"):        # (likewise)
+        lib.gklhip_set_mid_combine.argtypes = [C.c_void_p, C.c_int]
+        lib.gklhip_set_mid_combine.restype = C.c_int
     lib.gklhip_gather_note.argtypes = [C.c_void_p]
     lib.gklhip_gather_note.restype = C.c_char_p
     lib.gklhip_partition_reads.argtypes = [C.c_int32, _i64p, C.c_int32, C.POINTER(C.c_int32)]
@@ -339,6 +342,14 @@ class PairHmmContext:
         """The longest read of a region that takes the small-call path (gklhip_set_small_read_limit): 383, the default,
         or 511.  New contexts start from GKL_HIP_SMALL_READ_LIMIT; a client context of a server cannot set it."""
         st = self.lib.gklhip_set_small_read_limit(self.handle, int(max_read_len))
+        if st != OK:
+            _raise(self.lib, st)
+
+    def set_mid_combine(self, on: bool) -> None:
+        """Whether this context's mid-size single calls (2049 - 65 536 pairs) enter the small-call combiner and share
+        sets of launches with those of concurrent callers (gklhip_set_mid_combine): off by default.  New contexts start
+        from GKL_HIP_COMBINE_MID; a client context of a server cannot set it."""
+        st = self.lib.gklhip_set_mid_combine(self.handle, 1 if on else 0)
         if st != OK:
             _raise(self.lib, st)
 

@@ -179,7 +179,8 @@ int gklhip_compute(gklhip_ctx* ctx, const gklhip_batch* host_batch, double* out_
  * concurrent callers, but takes nobody else's calls and waits for no company.  Every other region -- and every region of
  * a multi-device context, of a process with GKL_HIP_COMBINE=0 and of a client context, whose wire protocol has no multi
  * request -- is computed afterwards through the single-call path, in input order.  A single gklhip_compute of a mid-size
- * region is never combined with anything.
+ * region -- and a region of a multi call that runs through the single-call path -- is combined with nothing unless the
+ * context's mid-size switch is on (gklhip_set_mid_combine, below; off by default).
  * Memory: a lane keeps the buffers of the biggest region it staged until gklhip_release_idle.  One that held a
  * 65 536-pair region keeps at most about 7 MB of device memory (two plan blocks of up to 1 MB, the haplotype streams,
  * 4 + 8 + 1 bytes per pair of raw sums and flags, the 4 bytes per pair of its list of flagged pairs, its lane map; each
@@ -262,6 +263,30 @@ int gklhip_small_call_counts(int device, int64_t out[3], int reset);
  * contexts follow the server process's environment). */
 int gklhip_set_small_read_limit(gklhip_ctx* ctx, int32_t max_read_len);
 
+/* The mid-size switch (opt-in): with on != 0 a single gklhip_compute of a MID-SIZE region on this context -- 2049 to
+ * 65 536 pairs, and everything else gklhip_compute_multi asks of a mid-size region that shares a set: inputs of at most
+ * 1 MB, host finalisation, no record_events, no read beyond the small-read limit (use_double: beyond 639 bases),
+ * GKL_HIP_COMBINE not 0 -- enters the small-call combiner: it is staged as a multi call stages such a region and leaves
+ * in ONE set of launches with the like regions of the threads (contexts) that meet it on the device, through the set
+ * kernels of the multi call.  Results are bit for bit those of the switched-off call.
+ * What stays: a set holds one kind and one fma mode -- mid-size regions never share with small calls, fp32 never with
+ * use_double.  Two caps apply to mid-size sets of concurrent callers: a set holds at most 131 072 pairs (the leader, then
+ * the waiting regions in arrival order that still fit; one that does not fit is passed over and leads its own set) and at
+ * most 16 calls; and at most two of the combiner's four flight slots carry mid-size sets at a time -- a mid-size call that
+ * finds two in the air waits in the queue, where it gains company, so that GATK-sized calls always find a slot (with
+ * GKL_HIP_COMBINE_FLIGHTS = 2 or 3: at most min(2, slots - 1); with ONE slot there is none to leave them).
+ * GKL_HIP_COMBINE_MIN / GKL_HIP_COMBINE_WAIT_US apply as to small calls.  A call that meets nobody leaves as a set of one
+ * through the same kernels, on its context's own stream like any lone call (a one-caller process makes no flight streams).
+ * What never enters and keeps the general pass: multi-device contexts, device finalisation, record_events != 0, a context
+ * with an asynchronous device-resident call in flight, regions above 65 536 pairs or 1 MB of inputs, client contexts.
+ * gklhip_small_call_counts counts such calls like small ones: a lone one adds (1, 0, 1) -- (0, 0, 0) with the switch off.
+ * gklhip_get_raw and gklhip_get_stats work as after any single call.  The shared sets of a multi call are unchanged.
+ * Takes the context's lock and applies to the calls planned afterwards; every engine and staging lane of the context
+ * follows.  New contexts start from the process's environment, read once: GKL_HIP_COMBINE_MID set to a non-zero number
+ * means on (how the JNI libraries and the PairHMM server get it).  On a client context of the server:
+ * GKLHIP_ERR_UNSUPPORTED (the server's contexts follow the server's GKL_HIP_COMBINE_MID). */
+int gklhip_set_mid_combine(gklhip_ctx* ctx, int on);
+
 /* Gives back what an IDLE context holds only for speed: the streams it made for big calls (every stream is a hardware
  * queue the device's scheduler rotates among all processes' -- an idle process should hold one or two, not seven), its
  * twin engines of big host-buffer calls and second engines of two-stream device-resident callers.  Nothing happens while a
@@ -282,7 +307,7 @@ int gklhip_fault_inject(const char* spec);
  * processes meet in one process's small-call combiner.  A client process makes no HIP call: batches travel through a
  * shared-memory arena (memfd) the server maps.  gklhip_init with GKL_HIP_SERVER=PATH in the environment is
  * gklhip_connect(PATH, cfg, out_ctx).  On a remote context gklhip_compute, gklhip_compute_multi (region by region), gklhip_get_stats, gklhip_release_idle (no-op)
- * and gklhip_done work; gklhip_compute_device, gklhip_get_raw, gklhip_get_raw_region, gklhip_get_step_times, gklhip_set_small_read_limit and gklhip_measure_issue_ceiling
+ * and gklhip_done work; gklhip_compute_device, gklhip_get_raw, gklhip_get_raw_region, gklhip_get_step_times, gklhip_set_small_read_limit, gklhip_set_mid_combine and gklhip_measure_issue_ceiling
  * return GKLHIP_ERR_UNSUPPORTED, and so does gklhip_fault_inject in a process with GKL_HIP_SERVER set.  A server that
  * has gone away fails the call with GKLHIP_ERR_HIP and a message that names the socket. */
 #define GKLHIP_SERVER_PROTOCOL 1
