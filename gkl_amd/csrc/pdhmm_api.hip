@@ -77,6 +77,7 @@ struct gklhip_pdhmm_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  hipEvent_t dev_ev = nullptr;          // device-resident calls: recorded on the caller's stream, waited for by `stream`
   // big paired calls are cut into slices of pairs whose kernels run while later slices still cross PCIe (pd_run_locked)
   static constexpr int kMaxSlices = 8;
   hipStream_t up_stream = nullptr;
@@ -185,7 +186,9 @@ int gklhip_pdhmm_init(int device, gklhip_pdhmm_ctx** out_ctx) {
   c->device = device;
   auto bail = [&](int st) { gklhip_pdhmm_done(c); return st; };
   if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) return bail(fail(GKLHIP_ERR_HIP, "hipStreamCreate failed"));
-  if (hipEventCreate(&c->ev0) != hipSuccess || hipEventCreate(&c->ev1) != hipSuccess) return bail(fail(GKLHIP_ERR_HIP, "hipEventCreate failed"));
+  if (hipEventCreate(&c->ev0) != hipSuccess || hipEventCreate(&c->ev1) != hipSuccess ||
+      hipEventCreateWithFlags(&c->dev_ev, hipEventDisableTiming) != hipSuccess)
+    return bail(fail(GKLHIP_ERR_HIP, "hipEventCreate failed"));
   if (hipStreamCreateWithFlags(&c->up_stream, hipStreamNonBlocking) != hipSuccess) return bail(fail(GKLHIP_ERR_HIP, "hipStreamCreate failed"));
   for (int k = 0; k < gklhip_pdhmm_ctx::kMaxSlices; k++)
     if (hipEventCreateWithFlags(&c->up_ev[k], hipEventDisableTiming) != hipSuccess || hipEventCreate(&c->sl_ev0[k]) != hipSuccess ||
@@ -255,6 +258,7 @@ int gklhip_pdhmm_done(gklhip_pdhmm_ctx* c) {
   for (PinBuf* b : {&c->stage_in, &c->stage_jobs, &c->sums_pin}) b->release();
   if (c->ev0) (void)hipEventDestroy(c->ev0);
   if (c->ev1) (void)hipEventDestroy(c->ev1);
+  if (c->dev_ev) (void)hipEventDestroy(c->dev_ev);
   if (c->stream) (void)hipStreamDestroy(c->stream);
   delete c;
   return GKLHIP_OK;
@@ -296,6 +300,9 @@ struct PdProblem {
   // cross layout, reference-tail mode: the reference cuts the read-major pair list into batches of this many pairs
   // (JavaData.h:83-101) and each batch has its own scalar tail; 0 = the whole cross product is one batch
   int64_t ref_batch_pairs;
+  // a device-resident call (gklhip_pdhmm_compute_device / _cross_device): the seven byte arrays are HBM addresses on the
+  // context's device -- no host code reads through them; the two length arrays are host arrays as always
+  bool in_hbm = false;
 };
 
 int pd_validate(const PdProblem& q, const double* out_host) {
@@ -325,7 +332,16 @@ int pd_cross_problem(const gklhip_pdhmm_cross* x, int64_t ref_batch_pairs, const
   return pd_validate(*q, out_host);
 }
 
-int pd_run_locked(gklhip_pdhmm_ctx* c, const PdProblem& q, double* out_host);
+// Where a device-resident call leaves its results (HBM of the context's device) and the caller's stream, behind whose
+// work the call is ordered.
+struct PdDeviceOut {
+  double* out;        // [n_pairs] log10 likelihoods
+  double* sums;       // [n_pairs] raw sums, or NULL
+  hipStream_t after;  // NULL: HIP's default stream
+};
+
+// dev == NULL: a host call, results to out_host; else a device-resident call (q.in_hbm), results to *dev.
+int pd_run_locked(gklhip_pdhmm_ctx* c, const PdProblem& q, double* out_host, const PdDeviceOut* dev = nullptr);
 
 // Does the haplotype hold a base outside ACGTN?  (Such columns need the byte-comparing step: the job goes to the full kernel.)
 bool has_odd_base_scalar(const int8_t* b, int64_t n) {
@@ -417,6 +433,7 @@ struct PdInputArray {
   size_t src_row, dst_row;  // bytes per item in the caller's array / in the layout
   size_t n_items;
   bool hap;                 // one item per haplotype item (else: per read item)
+  bool on_host;             // src is host memory: the lengths always, the byte arrays unless the problem's inputs are in HBM
 };
 struct PdInputArrays {
   PdInputArray v[9];
@@ -426,11 +443,12 @@ struct PdInputArrays {
 PdInputArrays pd_input_arrays(const PdInputLayout& in, const PdProblem& q) {
   const size_t qh = (size_t)q.max_hap_len, qr = (size_t)q.max_read_len, nh = (size_t)q.n_hap_items, nr = (size_t)q.n_read_items;
   auto bytes = [](const void* p) { return static_cast<const char*>(p); };
-  return {{{in.o_hl, bytes(q.hap_lengths), 8, 8, nh, true}, {in.o_rl, bytes(q.read_lengths), 8, 8, nr, false},
-           {in.o_hb, bytes(q.hap_bases), qh, in.hap_row, nh, true}, {in.o_hp, bytes(q.hap_pdbases), qh, in.hap_row, nh, true},
-           {in.o_rb, bytes(q.read_bases), qr, in.read_row, nr, false}, {in.o_rq, bytes(q.read_qual), qr, in.read_row, nr, false},
-           {in.o_ri, bytes(q.read_ins_qual), qr, in.read_row, nr, false}, {in.o_rd, bytes(q.read_del_qual), qr, in.read_row, nr, false},
-           {in.o_gc, bytes(q.gcp), qr, in.read_row, nr, false}}};
+  const bool host = !q.in_hbm;
+  return {{{in.o_hl, bytes(q.hap_lengths), 8, 8, nh, true, true}, {in.o_rl, bytes(q.read_lengths), 8, 8, nr, false, true},
+           {in.o_hb, bytes(q.hap_bases), qh, in.hap_row, nh, true, host}, {in.o_hp, bytes(q.hap_pdbases), qh, in.hap_row, nh, true, host},
+           {in.o_rb, bytes(q.read_bases), qr, in.read_row, nr, false, host}, {in.o_rq, bytes(q.read_qual), qr, in.read_row, nr, false, host},
+           {in.o_ri, bytes(q.read_ins_qual), qr, in.read_row, nr, false, host}, {in.o_rd, bytes(q.read_del_qual), qr, in.read_row, nr, false, host},
+           {in.o_gc, bytes(q.gcp), qr, in.read_row, nr, false, host}}};
 }
 // Cross layout: reads are packed into 64-lane chunks by best fit within windows of this many reads.  The chunks are reused
 // for every haplotype, so a fuller chunk pays off nh times: 2048 fills 99.2 % of the lanes on the reference's fixture
@@ -737,10 +755,10 @@ struct PdCallPlan {
 
 void pd_plan_slices(const gklhip_pdhmm_ctx* c, const PdProblem& q, const PdInputLayout& in, PdCallPlan* p) {
   const size_t n = (size_t)q.n_pairs;
-  p->staged = in.total <= kPdStageBytes;
+  p->staged = !q.in_hbm && in.total <= kPdStageBytes;   // (inputs in HBM: never through host memory, and no bus to hide: one slice)
   p->n_slices = 1;
   p->slice_lo[0] = 0; p->slice_lo[1] = n;
-  if (!q.cross_haps && c->pipeline && n >= 65536 && in.hap_bytes + 5 * in.read_bytes >= kPdSliceMinBytes) {
+  if (!q.in_hbm && !q.cross_haps && c->pipeline && n >= 65536 && in.hap_bytes + 5 * in.read_bytes >= kPdSliceMinBytes) {
     static const double kShare[] = {0.28, 0.24, 0.19, 0.13, 0.09, 0.05, 0.02};
     p->n_slices = (int)(sizeof kShare / sizeof kShare[0]);
     double acc = 0.0;
@@ -830,7 +848,7 @@ int pd_plan_counts(gklhip_pdhmm_ctx* c, const PdProblem& q, PdCallPlan* p) {
   // A region-sized call (up to kPdMultiMaxPairs = 1 MB of sums): the kernels store the sums -- write-only, one store per pair --
   // straight into the pinned host block (posted writes over PCIe) instead of a device array that a copy then fetches: one
   // copy launch (~15 us of a 0.28 ms call) less.
-  p->sums_direct = n <= kPdMultiMaxPairs;
+  p->sums_direct = !q.in_hbm && n <= kPdMultiMaxPairs;   // (a device-resident call: the sums stay in c->sums for pdhmm_finalise_kernel)
   p->n_striped_listed = cross ? p->n_general : (int32_t)p->n_striped;
   p->full_first.resize((size_t)p->n_striped_listed);
   for (int32_t k = 0; k < p->n_striped_listed; k++) p->full_first[(size_t)k] = k;
@@ -856,7 +874,9 @@ struct PdUploads {
       unsigned char* h = c->stage_in.as<unsigned char>();
       for (const PdInputArray& v : pd_input_arrays(in, q)) memcpy(h + v.offset, v.src, v.n_items * v.src_row);
       HIP_TRY(hipMemcpyAsync(c->inputs.p, h, in.total, hipMemcpyHostToDevice, c->stream));
-    } else if (p.n_slices > 1 || in.hap_bytes + 5 * in.read_bytes >= kPdHelperUploadBytes) {
+    } else if (!q.in_hbm && (p.n_slices > 1 || in.hap_bytes + 5 * in.read_bytes >= kPdHelperUploadBytes)) {
+      // (inputs in HBM: the byte arrays are copied device to device into the context's layout -- a fraction of a
+      //  millisecond for the largest call, no pages to pin: the copies are enqueued inline below)
       th = std::thread([this, c, &q, &in, &p] { send(c, q, in, p); });
     } else {
       send(c, q, in, p);
@@ -884,7 +904,8 @@ struct PdUploads {
       for (const PdInputArray& v : pd_input_arrays(in, q)) {
         const size_t i0 = p.n_slices > 1 ? p.slice_lo[k] : 0, i1 = p.n_slices > 1 ? p.slice_lo[k + 1] : v.n_items;
         if (err != hipSuccess || i1 == i0) continue;
-        err = hipMemcpyAsync(d + v.offset + i0 * v.src_row, v.src + i0 * v.src_row, (i1 - i0) * v.src_row, hipMemcpyHostToDevice, us);
+        err = hipMemcpyAsync(d + v.offset + i0 * v.src_row, v.src + i0 * v.src_row, (i1 - i0) * v.src_row,
+                             v.on_host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, us);
       }
       if (p.n_slices > 1) {
         if (err == hipSuccess) err = hipEventRecord(c->up_ev[k], us);
@@ -965,7 +986,7 @@ int pd_call_args(gklhip_pdhmm_ctx* c, const PdProblem& q, const PdInputLayout& i
   a.cross_haps = q.cross_haps;
   a.sums = c->sums.as<double>();
   int rc;
-  if ((rc = c->sums_pin.reserve(n * 8 + 64))) return rc;
+  if ((rc = c->sums_pin.reserve((q.in_hbm ? 0 : n * 8) + 64))) return rc;   // (a device-resident call: the status words alone come back)
   if (p.sums_direct) {
     void* dp = nullptr;
     HIP_TRY(hipHostGetDevicePointer(&dp, c->sums_pin.p, 0));
@@ -1155,6 +1176,16 @@ struct PdCallClock {
   double ms() const { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count(); }
 };
 
+// last_routing of a paired call, from the status words it read back: packed jobs by kernel (the full launch's list, the
+// striped jobs included; the predicate launch's)
+void pd_paired_routing(gklhip_pdhmm_ctx* c, const PdCallPlan& p, const int32_t* status) {
+  const int32_t n_full_packed = status[kPdMiscFullCount] - (int32_t)p.n_striped,
+                n_hot = p.tab_paired ? status[kPdMiscHotCount] : (int32_t)p.n_packed - n_full_packed;
+  c->last_routing[0] = p.tab_paired ? (int32_t)p.n_packed - n_hot - n_full_packed : 0;
+  c->last_routing[1] = n_hot;
+  c->last_routing[2] = n_full_packed;
+}
+
 // Behind the last launch: the sums and the status words come back, the stream drains, the helper thread is met, the
 // kernel time and the paired routing counts are read, the sums become the caller's log10 values.
 int pd_finish(gklhip_pdhmm_ctx* c, const PdProblem& q, const PdCallPlan& p, PdUploads* up, PdCallClock* clock, double* out_host) {
@@ -1189,13 +1220,7 @@ int pd_finish(gklhip_pdhmm_ctx* c, const PdProblem& q, const PdCallPlan& p, PdUp
   if (timing)
     fprintf(stderr, "[gklhip] pdhmm call: uploads enqueued %.2f ms, jobs built %.2f, routed %.2f, launched %.2f, synchronised %.2f (kernels %.2f ms), %zu pairs\n",
             clock->uploads, clock->jobs, clock->routing, clock->launched, clock->ms(), (double)c->last_ms, n);
-  if (!q.cross_haps) {   // paired layout: packed jobs by kernel (the full launch's list, the striped jobs included; the predicate launch's)
-    const int32_t n_full_packed = status[kPdMiscFullCount] - (int32_t)p.n_striped,
-                  n_hot = p.tab_paired ? status[kPdMiscHotCount] : (int32_t)p.n_packed - n_full_packed;
-    c->last_routing[0] = p.tab_paired ? (int32_t)p.n_packed - n_hot - n_full_packed : 0;
-    c->last_routing[1] = n_hot;
-    c->last_routing[2] = n_full_packed;
-  }
+  if (!q.cross_haps) pd_paired_routing(c, p, status);
   if (status[kPdMiscInputError] != 0)  // PDHMM_INPUT_DATA_ERROR (pdhmm-serial.cc:183-199): negative ins / del / gcp quality
     return fail(GKLHIP_ERR_INVALID_ARG, "Error while calculating pdhmm. Input arrays aren't valid.");
   PdRegion one[2] = {};   // the call as ONE region of n pairs
@@ -1203,16 +1228,68 @@ int pd_finish(gklhip_pdhmm_ctx* c, const PdProblem& q, const PdCallPlan& p, PdUp
   return pd_finalise(c, sums, one, 1, &out_host, status);   // (status[0] == 0 here)
 }
 
-int pd_run_locked(gklhip_pdhmm_ctx* c, const PdProblem& q, double* out_host) {
+// pd_finish of a device-resident call: behind the last forward or tail launch (and behind ev1: the kernel time stays the
+// forward launches') pdhmm_finalise_kernel turns c->sums into the caller's log10 values in HBM -- and copies the sums
+// themselves when asked to -- unless the status word reports an input error: then it writes nothing.  Only the status
+// words cross the bus; one synchronisation; no host log10.
+int pd_finish_device(gklhip_pdhmm_ctx* c, const PdProblem& q, const PdCallPlan& p, PdUploads* up, PdCallClock* clock, const PdDeviceOut& dev) {
+  static const bool timing = getenv("GKLHIP_TIMING") != nullptr;
+  const hipStream_t s = c->stream;
+  const int64_t n = q.n_pairs;
+  HIP_TRY(hipEventRecord(c->ev1, s));
+  hipLaunchKernelGGL(pdhmm_finalise_kernel, dim3((unsigned)std::min<int64_t>((n + kPdFinaliseBlock - 1) / kPdFinaliseBlock, 2048)),
+                     dim3(kPdFinaliseBlock), 0, s, c->sums.as<double>(), c->misc.as<int32_t>() + kPdMiscInputError, n,
+                     pd_tables().initial_condition_log10, dev.out, dev.sums);
+  HIP_TRY(hipGetLastError());
+  int32_t* status = c->sums_pin.as<int32_t>();
+  HIP_TRY(hipMemcpyAsync(status, c->misc.p, 4 * kPdMiscStatusWords, hipMemcpyDeviceToHost, s));
+  clock->launched = clock->ms();
+  HIP_TRY(hipStreamSynchronize(s));
+  if (int rc = up->wait_all()) return rc;
+  HIP_TRY(hipEventElapsedTime(&c->last_ms, c->ev0, c->ev1));
+  if (timing)
+    fprintf(stderr, "[gklhip] pdhmm device-resident call: copies enqueued %.2f ms, jobs built %.2f, routed %.2f, launched %.2f, synchronised %.2f (kernels %.2f ms), %lld pairs\n",
+            clock->uploads, clock->jobs, clock->routing, clock->launched, clock->ms(), (double)c->last_ms, (long long)n);
+  if (!q.cross_haps) pd_paired_routing(c, p, status);
+  if (status[kPdMiscInputError] != 0) return fail(GKLHIP_ERR_INVALID_ARG, "Error while calculating pdhmm. Input arrays aren't valid.");
+  return GKLHIP_OK;
+}
+
+// Cross layout of a device-resident call: the planners (pd_plan_cross_routing, has_odd_base) read haplotype bytes on the
+// host, so hap_bases and hap_pdbases -- n_haps * max_hap_len bytes each, the small side of a cross product -- come back
+// into the context's pinned block first (free here: such a call never stages its inputs), behind the caller's work, and
+// the call waits for them: its one early wait.  *plan_q: the problem as the planners may read it.
+int pd_fetch_haps(gklhip_pdhmm_ctx* c, const PdProblem& q, PdProblem* plan_q) {
+  const size_t hap_bytes = (size_t)q.n_hap_items * (size_t)q.max_hap_len;
+  if (int rc = c->stage_in.reserve(2 * hap_bytes)) return rc;
+  int8_t* h = c->stage_in.as<int8_t>();
+  HIP_TRY(hipMemcpyAsync(h, q.hap_bases, hap_bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(h + hap_bytes, q.hap_pdbases, hap_bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  plan_q->hap_bases = h;
+  plan_q->hap_pdbases = h + hap_bytes;
+  return GKLHIP_OK;
+}
+
+int pd_run_locked(gklhip_pdhmm_ctx* c, const PdProblem& q_call, double* out_host, const PdDeviceOut* dev) {
   PdCallClock clock;
   HIP_TRY(hipSetDevice(c->device));
+  int rc;
+  // q_call: the caller's arrays, what the uploads copy from; q: what the host reads while it plans -- the same, but the
+  // two haplotype arrays of a device-resident cross call (pd_fetch_haps)
+  PdProblem q = q_call;
+  if (dev) {
+    // everything the call enqueues is ordered behind what the caller's stream already holds
+    HIP_TRY(hipEventRecord(c->dev_ev, dev->after));
+    HIP_TRY(hipStreamWaitEvent(c->stream, c->dev_ev, 0));
+    if (q.cross_haps && (rc = pd_fetch_haps(c, q_call, &q))) return rc;
+  }
   const int cross = q.cross_haps;
   const PdInputLayout in((size_t)q.n_hap_items, (size_t)q.n_read_items, (size_t)q.max_hap_len, (size_t)q.max_read_len);
   PdCallPlan plan;
   pd_plan_slices(c, q, in, &plan);
   PdUploads up;
-  int rc;
-  if ((rc = up.start(c, q, in, plan))) return rc;
+  if ((rc = up.start(c, q_call, in, plan))) return rc;
   clock.uploads = clock.ms();
   if (cross) pd_plan_cross_jobs(c, q, &plan.x); else pd_plan_paired_jobs(c, q, &plan);
   clock.jobs = clock.ms();
@@ -1235,7 +1312,7 @@ int pd_run_locked(gklhip_pdhmm_ctx* c, const PdProblem& q, double* out_host) {
   if ((rc = pd_call_args(c, q, in, plan, L, X, &a))) return rc;
   if ((rc = plan.paired_packed() ? pd_launch_paired(c, plan, L, X, a, &up) : pd_launch_cross(c, q, plan, a, &up))) return rc;
   if (plan.x.n_tail > 0) pd_launch_tail(c, pdhmm_fwd_kernel<false, true>, a, L, plan.x.n_tail, plan.n_blocks);
-  return pd_finish(c, q, plan, &up, &clock, out_host);
+  return dev ? pd_finish_device(c, q, plan, &up, &clock, *dev) : pd_finish(c, q, plan, &up, &clock, out_host);
 }
 
 // ---- several region calls in one set of launches (gklhip_pdhmm_compute_cross_multi) ----
@@ -1608,6 +1685,47 @@ int gklhip_pdhmm_compute_cross_batched(gklhip_pdhmm_ctx* c, const gklhip_pdhmm_c
   PdProblem q;
   const int rc = pd_cross_problem(x, ref_batch_pairs, out_host, &q);
   return rc ? rc : pd_run_cross(c, q, out_host);
+}
+
+// ---- device-resident calls: byte arrays and results in HBM, synchronous ----
+namespace {
+constexpr const char* kPdDeviceRemoteText = "device-resident batches cannot go to the PDHMM server (client context)";
+
+// The checked problem on the context's own stream and buffers: never through the combiner, never counted
+// (gklhip_pdhmm_combine_counts).
+int pd_run_device(gklhip_pdhmm_ctx* c, PdProblem q, double* out_dev, double* sums_dev, void* hip_stream) {
+  q.in_hbm = true;
+  const PdDeviceOut dev{out_dev, sums_dev, static_cast<hipStream_t>(hip_stream)};
+  std::lock_guard<std::mutex> lock(c->mu);
+  return pd_fenced(c, [&] { return pd_run_locked(c, q, nullptr, &dev); });
+}
+}  // namespace
+
+int gklhip_pdhmm_compute_device(gklhip_pdhmm_ctx* c, const gklhip_pdhmm_batch* b, double* out_dev, double* sums_dev, void* hip_stream) {
+  if (!c) return fail(GKLHIP_ERR_INVALID_ARG, "context is NULL (initNative not called)");
+  if (c->remote) return fail(GKLHIP_ERR_UNSUPPORTED, "gklhip_pdhmm_compute_device: %s", kPdDeviceRemoteText);
+  if (!b) return fail(GKLHIP_ERR_INVALID_ARG, "batch is NULL");
+  if (b->batch <= 0) return fail(GKLHIP_ERR_INVALID_ARG, "batchSize must be greater than 0");
+  PdProblem q{b->batch, b->batch, b->batch, 0, b->max_hap_len, b->max_read_len, b->hap_bases, b->hap_pdbases,
+              b->read_bases, b->read_qual, b->read_ins_qual, b->read_del_qual, b->gcp, b->hap_lengths, b->read_lengths, 0};
+  const int rc = pd_validate(q, out_dev);
+  return rc ? rc : pd_run_device(c, q, out_dev, sums_dev, hip_stream);
+}
+
+int gklhip_pdhmm_compute_cross_device(gklhip_pdhmm_ctx* c, const gklhip_pdhmm_cross* x, int64_t ref_batch_pairs, double* out_dev,
+                                      double* sums_dev, void* hip_stream) {
+  if (!c) return fail(GKLHIP_ERR_INVALID_ARG, "context is NULL (initNative not called)");
+  if (c->remote) return fail(GKLHIP_ERR_UNSUPPORTED, "gklhip_pdhmm_compute_cross_device: %s", kPdDeviceRemoteText);
+  PdProblem q;
+  const int rc = pd_cross_problem(x, ref_batch_pairs, out_dev, &q);
+  return rc ? rc : pd_run_device(c, q, out_dev, sums_dev, hip_stream);
+}
+
+int gklhip_pdhmm_finalise_host(const double* sums, int64_t n, double* out) {
+  if (n < 0 || (n > 0 && (!sums || !out))) return fail(GKLHIP_ERR_INVALID_ARG, "gklhip_pdhmm_finalise_host: NULL array or negative count");
+  const double scale_log10 = pd_tables().initial_condition_log10;
+  for (int64_t i = 0; i < n; i++) out[i] = std::log10(sums[i]) - scale_log10;   // exactly pd_finalise's expression
+  return GKLHIP_OK;
 }
 
 int gklhip_pdhmm_compute_cross_multi(gklhip_pdhmm_ctx* c, int32_t n_regions, const gklhip_pdhmm_cross* regions, const int64_t* ref_batch_pairs,

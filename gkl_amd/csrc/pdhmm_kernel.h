@@ -1218,4 +1218,21 @@ __global__ __launch_bounds__(64) void pdhmm_idle_class_selftest_kernel(uint32_t*
   if (lds[threadIdx.x] == 0) atomicOr(out, 0x80000000u);   // (keeps the stores above alive)
 }
 
+// The last launch of a device-resident call (gklhip_pdhmm_compute_device / _cross_device): the raw sums of the call's n
+// pairs become the caller's log10 likelihoods in HBM, out[i] = log10(sum[i]) - log10(2^1020) with the DEVICE's double
+// log10 (the host calls use the host libm: the last bits may differ) and the host tables' constant; sums_out, when given,
+// receives the sums themselves, bit for bit what the host path finalises.  A thread per pair, grid-stride.  *status != 0
+// (a forward kernel met a negative quality: PDHMM_INPUT_DATA_ERROR): the call fails and nothing is written.
+constexpr int kPdFinaliseBlock = 256;
+__global__ __launch_bounds__(kPdFinaliseBlock) void pdhmm_finalise_kernel(const double* sums, const int32_t* status, int64_t n, double log10_init,
+                                                                         double* out, double* sums_out) {
+  if (*status != 0) return;
+  const int64_t stride = (int64_t)gridDim.x * kPdFinaliseBlock;
+  for (int64_t i = (int64_t)blockIdx.x * kPdFinaliseBlock + threadIdx.x; i < n; i += stride) {
+    const double s = sums[i];
+    out[i] = log10(s) - log10_init;
+    if (sums_out) sums_out[i] = s;
+  }
+}
+
 }  // namespace gklhip

@@ -573,6 +573,17 @@ def load_pdhmm_library(path: Optional[str] = None):
     lib.gklhip_pdhmm_is_remote.restype = C.c_int
     lib.gklhip_pdhmm_server_stats.argtypes = [C.c_char_p, C.POINTER(PdhmmServerInfo)]
     lib.gklhip_pdhmm_server_stats.restype = C.c_int
+    # the device-resident calls: other builds and stubs of the library (an older build under GKL_AMD_PDHMM_LIB, the
+    # tests' stub) may not have them and must still load -- calling one there raises AttributeError
+    if hasattr(lib, "gklhip_pdhmm_compute_device"):
+        lib.gklhip_pdhmm_compute_device.argtypes = [C.c_void_p, C.POINTER(CPdhmmBatch), C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.gklhip_pdhmm_compute_device.restype = C.c_int
+    if hasattr(lib, "gklhip_pdhmm_compute_cross_device"):
+        lib.gklhip_pdhmm_compute_cross_device.argtypes = [C.c_void_p, C.POINTER(CPdhmmCross), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.gklhip_pdhmm_compute_cross_device.restype = C.c_int
+    if hasattr(lib, "gklhip_pdhmm_finalise_host"):
+        lib.gklhip_pdhmm_finalise_host.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
+        lib.gklhip_pdhmm_finalise_host.restype = C.c_int
     if path is None:
         _pd_lib = lib
     return lib
@@ -644,6 +655,82 @@ def pdhmm_server_stats(socket_path: str) -> dict:
     if st != OK:
         _raise_pdhmm(lib, st)
     return info.as_dict()
+
+
+def pdhmm_finalise_host(sums) -> np.ndarray:
+    """The host calls' finalisation of raw sums (gklhip_pdhmm_finalise_host): log10(sum) - log10(2^1020) with the host
+    libm, i.e. GKL's bits -- for the `sums` of PdhmmContext.compute_device / compute_cross_device, brought to the host
+    (a numpy array or a CPU tensor).  Needs no GPU."""
+    lib = load_pdhmm_library()
+    s = np.ascontiguousarray(np.asarray(sums), np.float64).reshape(-1)
+    out = np.empty(s.size, np.float64)
+    st = lib.gklhip_pdhmm_finalise_host(s.ctypes.data, s.size, out.ctypes.data)
+    if st != OK:
+        _raise_pdhmm(lib, st)
+    return out
+
+
+_PD_HAP_ARRAYS = ("hap_bases", "hap_pdbases")
+_PD_READ_ARRAYS = ("read_bases", "read_qual", "read_ins_qual", "read_del_qual", "gcp")
+
+
+@dataclass
+class PdhmmDeviceBatch:
+    """A PdhmmBatch whose seven byte arrays live in HBM: torch int8 tensors own the memory, the two length arrays stay
+    numpy on the host (the library's planner reads them).  One side of a cross product holds its own arrays only: the
+    other side's tensors and lengths are None."""
+    batch: int
+    max_hap_len: int
+    max_read_len: int
+    hap_tensors: Optional[tuple]    # (hap_bases, hap_pdbases), each [batch * max_hap_len]
+    read_tensors: Optional[tuple]   # (read_bases, read_qual, read_ins_qual, read_del_qual, gcp), each [batch * max_read_len]
+    hap_lengths: Optional[np.ndarray]
+    read_lengths: Optional[np.ndarray]
+
+    @staticmethod
+    def upload(b, device="cuda:0", side: str = "both") -> "PdhmmDeviceBatch":
+        """b: a PdhmmBatch (or anything with its fields).  side: "both", or "reads" / "haps" for one side of a cross product."""
+        import torch
+        up = lambda names: tuple(torch.from_numpy(np.ascontiguousarray(getattr(b, n), np.int8).reshape(-1)).to(device)  # noqa: E731
+                                 for n in names)
+        haps, reads = side in ("both", "haps"), side in ("both", "reads")
+        if not (haps or reads):
+            raise IllegalArgumentException(f"side {side!r} (both, reads or haps)")
+        return PdhmmDeviceBatch(b.batch, b.max_hap_len if haps else 0, b.max_read_len if reads else 0,
+                                up(_PD_HAP_ARRAYS) if haps else None, up(_PD_READ_ARRAYS) if reads else None,
+                                np.ascontiguousarray(b.hap_lengths, np.int64) if haps else None,
+                                np.ascontiguousarray(b.read_lengths, np.int64) if reads else None)
+
+    @staticmethod
+    def upload_cross(reads, haps, device="cuda:0"):
+        """The cross form: (reads_db, haps_db) for PdhmmContext.compute_cross_device, from what compute_cross takes."""
+        return PdhmmDeviceBatch.upload(reads, device, "reads"), PdhmmDeviceBatch.upload(haps, device, "haps")
+
+    def _checked(self, tensors, row: int, what: str):
+        # the library trusts these addresses: a tensor of the wrong kind or size would be read out of bounds on the device
+        if tensors is None or (self.hap_lengths if what == "haplotype" else self.read_lengths) is None:
+            raise IllegalArgumentException(f"this device batch holds no {what} arrays")
+        for t in tensors:
+            if not t.is_cuda or t.element_size() != 1 or not t.is_contiguous() or t.numel() != self.batch * row:
+                raise IllegalArgumentException(f"{what} arrays must be contiguous one-byte CUDA tensors of batch * max length = "
+                                               f"{self.batch * row} elements")
+        return [t.data_ptr() for t in tensors]
+
+    def hap_pointers(self):
+        return self._checked(self.hap_tensors, self.max_hap_len, "haplotype")
+
+    def read_pointers(self):
+        return self._checked(self.read_tensors, self.max_read_len, "read")
+
+
+def _pd_result_tensor(t, n: int, device, name: str):
+    """`out` / `sums` of a device-resident call: given, it must be a contiguous float64 tensor of n elements on `device`."""
+    import torch
+    if t is None:
+        return torch.empty(n, dtype=torch.float64, device=device)
+    if t.dtype != torch.float64 or not t.is_cuda or t.device != device or not t.is_contiguous() or t.numel() != n:
+        raise IllegalArgumentException(f"{name} must be a contiguous float64 tensor of {n} elements on {device}")
+    return t
 
 
 class PdhmmContext:
@@ -744,6 +831,52 @@ class PdhmmContext:
         errors = [None if status[k] == OK else _pdhmm_exception(status[k], msg if k == first or status[k] == status[first] else
                                                                 f"region {k} failed with status {status[k]}") for k in range(n)]
         raise PdhmmMultiError([o if status[k] == OK else None for k, o in enumerate(outs)], [int(status[k]) for k in range(n)], errors)
+
+    # -- device-resident calls: byte arrays and results in HBM; `out` / `sums` are torch float64 CUDA tensors --
+    def compute_device(self, db: PdhmmDeviceBatch, out=None, sums=None, stream=None):
+        """gklhip_pdhmm_compute_device: compute() with the arrays of `db` in HBM.  Returns the float64 tensor of log10
+        likelihoods (`out`, or a new one), evaluated with the device's log10: equal to compute() to the last bits, not
+        bit for bit.  sums: a float64 tensor that receives the raw sums -- pdhmm_finalise_host(sums.cpu()) is compute()'s
+        output byte for byte.  The call is ordered behind the work already on `stream` (default: torch's current stream)
+        and synchronous: the results are in place when it returns."""
+        import torch
+        hp, rp = db.hap_pointers(), db.read_pointers()
+        device = db.read_tensors[0].device
+        out = _pd_result_tensor(out, max(db.batch, 0), device, "out")
+        if sums is not None:
+            sums = _pd_result_tensor(sums, max(db.batch, 0), device, "sums")
+        if stream is None:
+            stream = torch.cuda.current_stream(device)
+        cb = CPdhmmBatch(db.batch, db.max_hap_len, db.max_read_len, *hp, *rp, db.hap_lengths.ctypes.data, db.read_lengths.ctypes.data)
+        st = self.lib.gklhip_pdhmm_compute_device(self.handle, C.byref(cb), out.data_ptr(), None if sums is None else sums.data_ptr(),
+                                                  stream.cuda_stream)
+        if st != OK:
+            self._raise(st)
+        return out
+
+    def compute_cross_device(self, reads_db: PdhmmDeviceBatch, haps_db: PdhmmDeviceBatch, ref_batch_pairs: int = 0, out=None, sums=None,
+                             stream=None):
+        """gklhip_pdhmm_compute_cross_device: compute_cross() with both sides in HBM (PdhmmDeviceBatch.upload_cross),
+        out[r * n_haps + h].  As compute_device; the two haplotype arrays are read back to the host once, early, for
+        the planner."""
+        import torch
+        hp, rp = haps_db.hap_pointers(), reads_db.read_pointers()
+        device = reads_db.read_tensors[0].device
+        if haps_db.hap_tensors[0].device != device:
+            raise IllegalArgumentException("reads and haplotypes are on different devices")
+        n = max(reads_db.batch * haps_db.batch, 0)
+        out = _pd_result_tensor(out, n, device, "out")
+        if sums is not None:
+            sums = _pd_result_tensor(sums, n, device, "sums")
+        if stream is None:
+            stream = torch.cuda.current_stream(device)
+        cb = CPdhmmCross(reads_db.batch, haps_db.batch, haps_db.max_hap_len, reads_db.max_read_len, *hp, *rp,
+                         haps_db.hap_lengths.ctypes.data, reads_db.read_lengths.ctypes.data)
+        st = self.lib.gklhip_pdhmm_compute_cross_device(self.handle, C.byref(cb), C.c_int64(ref_batch_pairs), out.data_ptr(),
+                                                        None if sums is None else sums.data_ptr(), stream.cuda_stream)
+        if st != OK:
+            self._raise(st)
+        return out
 
     def last_kernel_ms(self) -> float:
         return float(self.lib.gklhip_pdhmm_last_kernel_ms(self.handle))

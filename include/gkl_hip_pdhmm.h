@@ -114,6 +114,35 @@ int gklhip_pdhmm_compute_cross(gklhip_pdhmm_ctx* ctx, const gklhip_pdhmm_cross* 
  * initialisation like the reference's getMaxMemoryAvailable (pdhmm-implementation.h:204-235), so that identical calls
  * are cut -- and therefore rounded -- identically.  What the JNI shim's computeLikelihoodsNative calls. */
 int gklhip_pdhmm_compute_cross_batched(gklhip_pdhmm_ctx* ctx, const gklhip_pdhmm_cross* batch, int64_t ref_batch_pairs, double* out_host);
+/* ---- device-resident calls: the byte arrays and the results stay in HBM (cf. gklhip_compute_device of the PairHMM) ----
+ * dev_batch: the seven byte arrays (hap_bases, hap_pdbases, read_bases, read_qual, read_ins_qual, read_del_qual, gcp) are
+ * addresses in HBM on the context's device, same row strides as in the host calls; hap_lengths and read_lengths are HOST
+ * arrays as always (the planner and the argument checks read them).  out_dev: [n_pairs] doubles in HBM, in the host
+ * call's order (paired: by position; cross: r * n_haps + h).  sums_dev: NULL, or [n_pairs] doubles in HBM that receive
+ * the raw sums of the same pairs -- bit for bit the doubles the host calls finalise.
+ * Ordering: the library's work is ordered behind everything already enqueued on hip_stream (a hipStream_t; NULL = HIP's
+ * default stream): an event recorded there, which the context's stream waits for.  The calls are SYNCHRONOUS: they return
+ * after the context's stream has drained, the results are in place and the status is final.  There is no asynchronous
+ * variant.  The cross call waits once early as well: its planner reads haplotype bytes on the host, so hap_bases and
+ * hap_pdbases (n_haps * max_hap_len bytes each) are first copied back to pinned host memory, behind the caller's
+ * stream; the read arrays -- the bulk -- never leave the device.
+ * Arithmetic: fma mode, tail mode and ref_batch_pairs act exactly as in the host calls, and the sums are the host calls'
+ * bit for bit.  out_dev[i] = log10(sum[i]) - log10(2^1020) is evaluated ON THE DEVICE in double: it is NOT guaranteed to
+ * be bit-identical to the host calls' output, which takes glibc's log10 like GKL (differences are in the last bits).  A
+ * caller that needs GKL's bits asks for sums_dev and finalises them with gklhip_pdhmm_finalise_host.
+ * Errors: the argument checks of the host calls, with the same statuses and texts (a NULL out_dev like a NULL out_host),
+ * before anything touches the device.  A negative ins / del / gcp quality is found on the device as in the host calls:
+ * GKLHIP_ERR_INVALID_ARG, and out_dev and sums_dev are left untouched.  On a client context of the server both return
+ * GKLHIP_ERR_UNSUPPORTED before anything else.  These calls never enter the combiner and do not count in
+ * gklhip_pdhmm_combine_counts; gklhip_pdhmm_last_routing and gklhip_pdhmm_last_kernel_ms (the forward launches, not the
+ * finalisation) report as after the host call of the same problem. */
+int gklhip_pdhmm_compute_device(gklhip_pdhmm_ctx* ctx, const gklhip_pdhmm_batch* dev_batch, double* out_dev,
+                                double* sums_dev /* may be NULL */, void* hip_stream);
+int gklhip_pdhmm_compute_cross_device(gklhip_pdhmm_ctx* ctx, const gklhip_pdhmm_cross* dev_batch, int64_t ref_batch_pairs,
+                                      double* out_dev, double* sums_dev /* may be NULL */, void* hip_stream);
+/* The host calls' finalisation of n raw sums (host arrays): out[i] = log10(sums[i]) - log10(2^1020) with the host libm.
+ * Needs no context and makes no HIP call. */
+int gklhip_pdhmm_finalise_host(const double* sums, int64_t n, double* out);
 /* Several region calls in ONE set of launches: region k's output is, byte for byte, what
  * gklhip_pdhmm_compute_cross_batched(ctx, &regions[k], ref_batch_pairs[k], out_host[k]) writes on the same context -- whichever
  * other regions ride along, in whatever order, in both fma modes and both tail modes (tail mode 1: every region is cut into
