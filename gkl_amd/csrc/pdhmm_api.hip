@@ -398,8 +398,9 @@ constexpr size_t kPdStageBytes = (size_t)4 << 20;
 // flags of a multi-region call
 constexpr size_t kPdMiscBytes = 256 + 4 * (size_t)kPdMaxRegions;
 // Up to this many pairs (1 MB of sums) the kernels store the sums straight into pinned host memory (pd_plan_counts:
-// sums_direct).  A multi-region call has no other way to return them, so this is also the most pairs it takes: both
-// paths depend on the one constant.
+// sums_direct).  The host form of a multi-region call has no other way to return them, so this is also the most pairs a
+// shared launch set takes (the device form, whose sums stay in HBM, keeps the same limit): both paths depend on the
+// one constant.
 constexpr size_t kPdMultiMaxPairs = 131072;
 // Padded input bytes (haplotype bases + the five read arrays) from which a paired call of 65 536 pairs or more is cut
 // into upload slices (pd_plan_slices), and from which a call too big to stage leaves its copies to a helper thread
@@ -1315,125 +1316,198 @@ int pd_run_locked(gklhip_pdhmm_ctx* c, const PdProblem& q_call, double* out_host
   return dev ? pd_finish_device(c, q, plan, &up, &clock, *dev) : pd_finish(c, q, plan, &up, &clock, out_host);
 }
 
-// ---- several region calls in one set of launches (gklhip_pdhmm_compute_cross_multi) ----
+// ==== several region calls in one set of launches (pd_run_multi_locked, at the end): the host form
+// (gklhip_pdhmm_compute_cross_multi: arrays and results on the host) and the device form (_cross_multi_device: the byte
+// arrays and the results in HBM).  Plan, stage the inputs, stage the job tables, launch, finish: the two forms differ in
+// how the inputs are staged and in the finish only ====
 struct PdMultiRegion {
   PdProblem q;
-  double* out;
+  double* out;                          // host form: a host array; device form: HBM
+  double* sums_out = nullptr;           // device form: HBM, or NULL
   int32_t flag = 0;                     // out: the region's input-error flag (PDHMM_INPUT_DATA_ERROR)
   int32_t routing[3] = {0, 0, 0};       // out: its haplotypes by kernel
 };
 
-// Bytes of the regions' inputs in the layout of a multi-region call: one common row stride per side.
-size_t pd_multi_input_bytes(const std::vector<PdMultiRegion>& R) {
-  size_t nh = 0, nr = 0, mh = 0, mr = 0;
-  for (const PdMultiRegion& r : R) {
-    nh += (size_t)r.q.n_hap_items; nr += (size_t)r.q.n_read_items;
-    mh = std::max(mh, (size_t)r.q.max_hap_len); mr = std::max(mr, (size_t)r.q.max_read_len);
+// The set's totals and its input layout: one common row stride per side.
+struct PdMultiShape {
+  size_t NH = 0, NR = 0, NP = 0, mh = 0, mr = 0;
+  explicit PdMultiShape(const std::vector<PdMultiRegion>& R) {
+    for (const PdMultiRegion& r : R) {
+      NH += (size_t)r.q.n_hap_items; NR += (size_t)r.q.n_read_items; NP += (size_t)r.q.n_pairs;
+      mh = std::max(mh, (size_t)r.q.max_hap_len); mr = std::max(mr, (size_t)r.q.max_read_len);
+    }
   }
-  return PdInputLayout(nh, nr, mh, mr).total;
-}
+  PdInputLayout layout() const { return PdInputLayout(NH, NR, mh, mr); }
+};
+// Bytes of the regions' inputs in the layout of a multi-region call.
+size_t pd_multi_input_bytes(const std::vector<PdMultiRegion>& R) { return PdMultiShape(R).layout().total; }
 
-// The regions of R (all valid, same context settings; at most kPdMaxRegions, kPdMultiMaxPairs pairs, kPdStageBytes of
-// inputs) as ONE problem: planned region by region exactly as pd_run_locked plans a single call, then concatenated -- one
-// pinned block and one copy for the inputs, one for the job tables, one pdhmm_entries_kernel, at most one launch each of the
-// table, predicate and full kernels and one tail launch, the sums straight into pinned memory, one host finalisation.
-// The return value is the status of the launch set (a HIP failure fails every region); R[k].flag != 0: region k had a
-// negative quality (PDHMM_INPUT_DATA_ERROR), its output is not written.
-int pd_run_multi_locked(gklhip_pdhmm_ctx* c, std::vector<PdMultiRegion>& R) {
-  HIP_TRY(hipSetDevice(c->device));
-  hipStream_t s = c->stream;
-  const int K = (int)R.size();
-  std::vector<PdCrossPlan> plans((size_t)K);
+// ---- step 1: the plan.  Every region planned exactly as pd_run_locked plans a single call, then the region table. ----
+struct PdMultiPlan {
+  std::vector<PdCrossPlan> plans;
+  std::vector<PdRegion> regions;          // K + 1 (pd_build_regions)
+  std::vector<int32_t> tab_group_start;
+  size_t n_tab_haps = 0, n_hot_haps = 0, n_full_haps = 0, n_chunks = 0, n_general = 0, n_tail = 0;
+  int n_tab_units = 0, n_hot_units = 0, n_full_units = 0, entry_stride = 0, n_blocks = 0;
+};
+// Q[k]: region k's problem as the planners may read it (the device form: its haplotype arrays are the pinned copies).
+void pd_multi_plan(gklhip_pdhmm_ctx* c, const std::vector<PdProblem>& Q, const PdMultiShape& sh, PdMultiPlan* p) {
+  const int K = (int)Q.size();
+  p->plans.resize((size_t)K);
   std::vector<PdRegionShape> shapes((size_t)K);
   std::vector<size_t> tab_haps((size_t)K);
   std::vector<int32_t> groups((size_t)K);
-  size_t NH = 0, NR = 0, NP = 0, mh = 0, mr = 0;
-  size_t n_tab_haps = 0, n_hot_haps = 0, n_full_haps = 0, n_chunks = 0, n_general = 0, n_tail = 0;
   int64_t n_cross_tab = 0;   // (haplotype, chunk) jobs of the table launch
   for (int k = 0; k < K; k++) {
-    const PdProblem& q = R[(size_t)k].q;
-    pd_plan_cross_jobs(c, q, &plans[(size_t)k]);
-    pd_plan_cross_routing(c, q, &plans[(size_t)k]);
-    const PdCrossPlan& pl = plans[(size_t)k];
-    NH += (size_t)q.n_hap_items; NR += (size_t)q.n_read_items; NP += (size_t)q.n_pairs;
-    mh = std::max(mh, (size_t)q.max_hap_len); mr = std::max(mr, (size_t)q.max_read_len);
+    const PdProblem& q = Q[(size_t)k];
+    pd_plan_cross_jobs(c, q, &p->plans[(size_t)k]);
+    pd_plan_cross_routing(c, q, &p->plans[(size_t)k]);
+    const PdCrossPlan& pl = p->plans[(size_t)k];
     tab_haps[(size_t)k] = pl.n_tab_haps;
-    n_tab_haps += pl.n_tab_haps; n_hot_haps += pl.n_clean_haps - pl.n_tab_haps; n_full_haps += (size_t)q.n_hap_items - pl.n_clean_haps;
-    n_chunks += pl.chunk_steps.size(); n_general += pl.job_pair.size(); n_tail += pl.n_tail;
+    p->n_tab_haps += pl.n_tab_haps; p->n_hot_haps += pl.n_clean_haps - pl.n_tab_haps; p->n_full_haps += (size_t)q.n_hap_items - pl.n_clean_haps;
+    p->n_chunks += pl.chunk_steps.size(); p->n_general += pl.job_pair.size(); p->n_tail += pl.n_tail;
     n_cross_tab += (int64_t)pl.chunk_steps.size() * (int64_t)pl.n_tab_haps;
   }
-  std::vector<int32_t> tab_group_start;
-  pd_size_tab_groups(tab_haps.data(), K, n_cross_tab, &tab_group_start, groups.data());
+  pd_size_tab_groups(tab_haps.data(), K, n_cross_tab, &p->tab_group_start, groups.data());
   for (int k = 0; k < K; k++) {
-    const PdProblem& q = R[(size_t)k].q;
-    const PdCrossPlan& pl = plans[(size_t)k];
+    const PdProblem& q = Q[(size_t)k];
+    const PdCrossPlan& pl = p->plans[(size_t)k];
     shapes[(size_t)k] = PdRegionShape{q.n_read_items, q.n_hap_items, (int32_t)pl.chunk_steps.size(),
                                       {groups[(size_t)k], (int32_t)(pl.n_clean_haps - pl.n_tab_haps), (int32_t)((size_t)q.n_hap_items - pl.n_clean_haps)}};
   }
-  std::vector<PdRegion> regions((size_t)K + 1);
-  pd_build_regions(shapes.data(), K, regions.data());
-  const int n_tab_units = regions[(size_t)K].unit_start[kPdLaunchTab], n_hot_units = regions[(size_t)K].unit_start[kPdLaunchHot],
-            n_full_units = regions[(size_t)K].unit_start[kPdLaunchFull];
+  p->regions.resize((size_t)K + 1);
+  pd_build_regions(shapes.data(), K, p->regions.data());
+  p->n_tab_units = p->regions[(size_t)K].unit_start[kPdLaunchTab];
+  p->n_hot_units = p->regions[(size_t)K].unit_start[kPdLaunchHot];
+  p->n_full_units = p->regions[(size_t)K].unit_start[kPdLaunchFull];
+  p->entry_stride = ((int)sh.mh + 2 * kLanes + 4 + 63) / 64 * 64;
+  const int n_jobs_max = std::max(std::max(p->n_tab_units, p->n_hot_units), p->n_full_units + (int)p->n_general);
+  p->n_blocks = std::max(1, std::min(std::max(n_jobs_max, (int)p->n_tail), 256 * 8));
+}
 
-  // ---- inputs: one pinned block, every region's rows at the common strides, one copy ----
-  const PdInputLayout in(NH, NR, mh, mr);
+// ---- step 2: the inputs go to the device, every region's rows at the common strides ----
+// Host form: one pinned block, one copy.
+int pd_multi_stage_inputs_host(gklhip_pdhmm_ctx* c, const std::vector<PdMultiRegion>& R, const PdInputLayout& in, const PdRegion* regions) {
   int rc;
   if ((rc = c->inputs.reserve(in.total)) || (rc = c->stage_in.reserve(in.total))) return rc;
-  unsigned char* d = c->inputs.as<unsigned char>();
-  {
-    unsigned char* h = c->stage_in.as<unsigned char>();
-    for (int k = 0; k < K; k++) {
-      const PdProblem& q = R[(size_t)k].q;
-      const PdRegion& rg = regions[(size_t)k];
-      for (const PdInputArray& v : pd_input_arrays(in, q)) {   // the region's rows at the common strides
-        unsigned char* dst = h + v.offset + (size_t)(v.hap ? rg.hap_base : rg.read_base) * v.dst_row;
-        if (v.dst_row == v.src_row) { memcpy(dst, v.src, v.n_items * v.src_row); continue; }
-        for (size_t i = 0; i < v.n_items; i++) memcpy(dst + i * v.dst_row, v.src + i * v.src_row, v.src_row);
-      }
+  unsigned char* h = c->stage_in.as<unsigned char>();
+  for (size_t k = 0; k < R.size(); k++) {
+    const PdRegion& rg = regions[k];
+    for (const PdInputArray& v : pd_input_arrays(in, R[k].q)) {   // the region's rows at the common strides
+      unsigned char* dst = h + v.offset + (size_t)(v.hap ? rg.hap_base : rg.read_base) * v.dst_row;
+      if (v.dst_row == v.src_row) { memcpy(dst, v.src, v.n_items * v.src_row); continue; }
+      for (size_t i = 0; i < v.n_items; i++) memcpy(dst + i * v.dst_row, v.src + i * v.src_row, v.src_row);
     }
-    HIP_TRY(hipMemcpyAsync(d, h, in.total, hipMemcpyHostToDevice, s));
   }
+  HIP_TRY(hipMemcpyAsync(c->inputs.p, h, in.total, hipMemcpyHostToDevice, c->stream));
+  return GKLHIP_OK;
+}
 
-  // ---- job tables: the regions' plans, shifted to the concatenated indices, in one more pinned block ----
-  const int entry_stride = ((int)mh + 2 * kLanes + 4 + 63) / 64 * 64;
-  const int n_jobs_max = std::max(std::max(n_tab_units, n_hot_units), n_full_units + (int)n_general);
-  const int n_blocks = std::max(1, std::min(std::max(n_jobs_max, (int)n_tail), 256 * 8));
-  if ((rc = c->entries.reserve(NH * (size_t)entry_stride * 4))) return rc;
-  if (n_tab_haps && (rc = c->entries_tab.reserve(2 * NH * (size_t)entry_stride * 4))) return rc;
+// Device form.  `inputs` and `stage_in` hold the set's layout with the gather table behind it (PdGatherTable), at the same
+// offsets in both.  Behind the caller's stream: ONE copy up -- the regions' host length arrays into o_hl / o_rl, the
+// descriptors and the result pointers behind the layout, contiguous in both blocks --, pdhmm_gather_regions_kernel, ONE
+// copy back of [o_hb, o_rb): both haplotype arrays of all regions, at the common stride, for the planners
+// (pd_plan_cross_routing, has_odd_base read haplotype bytes on the host); the call's one early wait.  Q[k]: region k's
+// problem with its haplotype arrays in that pinned copy.
+int pd_multi_stage_inputs_device(gklhip_pdhmm_ctx* c, const std::vector<PdMultiRegion>& R, const PdInputLayout& in, hipStream_t after,
+                                 std::vector<PdProblem>* Q) {
+  const int K = (int)R.size();
+  const hipStream_t s = c->stream;
+  const PdGatherTable T(in, K);
+  int rc;
+  if ((rc = c->inputs.reserve(T.total)) || (rc = c->stage_in.reserve(T.total))) return rc;
+  unsigned char *d = c->inputs.as<unsigned char>(), *h = c->stage_in.as<unsigned char>();
+  PdGatherRegion G[kPdMaxRegions];
+  PdRegionResults* results = reinterpret_cast<PdRegionResults*>(h + T.o_results);
+  size_t hap_base = 0, read_base = 0;
+  for (int k = 0; k < K; k++) {
+    const PdProblem& q = R[(size_t)k].q;
+    G[k] = PdGatherRegion{{q.hap_bases, q.hap_pdbases, q.read_bases, q.read_qual, q.read_ins_qual, q.read_del_qual, q.gcp},
+                          q.n_hap_items, q.n_read_items, q.max_hap_len, q.max_read_len};
+    results[k] = PdRegionResults{R[(size_t)k].out, R[(size_t)k].sums_out};
+    memcpy(h + in.o_hl + hap_base * 8, q.hap_lengths, (size_t)q.n_hap_items * 8);
+    memcpy(h + in.o_rl + read_base * 8, q.read_lengths, (size_t)q.n_read_items * 8);
+    PdProblem& pq = (*Q)[(size_t)k];   // the planners' view: the haplotype rows at the common stride
+    pq.hap_bases = reinterpret_cast<const int8_t*>(h + in.o_hb + hap_base * in.hap_row);
+    pq.hap_pdbases = reinterpret_cast<const int8_t*>(h + in.o_hp + hap_base * in.hap_row);
+    pq.max_hap_len = (int32_t)in.hap_row;
+    hap_base += (size_t)q.n_hap_items; read_base += (size_t)q.n_read_items;
+  }
+  PdGatherDesc* descs = reinterpret_cast<PdGatherDesc*>(h + T.o_desc);
+  pd_build_gather(G, K, in, descs);
+  uint32_t most = 1;   // bytes of the largest array
+  for (int i = 0; i < K * kPdGatherArrays; i++) most = std::max(most, descs[i].n_items * descs[i].src_row);
+  // everything the call enqueues is ordered behind what the caller's stream already holds
+  HIP_TRY(hipEventRecord(c->dev_ev, after));
+  HIP_TRY(hipStreamWaitEvent(s, c->dev_ev, 0));
+  HIP_TRY(hipMemcpyAsync(d + in.o_hl, h + in.o_hl, T.total - in.o_hl, hipMemcpyHostToDevice, s));
+  const unsigned per_block = kPdGatherBlock * 16;
+  hipLaunchKernelGGL(pdhmm_gather_regions_kernel, dim3(std::min((most + per_block - 1) / per_block, 64u), (unsigned)(K * kPdGatherArrays)),
+                     dim3(kPdGatherBlock), 0, s, reinterpret_cast<const PdGatherDesc*>(d + T.o_desc), d);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(h + in.o_hb, d + in.o_hb, in.o_rb - in.o_hb, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return GKLHIP_OK;
+}
+
+// ---- step 3: the device buffers and the job tables ----
+// `sums_pin` holds the host form's sums (the kernels store them straight into it) and, in both forms, the status words
+// that come back behind them; the device form's sums stay in `sums`.
+int pd_multi_reserve(gklhip_pdhmm_ctx* c, const PdMultiShape& sh, const PdMultiPlan& p, bool device) {
+  int rc;
+  if ((rc = c->entries.reserve(sh.NH * (size_t)p.entry_stride * 4))) return rc;
+  if (p.n_tab_haps && (rc = c->entries_tab.reserve(2 * sh.NH * (size_t)p.entry_stride * 4))) return rc;
   if ((rc = c->misc.reserve(kPdMiscBytes))) return rc;
-  if ((rc = c->carry.reserve((size_t)n_blocks * 2 * (6 * (size_t)entry_stride + 64) * 8))) return rc;   // (carry_len = entry_stride)
-  if ((rc = c->sums_pin.reserve(NP * 8 + 4 * ((size_t)kPdMiscRegionFlags + (size_t)kPdMaxRegions)))) return rc;
-  const size_t o_rg = 0, o_cl = o_rg + pd_up(((size_t)K + 1) * sizeof(PdRegion)), o_cs = o_cl + pd_up(n_chunks * kLanes * sizeof(PlanLane)),
-               o_cr = o_cs + pd_up(n_chunks * 4), o_ho = o_cr + pd_up(n_chunks * 4), o_tg = o_ho + pd_up(NH * 4),
-               o_nc = o_tg + pd_up(tab_group_start.size() * 4), o_cc = o_nc + pd_up(NH), o_jp = o_cc + pd_up(NH * 32), o_jn = o_jp + pd_up(n_general * 4),
-               o_js = o_jn + pd_up(n_general * 4), o_jf = o_js + pd_up(n_general), o_fj = o_jf + pd_up(n_general), o_fc = o_fj + pd_up(n_general * 4),
-               o_tl = o_fc + 256, o_tp = o_tl + pd_up(n_tail * kLanes * sizeof(PlanLane)), o_tn = o_tp + pd_up(n_tail * 4),
-               o_ts = o_tn + pd_up(n_tail * 4), staged_total = o_ts + pd_up(n_tail),
-               o_jl = staged_total, jobs_total = o_jl + pd_up(n_general * kLanes * sizeof(PlanLane));   // (a striped job's lane row stays unused)
-  if ((rc = c->jobs.reserve(jobs_total + 256)) || (rc = c->stage_jobs.reserve(staged_total + 256))) return rc;
-  unsigned char* dj = c->jobs.as<unsigned char>();
+  if ((rc = c->carry.reserve((size_t)p.n_blocks * 2 * (6 * (size_t)p.entry_stride + 64) * 8))) return rc;   // (carry_len = entry_stride)
+  if (device && (rc = c->sums.reserve(sh.NP * 8))) return rc;
+  return c->sums_pin.reserve((device ? 0 : sh.NP * 8) + 4 * ((size_t)kPdMiscRegionFlags + (size_t)kPdMaxRegions));
+}
+
+// A multi-region call's block in `jobs`: the region table (rg), the launches' haplotype lists (ho), the length of the
+// full launch's list (fc) and the tables of PdJobOffsets; everything but the lane rows of the listed jobs (jl: striped
+// jobs, their rows stay unused) is staged in one pinned block.
+struct PdMultiJobLayout : PdJobOffsets {
+  size_t rg, ho, fc, staged_total, total;
+  PdMultiJobLayout(size_t K, size_t NH, const PdMultiPlan& p) {
+    const size_t n_chunks = p.n_chunks, n_general = p.n_general, n_tail = p.n_tail;
+    rg = 0; cl = rg + pd_up((K + 1) * sizeof(PdRegion)); cs = cl + pd_up(n_chunks * kLanes * sizeof(PlanLane));
+    cr = cs + pd_up(n_chunks * 4); ho = cr + pd_up(n_chunks * 4); tg = ho + pd_up(NH * 4);
+    nc = tg + pd_up(p.tab_group_start.size() * 4); cc = nc + pd_up(NH); jp = cc + pd_up(NH * 32); jn = jp + pd_up(n_general * 4);
+    js = jn + pd_up(n_general * 4); jf = js + pd_up(n_general); fj = jf + pd_up(n_general); fc = fj + pd_up(n_general * 4);
+    tl = fc + 256; tp = tl + pd_up(n_tail * kLanes * sizeof(PlanLane)); tn = tp + pd_up(n_tail * 4);
+    ts = tn + pd_up(n_tail * 4); staged_total = ts + pd_up(n_tail);
+    jl = staged_total; total = jl + pd_up(n_general * kLanes * sizeof(PlanLane));
+  }
+};
+
+// The regions' plans, shifted to the concatenated indices, in one pinned block and one copy; clears the status words.
+int pd_multi_stage_tables(gklhip_pdhmm_ctx* c, const PdMultiPlan& p, const PdMultiJobLayout& L) {
+  const int K = (int)p.plans.size();
+  const size_t n_general = p.n_general;
+  int rc;
+  if ((rc = c->jobs.reserve(L.total + 256)) || (rc = c->stage_jobs.reserve(L.staged_total + 256))) return rc;
   {
     unsigned char* hj = c->stage_jobs.as<unsigned char>();
-    memcpy(hj + o_rg, regions.data(), ((size_t)K + 1) * sizeof(PdRegion));
-    memcpy(hj + o_tg, tab_group_start.data(), tab_group_start.size() * 4);
-    PlanLane* cl = reinterpret_cast<PlanLane*>(hj + o_cl);
-    int32_t *cs = reinterpret_cast<int32_t*>(hj + o_cs), *cr = reinterpret_cast<int32_t*>(hj + o_cr);
-    int32_t* ho = reinterpret_cast<int32_t*>(hj + o_ho);   // [table launch's list | predicate launch's | byte-comparing launch's]
-    int32_t *ho_tab = ho, *ho_hot = ho + n_tab_haps, *ho_full = ho + n_tab_haps + n_hot_haps;
-    uint8_t* nc = hj + o_nc;
-    uint32_t* cc = reinterpret_cast<uint32_t*>(hj + o_cc);
-    int32_t *jp = reinterpret_cast<int32_t*>(hj + o_jp), *fj = reinterpret_cast<int32_t*>(hj + o_fj);
-    PlanLane* tl = reinterpret_cast<PlanLane*>(hj + o_tl);
-    int32_t *tp = reinterpret_cast<int32_t*>(hj + o_tp), *tn = reinterpret_cast<int32_t*>(hj + o_tn);
-    uint8_t* ts = hj + o_ts;
-    memset(hj + o_js, 1, n_general);
-    memset(hj + o_jf, 0, n_general);
-    memset(hj + o_jn, 0, n_general * 4);   // (job_steps: unused by striped jobs)
+    memcpy(hj + L.rg, p.regions.data(), ((size_t)K + 1) * sizeof(PdRegion));
+    memcpy(hj + L.tg, p.tab_group_start.data(), p.tab_group_start.size() * 4);
+    PlanLane* cl = reinterpret_cast<PlanLane*>(hj + L.cl);
+    int32_t *cs = reinterpret_cast<int32_t*>(hj + L.cs), *cr = reinterpret_cast<int32_t*>(hj + L.cr);
+    int32_t* ho = reinterpret_cast<int32_t*>(hj + L.ho);   // [table launch's list | predicate launch's | byte-comparing launch's]
+    int32_t *ho_tab = ho, *ho_hot = ho + p.n_tab_haps, *ho_full = ho + p.n_tab_haps + p.n_hot_haps;
+    uint8_t* nc = hj + L.nc;
+    uint32_t* cc = reinterpret_cast<uint32_t*>(hj + L.cc);
+    int32_t *jp = reinterpret_cast<int32_t*>(hj + L.jp), *fj = reinterpret_cast<int32_t*>(hj + L.fj);
+    PlanLane* tl = reinterpret_cast<PlanLane*>(hj + L.tl);
+    int32_t *tp = reinterpret_cast<int32_t*>(hj + L.tp), *tn = reinterpret_cast<int32_t*>(hj + L.tn);
+    uint8_t* ts = hj + L.ts;
+    memset(hj + L.js, 1, n_general);
+    memset(hj + L.jf, 0, n_general);
+    memset(hj + L.jn, 0, n_general * 4);   // (job_steps: unused by striped jobs)
     for (size_t j = 0; j < n_general; j++) fj[j] = (int32_t)j;
-    *reinterpret_cast<int32_t*>(hj + o_fc) = (int32_t)n_general;
+    *reinterpret_cast<int32_t*>(hj + L.fc) = (int32_t)n_general;
     for (int k = 0; k < K; k++) {
-      const PdCrossPlan& pl = plans[(size_t)k];
-      const PdRegion& rg = regions[(size_t)k];
+      const PdCrossPlan& pl = p.plans[(size_t)k];
+      const PdRegion& rg = p.regions[(size_t)k];
       for (const PlanLane& l : pl.cross_lanes) *cl++ = PlanLane{l.read < 0 ? -1 : l.read + rg.read_base, l.block};
       for (const int32_t v : pl.chunk_steps) *cs++ = v;
       for (const int32_t v : pl.chunk_rep) *cr++ = v + rg.read_base;
@@ -1450,53 +1524,110 @@ int pd_run_multi_locked(gklhip_pdhmm_ctx* c, std::vector<PdMultiRegion>& R) {
       for (const int32_t v : pl.tail_steps) *tn++ = v;
       for (const uint8_t v : pl.tail_striped) *ts++ = v;
     }
-    HIP_TRY(hipMemcpyAsync(dj, hj, staged_total, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(c->jobs.p, hj, L.staged_total, hipMemcpyHostToDevice, c->stream));
   }
-  HIP_TRY(hipMemsetAsync(c->misc.p, 0, kPdMiscBytes, s));
+  HIP_TRY(hipMemsetAsync(c->misc.p, 0, kPdMiscBytes, c->stream));
+  return GKLHIP_OK;
+}
 
-  const PdJobOffsets o{o_jl, o_jp, o_jn, o_js, o_cl, o_cs, o_cr, o_nc, o_cc, o_jf, o_fj, o_tg, o_tl, o_tp, o_tn, o_ts};
-  PdArgs a = pd_common_args(c, in, o, NH, (int32_t)mh, (int32_t)mr, entry_stride, n_tab_haps != 0);
-  a.batch = (int32_t)NP;
+// ---- step 4: the launches.  One pdhmm_entries_kernel, at most one launch each of the table, predicate and full kernels and
+// one tail launch, in their multi-region instantiations; `sums`: where they store the set's sums (a device address). ----
+int pd_multi_launch(gklhip_pdhmm_ctx* c, const PdMultiShape& sh, const PdInputLayout& in, const PdMultiPlan& p, const PdMultiJobLayout& L, double* sums) {
+  const hipStream_t s = c->stream;
+  const unsigned char* dj = c->jobs.as<unsigned char>();
+  PdArgs a = pd_common_args(c, in, L, sh.NH, (int32_t)sh.mh, (int32_t)sh.mr, p.entry_stride, p.n_tab_haps != 0);
+  a.batch = (int32_t)sh.NP;
   a.cross_haps = 1;   // (cross layout; the pair index comes from the region table)
-  {
-    void* dp = nullptr;
-    HIP_TRY(hipHostGetDevicePointer(&dp, c->sums_pin.p, 0));
-    a.sums = static_cast<double*>(dp);
-  }
+  a.sums = sums;
   a.status = c->misc.as<int32_t>() + kPdMiscRegionFlags;   // one flag per region
   a.n_chunks_cross = 1;
-  a.full_count = reinterpret_cast<const int32_t*>(dj + o_fc);
-  a.regions = reinterpret_cast<const PdRegion*>(dj + o_rg);
-  a.n_regions = K;
-  const int32_t* d_ho = reinterpret_cast<const int32_t*>(dj + o_ho);
+  a.full_count = reinterpret_cast<const int32_t*>(dj + L.fc);
+  a.regions = reinterpret_cast<const PdRegion*>(dj + L.rg);
+  a.n_regions = (int32_t)p.plans.size();
+  const int32_t* d_ho = reinterpret_cast<const int32_t*>(dj + L.ho);
 
-  hipLaunchKernelGGL(pdhmm_entries_kernel, dim3((unsigned)NH), dim3(kLanes), 0, s, a);   // one wavefront per haplotype item
+  hipLaunchKernelGGL(pdhmm_entries_kernel, dim3((unsigned)sh.NH), dim3(kLanes), 0, s, a);   // one wavefront per haplotype item
   HIP_TRY(hipEventRecord(c->ev0, s));
   const PdCrossLaunches l{{pdhmm_fwd_tab_kernel<true, true>, pdhmm_fwd_tab_kernel<false, true>},
                           {pdhmm_fwd_kernel<true, false, true, true>, pdhmm_fwd_kernel<false, false, true, true>},
                           {pdhmm_fwd_kernel<true, false, false, true>, pdhmm_fwd_kernel<false, false, false, true>},
-                          true, d_ho, n_tab_haps, n_hot_haps, n_tab_units, n_hot_units, n_full_units,
-                          0, (int)n_general};   // the listed jobs: the striped reads, all from the host's list
-  pd_launch_cross_jobs(c, l, a, n_blocks);
-  if (n_tail > 0) pd_launch_tail(c, pdhmm_fwd_kernel<false, true, false, true>, a, o, n_tail, n_blocks);   // every region's tail pairs
+                          true, d_ho, p.n_tab_haps, p.n_hot_haps, p.n_tab_units, p.n_hot_units, p.n_full_units,
+                          0, (int)p.n_general};   // the listed jobs: the striped reads, all from the host's list
+  pd_launch_cross_jobs(c, l, a, p.n_blocks);
+  if (p.n_tail > 0) pd_launch_tail(c, pdhmm_fwd_kernel<false, true, false, true>, a, L, p.n_tail, p.n_blocks);   // every region's tail pairs
   HIP_TRY(hipEventRecord(c->ev1, s));
   HIP_TRY(hipGetLastError());
-  double* sums = c->sums_pin.as<double>();
-  int32_t* status = reinterpret_cast<int32_t*>(sums + NP);
+  return GKLHIP_OK;
+}
+
+// ---- step 5: finish.  Behind the last launch (and behind ev1: the kernel time is the forward launches'), the device form
+// first: pdhmm_finalise_multi_kernel turns every good region's part of c->sums into its log10 values in HBM -- no host
+// log10.  Both forms: the status words with the regions' flags come back to `status`, the stream drains, the routing and
+// the flags are noted.  Host form: one finalisation over all pairs of the pinned sums.  A region with an input error
+// keeps its results untouched in either. ----
+int pd_multi_finish(gklhip_pdhmm_ctx* c, std::vector<PdMultiRegion>& R, const PdInputLayout& in, const PdMultiPlan& p, const PdMultiJobLayout& L,
+                    bool device, int32_t* status) {
+  const hipStream_t s = c->stream;
+  const int K = (int)R.size();
+  if (device) {
+    int32_t most = 1;   // pairs of the largest region
+    for (int k = 0; k < K; k++) most = std::max(most, p.regions[(size_t)k + 1].pair_base - p.regions[(size_t)k].pair_base);
+    const unsigned char* d = c->inputs.as<unsigned char>();
+    hipLaunchKernelGGL(pdhmm_finalise_multi_kernel, dim3((unsigned)std::min((most + kPdFinaliseBlock - 1) / kPdFinaliseBlock, 512), (unsigned)K),
+                       dim3(kPdFinaliseBlock), 0, s, c->sums.as<double>(), reinterpret_cast<const PdRegion*>(c->jobs.as<unsigned char>() + L.rg),
+                       c->misc.as<int32_t>() + kPdMiscRegionFlags, pd_tables().initial_condition_log10,
+                       reinterpret_cast<const PdRegionResults*>(d + PdGatherTable(in, K).o_results));
+    HIP_TRY(hipGetLastError());
+  }
   HIP_TRY(hipMemcpyAsync(status, c->misc.p, 4 * ((size_t)kPdMiscRegionFlags + (size_t)K), hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
   HIP_TRY(hipEventElapsedTime(&c->last_ms, c->ev0, c->ev1));
-  c->last_routing[0] = (int32_t)n_tab_haps; c->last_routing[1] = (int32_t)n_hot_haps; c->last_routing[2] = (int32_t)n_full_haps;
+  c->last_routing[0] = (int32_t)p.n_tab_haps; c->last_routing[1] = (int32_t)p.n_hot_haps; c->last_routing[2] = (int32_t)p.n_full_haps;
   for (int k = 0; k < K; k++) {
     PdMultiRegion& r = R[(size_t)k];
+    const PdCrossPlan& pl = p.plans[(size_t)k];
     r.flag = status[kPdMiscRegionFlags + k];
-    r.routing[0] = (int32_t)plans[(size_t)k].n_tab_haps; r.routing[1] = (int32_t)(plans[(size_t)k].n_clean_haps - plans[(size_t)k].n_tab_haps);
-    r.routing[2] = (int32_t)((size_t)r.q.n_hap_items - plans[(size_t)k].n_clean_haps);
+    r.routing[0] = (int32_t)pl.n_tab_haps; r.routing[1] = (int32_t)(pl.n_clean_haps - pl.n_tab_haps);
+    r.routing[2] = (int32_t)((size_t)r.q.n_hap_items - pl.n_clean_haps);
   }
-  // one finalisation over all pairs; a region with an input error keeps its output untouched
+  if (device) return GKLHIP_OK;
   double* out[kPdMaxRegions];
   for (int k = 0; k < K; k++) out[k] = R[(size_t)k].out;
-  return pd_finalise(c, sums, regions.data(), K, out, status + kPdMiscRegionFlags);
+  return pd_finalise(c, c->sums_pin.as<double>(), p.regions.data(), K, out, status + kPdMiscRegionFlags);
+}
+
+// The regions of R (all valid, same context settings; at most kPdMaxRegions, kPdMultiMaxPairs pairs, kPdStageBytes of
+// inputs) as ONE problem.  after == NULL: the host form; else the device form (R[k].q.in_hbm), ordered behind *after (a
+// NULL stream: HIP's default stream).  The device form stages its inputs before it plans: the planners read the haplotype
+// bytes that come back with them.  The return value is the status of the launch set (a HIP failure fails every region);
+// R[k].flag != 0: region k had a negative quality (PDHMM_INPUT_DATA_ERROR), its results are not written.
+int pd_run_multi_locked(gklhip_pdhmm_ctx* c, std::vector<PdMultiRegion>& R, const hipStream_t* after = nullptr) {
+  HIP_TRY(hipSetDevice(c->device));
+  const bool device = after != nullptr;
+  const PdMultiShape sh(R);
+  const PdInputLayout in = sh.layout();
+  std::vector<PdProblem> Q(R.size());
+  for (size_t k = 0; k < R.size(); k++) Q[k] = R[k].q;
+  PdMultiPlan plan;
+  int rc;
+  if (device && (rc = pd_multi_stage_inputs_device(c, R, in, *after, &Q))) return rc;
+  pd_multi_plan(c, Q, sh, &plan);
+  if (!device && (rc = pd_multi_stage_inputs_host(c, R, in, plan.regions.data()))) return rc;
+  if ((rc = pd_multi_reserve(c, sh, plan, device))) return rc;
+  const PdMultiJobLayout L(R.size(), sh.NH, plan);
+  if ((rc = pd_multi_stage_tables(c, plan, L))) return rc;
+  // the sums: the device form's stay in HBM for its finalise kernel; the host form's go straight into pinned memory,
+  // the status words behind them
+  double* sums = c->sums.as<double>();
+  int32_t* status = c->sums_pin.as<int32_t>();
+  if (!device) {
+    void* dp = nullptr;
+    HIP_TRY(hipHostGetDevicePointer(&dp, c->sums_pin.p, 0));
+    sums = static_cast<double*>(dp);
+    status = reinterpret_cast<int32_t*>(c->sums_pin.as<double>() + sh.NP);
+  }
+  if ((rc = pd_multi_launch(c, sh, in, plan, L, sums))) return rc;
+  return pd_multi_finish(c, R, in, plan, L, device, status);
 }
 
 // process-wide, per device (gklhip_pdhmm_combine_counts): region calls computed, region calls that shared a launch set
@@ -1728,11 +1859,13 @@ int gklhip_pdhmm_finalise_host(const double* sums, int64_t n, double* out) {
   return GKLHIP_OK;
 }
 
-int gklhip_pdhmm_compute_cross_multi(gklhip_pdhmm_ctx* c, int32_t n_regions, const gklhip_pdhmm_cross* regions, const int64_t* ref_batch_pairs,
-                                     double* const* out_host, int32_t* status_out) {
-  if (!c) return fail(GKLHIP_ERR_INVALID_ARG, "context is NULL (initNative not called)");
+namespace {
+// The two multi-region entry points.  after == NULL: the host form (out: host arrays, no sums_out); else the device form
+// (the regions' byte arrays, out[k] and sums_out[k] in HBM; never on a client context), behind *after.
+int pd_cross_multi(gklhip_pdhmm_ctx* c, int32_t n_regions, const gklhip_pdhmm_cross* regions, const int64_t* ref_batch_pairs,
+                   double* const* out, double* const* sums_out, int32_t* status_out, const hipStream_t* after) {
   if (n_regions <= 0) return fail(GKLHIP_ERR_INVALID_ARG, "no regions to process");
-  if (!regions || !out_host) return fail(GKLHIP_ERR_INVALID_ARG, "regions / out_host is NULL");
+  if (!regions || !out) return fail(GKLHIP_ERR_INVALID_ARG, "regions / out_host is NULL");
   int first_rc = GKLHIP_OK, first_k = n_regions;   // the failing region with the lowest index
   std::string first_err;
   auto note = [&](int k, int rc) {   // (g_err holds region k's message)
@@ -1746,8 +1879,10 @@ int gklhip_pdhmm_compute_cross_multi(gklhip_pdhmm_ctx* c, int32_t n_regions, con
     R.reserve((size_t)n_regions);
     for (int32_t k = 0; k < n_regions; k++) {
       PdMultiRegion r;
-      r.out = out_host[k];
+      r.out = out[k];
+      r.sums_out = after && sums_out ? sums_out[k] : nullptr;
       const int rc = pd_cross_problem(&regions[k], ref_batch_pairs ? ref_batch_pairs[k] : 0, r.out, &r.q);
+      r.q.in_hbm = after != nullptr;
       note(k, rc);
       if (rc == GKLHIP_OK) { R.push_back(r); index.push_back(k); }
     }
@@ -1762,7 +1897,7 @@ int gklhip_pdhmm_compute_cross_multi(gklhip_pdhmm_ctx* c, int32_t n_regions, con
       float ms = 0.f;
       for (size_t i = 0; i < R.size(); i++) {
         if (!c->remote) pd_count(c->device, 1, 0, 1);
-        note(index[i], pd_run(c, R[i].q, R[i].out));
+        note(index[i], after ? pd_run_device(c, R[i].q, R[i].out, R[i].sums_out, *after) : pd_run(c, R[i].q, R[i].out));
         std::lock_guard<std::mutex> lock(c->mu);
         ms += c->last_ms;
         for (int j = 0; j < 3; j++) routing[j] += c->last_routing[j];
@@ -1772,7 +1907,7 @@ int gklhip_pdhmm_compute_cross_multi(gklhip_pdhmm_ctx* c, int32_t n_regions, con
       for (int j = 0; j < 3; j++) c->last_routing[j] = routing[j];
     } else {
       std::lock_guard<std::mutex> lock(c->mu);
-      const int rc = pd_fenced(c, [&] { return pd_run_multi_locked(c, R); });
+      const int rc = pd_fenced(c, [&] { return pd_run_multi_locked(c, R, after); });
       pd_count(c->device, (int64_t)R.size(), R.size() > 1 ? (int64_t)R.size() : 0, 1);
       for (size_t i = 0; i < R.size(); i++) {
         if (rc != GKLHIP_OK) { note(index[i], rc); continue; }   // (g_err: the launch set's message)
@@ -1785,6 +1920,22 @@ int gklhip_pdhmm_compute_cross_multi(gklhip_pdhmm_ctx* c, int32_t n_regions, con
     return fail(GKLHIP_ERR_HIP, "unexpected C++ exception");
   }
   return first_rc == GKLHIP_OK ? GKLHIP_OK : fail(first_rc, "%s", first_err.c_str());
+}
+}  // namespace
+
+int gklhip_pdhmm_compute_cross_multi(gklhip_pdhmm_ctx* c, int32_t n_regions, const gklhip_pdhmm_cross* regions, const int64_t* ref_batch_pairs,
+                                     double* const* out_host, int32_t* status_out) {
+  if (!c) return fail(GKLHIP_ERR_INVALID_ARG, "context is NULL (initNative not called)");
+  return pd_cross_multi(c, n_regions, regions, ref_batch_pairs, out_host, nullptr, status_out, nullptr);
+}
+
+int gklhip_pdhmm_compute_cross_multi_device(gklhip_pdhmm_ctx* c, int32_t n_regions, const gklhip_pdhmm_cross* dev_regions,
+                                            const int64_t* ref_batch_pairs, double* const* out_dev, double* const* sums_dev,
+                                            int32_t* status_out, void* hip_stream) {
+  if (!c) return fail(GKLHIP_ERR_INVALID_ARG, "context is NULL (initNative not called)");
+  if (c->remote) return fail(GKLHIP_ERR_UNSUPPORTED, "gklhip_pdhmm_compute_cross_multi_device: %s", kPdDeviceRemoteText);
+  const hipStream_t after = static_cast<hipStream_t>(hip_stream);
+  return pd_cross_multi(c, n_regions, dev_regions, ref_batch_pairs, out_dev, sums_dev, status_out, &after);
 }
 
 int gklhip_pdhmm_combine_counts(int device, int64_t out[3], int reset) {

@@ -27,6 +27,7 @@
 
 #include "pairhmm_fwd_kernel.h"  // recv_above, read_lane, kLanes
 #include "pdhmm_multi_plan.h"   // PdRegion: the multi-region launches
+#include "pdhmm_gather_plan.h"  // PdGatherDesc, PdRegionResults: the device-resident multi-region call
 
 namespace gklhip {
 
@@ -1218,10 +1219,14 @@ __global__ __launch_bounds__(64) void pdhmm_idle_class_selftest_kernel(uint32_t*
   if (lds[threadIdx.x] == 0) atomicOr(out, 0x80000000u);   // (keeps the stores above alive)
 }
 
+// The finalisation of the device-resident calls, a thread per pair: the caller's log10 likelihood of a raw sum, with the
+// DEVICE's double log10 (the host calls use the host libm: the last bits may differ) and the host tables' constant.  Both
+// finalise kernels evaluate it HERE, so a region's values do not depend on which of them wrote them.
+__device__ __forceinline__ double pd_log10_likelihood(double sum, double log10_init) { return log10(sum) - log10_init; }
+
 // The last launch of a device-resident call (gklhip_pdhmm_compute_device / _cross_device): the raw sums of the call's n
-// pairs become the caller's log10 likelihoods in HBM, out[i] = log10(sum[i]) - log10(2^1020) with the DEVICE's double
-// log10 (the host calls use the host libm: the last bits may differ) and the host tables' constant; sums_out, when given,
-// receives the sums themselves, bit for bit what the host path finalises.  A thread per pair, grid-stride.  *status != 0
+// pairs become the caller's log10 likelihoods in HBM, out[i] = log10(sum[i]) - log10(2^1020); sums_out, when given,
+// receives the sums themselves, bit for bit what the host path finalises.  Grid-stride.  *status != 0
 // (a forward kernel met a negative quality: PDHMM_INPUT_DATA_ERROR): the call fails and nothing is written.
 constexpr int kPdFinaliseBlock = 256;
 __global__ __launch_bounds__(kPdFinaliseBlock) void pdhmm_finalise_kernel(const double* sums, const int32_t* status, int64_t n, double log10_init,
@@ -1230,8 +1235,49 @@ __global__ __launch_bounds__(kPdFinaliseBlock) void pdhmm_finalise_kernel(const 
   const int64_t stride = (int64_t)gridDim.x * kPdFinaliseBlock;
   for (int64_t i = (int64_t)blockIdx.x * kPdFinaliseBlock + threadIdx.x; i < n; i += stride) {
     const double s = sums[i];
-    out[i] = log10(s) - log10_init;
+    out[i] = pd_log10_likelihood(s, log10_init);
     if (sums_out) sums_out[i] = s;
+  }
+}
+
+// The same for the K regions of a device-resident multi-region call (gklhip_pdhmm_compute_cross_multi_device): blockIdx.y
+// is the region, whose pairs [pair_base, next pair_base) of `sums` go to ITS result arrays, results[k] (sums: may be NULL).
+// A region whose flag word is set (a negative quality) is left out: nothing of it is written.
+__global__ __launch_bounds__(kPdFinaliseBlock) void pdhmm_finalise_multi_kernel(const double* sums, const PdRegion* regions, const int32_t* flags,
+                                                                               double log10_init, const PdRegionResults* results) {
+  const int k = (int)blockIdx.y;
+  if (flags[k] != 0) return;
+  const int32_t base = regions[k].pair_base, n = regions[k + 1].pair_base - base;
+  double* const out = results[k].out;
+  double* const sums_out = results[k].sums;
+  const int32_t stride = (int32_t)gridDim.x * kPdFinaliseBlock;
+  for (int32_t i = (int32_t)blockIdx.x * kPdFinaliseBlock + (int32_t)threadIdx.x; i < n; i += stride) {
+    const double s = sums[base + i];
+    out[i] = pd_log10_likelihood(s, log10_init);
+    if (sums_out) sums_out[i] = s;
+  }
+}
+
+// The first launch of such a call: the regions' seven byte arrays, in HBM at their own row strides and at any alignment,
+// go to their places in the set's input block `dst` (pdhmm_gather_plan.h).  blockIdx.y is the descriptor; the threads of
+// its blocks grid-stride over the descriptor's 16-byte units, where its rows allow them, and over its remaining bytes.
+constexpr int kPdGatherBlock = 256;
+__global__ __launch_bounds__(kPdGatherBlock) void pdhmm_gather_regions_kernel(const PdGatherDesc* descs, unsigned char* dst) {
+  const PdGatherDesc d = descs[blockIdx.y];
+  const unsigned char* const src = static_cast<const unsigned char*>(d.src);
+  unsigned char* const to = dst + d.dst_off;
+  uint32_t n_vec, tail;
+  pd_gather_split(d, dst, &n_vec, &tail);
+  const uint32_t first = blockIdx.x * kPdGatherBlock + threadIdx.x, stride = gridDim.x * kPdGatherBlock;
+  for (uint32_t i = first; i < d.n_items * n_vec; i += stride) {
+    uint32_t sa, da;
+    pd_gather_unit_at(d, n_vec, i, &sa, &da);
+    *reinterpret_cast<uint4*>(to + da) = *reinterpret_cast<const uint4*>(src + sa);
+  }
+  for (uint32_t i = first; i < d.n_items * tail; i += stride) {
+    uint32_t sa, da;
+    pd_gather_tail_at(d, n_vec, tail, i, &sa, &da);
+    to[da] = src[sa];
   }
 }
 

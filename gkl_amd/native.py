@@ -581,6 +581,10 @@ def load_pdhmm_library(path: Optional[str] = None):
     if hasattr(lib, "gklhip_pdhmm_compute_cross_device"):
         lib.gklhip_pdhmm_compute_cross_device.argtypes = [C.c_void_p, C.POINTER(CPdhmmCross), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.gklhip_pdhmm_compute_cross_device.restype = C.c_int
+    if hasattr(lib, "gklhip_pdhmm_compute_cross_multi_device"):
+        lib.gklhip_pdhmm_compute_cross_multi_device.argtypes = [C.c_void_p, C.c_int32, C.POINTER(CPdhmmCross), C.POINTER(C.c_int64),
+                                                                C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_void_p]
+        lib.gklhip_pdhmm_compute_cross_multi_device.restype = C.c_int
     if hasattr(lib, "gklhip_pdhmm_finalise_host"):
         lib.gklhip_pdhmm_finalise_host.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
         lib.gklhip_pdhmm_finalise_host.restype = C.c_int
@@ -823,6 +827,10 @@ class PdhmmContext:
         st = self.lib.gklhip_pdhmm_compute_cross_multi(self.handle, n, crosses, rb, out_ptrs, status)
         if st == OK:
             return outs
+        self._raise_multi(st, n, status, outs)
+
+    def _raise_multi(self, st, n, status, outs):
+        """A multi-region call returned st != OK: the exception of the call itself, or PdhmmMultiError with the regions' own."""
         if n <= 0 or all(status[k] == OK for k in range(n)):
             self._raise(st)   # the call itself was refused
         # the library keeps the first failing region's message; the reference has one text per status for the others
@@ -877,6 +885,42 @@ class PdhmmContext:
         if st != OK:
             self._raise(st)
         return out
+
+    def compute_cross_multi_device(self, regions, ref_batch_pairs=None, outs=None, sums=None, stream=None):
+        """gklhip_pdhmm_compute_cross_multi_device: compute_cross_multi() with every region's two sides in HBM.  regions: a
+        list of (reads_db, haps_db) as PdhmmDeviceBatch.upload_cross returns them; ref_batch_pairs: None or one number per
+        region; outs: None, or one float64 tensor (or None: a new one) per region; sums: None, or a list whose entries are
+        float64 tensors or None.  Returns the list of output tensors, each byte for byte what compute_cross_device leaves
+        for its region alone.  Ordered behind `stream` and synchronous, as compute_cross_device.  When regions fail, the
+        others are still computed: PdhmmMultiError carries their tensors and every region's status and exception."""
+        import torch
+        n = len(regions)
+        crosses, out_list, sums_list, device = (CPdhmmCross * max(n, 1))(), [], [], None
+        if (outs is not None and len(outs) != n) or (sums is not None and len(sums) != n) or \
+                (ref_batch_pairs is not None and len(ref_batch_pairs) != n):
+            raise IllegalArgumentException(f"outs, sums and ref_batch_pairs must be None or hold one entry per region ({n})")
+        for k, (reads_db, haps_db) in enumerate(regions):
+            hp, rp = haps_db.hap_pointers(), reads_db.read_pointers()
+            if device is None:
+                device = reads_db.read_tensors[0].device
+            if haps_db.hap_tensors[0].device != device or reads_db.read_tensors[0].device != device:
+                raise IllegalArgumentException("the regions' reads and haplotypes are on different devices")
+            pairs = max(reads_db.batch * haps_db.batch, 0)
+            out_list.append(_pd_result_tensor(None if outs is None else outs[k], pairs, device, f"outs[{k}]"))
+            sums_list.append(None if sums is None or sums[k] is None else _pd_result_tensor(sums[k], pairs, device, f"sums[{k}]"))
+            crosses[k] = CPdhmmCross(reads_db.batch, haps_db.batch, haps_db.max_hap_len, reads_db.max_read_len, *hp, *rp,
+                                     haps_db.hap_lengths.ctypes.data, reads_db.read_lengths.ctypes.data)
+        if stream is None and device is not None:
+            stream = torch.cuda.current_stream(device)
+        out_ptrs = (C.c_void_p * max(n, 1))(*[o.data_ptr() for o in out_list])
+        sums_ptrs = None if sums is None else (C.c_void_p * max(n, 1))(*[None if s is None else s.data_ptr() for s in sums_list])
+        rb = None if ref_batch_pairs is None else (C.c_int64 * max(n, 1))(*[int(v) for v in ref_batch_pairs])
+        status = (C.c_int32 * max(n, 1))()
+        st = self.lib.gklhip_pdhmm_compute_cross_multi_device(self.handle, n, crosses, rb, out_ptrs, sums_ptrs, status,
+                                                              None if stream is None else stream.cuda_stream)
+        if st == OK:
+            return out_list
+        self._raise_multi(st, n, status, out_list)
 
     def last_kernel_ms(self) -> float:
         return float(self.lib.gklhip_pdhmm_last_kernel_ms(self.handle))

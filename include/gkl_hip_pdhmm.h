@@ -163,6 +163,38 @@ int gklhip_pdhmm_finalise_host(const double* sums, int64_t n, double* out);
  * shared launches (region by region: the sum of the calls' times). */
 int gklhip_pdhmm_compute_cross_multi(gklhip_pdhmm_ctx* ctx, int32_t n_regions, const gklhip_pdhmm_cross* regions,
                                      const int64_t* ref_batch_pairs, double* const* out_host, int32_t* status_out);
+/* The two combined: several region calls whose byte arrays already lie in HBM, in ONE set of launches, the results left in
+ * HBM region by region.  dev_regions: [n_regions], each as dev_batch of gklhip_pdhmm_compute_cross_device (the seven byte
+ * arrays in HBM on the context's device, at the region's own row strides and at any alignment; hap_lengths and read_lengths
+ * on the host).  ref_batch_pairs: [n_regions], NULL = all 0.  out_dev: [n_regions] HBM pointers, region k's n_reads * n_haps
+ * doubles.  sums_dev: NULL, or [n_regions] HBM pointers of which any may be NULL.  status_out: [n_regions] or NULL.  The
+ * pointer arrays themselves are host arrays.
+ * Ordering: SYNCHRONOUS, like gklhip_pdhmm_compute_cross_device: the work is ordered behind everything already enqueued
+ * on hip_stream (an event recorded there, which the context's stream waits for) and the call returns after the context's
+ * stream has drained.  It waits once early: one gather kernel copies all regions' arrays, device to device, to the common
+ * row strides of the set, and both haplotype arrays of all regions come back to pinned host memory in one copy for the
+ * planner.  There is no asynchronous variant.
+ * Results: region k's sums_dev[k] and out_dev[k] are byte for byte what gklhip_pdhmm_compute_cross_device(ctx,
+ * &dev_regions[k], ref_batch_pairs[k], ...) writes on the same context -- whichever regions ride along, in whatever order,
+ * in both fma modes and both tail modes (both calls evaluate out = log10(sum) - log10(2^1020) through one device
+ * function).  The sums are therefore the host calls' bits too, and gklhip_pdhmm_finalise_host of them gives GKL's values.
+ * Errors: as gklhip_pdhmm_compute_cross_multi, with the same statuses and texts.  The argument checks of the single call
+ * run per region before anything touches the device (a NULL out_dev[k] like a NULL out_host): a region that fails them
+ * is left out and the rest run.  A region with a negative ins / del / gcp quality gets GKLHIP_ERR_INVALID_ARG, its
+ * out_dev[k] / sums_dev[k] stay untouched and the other regions are not affected.  A HIP failure of the shared launches
+ * fails every region in them.  Return value and gklhip_pdhmm_last_error: the first failing region's.  On a client context:
+ * GKLHIP_ERR_UNSUPPORTED before anything else.
+ * Limits: those of a shared launch set (64 regions, 4 MB of inputs at the common row strides, 131 072 pairs); a call over
+ * any of them is computed region by region through gklhip_pdhmm_compute_cross_device's path, with the same results.
+ * Counters: unlike the single device-resident calls, which count nothing, this call counts in gklhip_pdhmm_combine_counts
+ * exactly as the host multi call does -- a shared set of n regions adds n calls, n shared calls when n > 1, and 1 set;
+ * region by region adds (1, 0, 1) per region -- because the counters are the only observable that shows that the regions
+ * shared their launches.  gklhip_pdhmm_last_routing holds the sums over the regions, gklhip_pdhmm_last_kernel_ms the
+ * forward launches of the set (not the gather, not the finalisation; region by region: the sum of the calls' times).  The
+ * call never enters the combiner. */
+int gklhip_pdhmm_compute_cross_multi_device(gklhip_pdhmm_ctx* ctx, int32_t n_regions, const gklhip_pdhmm_cross* dev_regions,
+                                            const int64_t* ref_batch_pairs, double* const* out_dev,
+                                            double* const* sums_dev /* may be NULL */, int32_t* status_out, void* hip_stream);
 /* Process-wide counters of the cross calls computed on `device` by contexts of this process (-1: summed over the devices;
  * client contexts compute nothing and count nothing): out[0] region calls computed, out[1] region calls that shared a
  * launch set with another (gklhip_pdhmm_compute_cross_multi with two or more regions in the set; concurrent calls joined

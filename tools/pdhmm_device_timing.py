@@ -8,7 +8,13 @@ calls, host to host (the device-resident call is synchronous), plus last_kernel_
 the same three problems (it has no device-resident calls), and the tool says whether this tree's p50 lies inside the
 parent's own p10-p90 band (the criterion of docs/NOTES.md 73).
 
-usage: tools/pdhmm_device_timing.py [--reps 30] [--warmup 5] [--parent-lib PATH] [--json OUT]"""
+--multi: the multi arm instead.  K = 1, 2, 4, 8, 16 copies of the 276 x 48 region, every copy with its own arrays in HBM, as
+(a) K single gklhip_pdhmm_compute_cross_device calls, (b) one host gklhip_pdhmm_compute_cross_multi call, (c) one
+gklhip_pdhmm_compute_cross_multi_device call: the same percentiles, the kernel times (a: summed over the K calls) and
+the ratios c / a and c / b of the p50s.  With --parent-lib: the parent's (a) and (b) in the same session, and whether this
+tree's p50 of each lies inside, below or above the parent's p10-p90 band.
+
+usage: tools/pdhmm_device_timing.py [--reps 30] [--warmup 5] [--parent-lib PATH] [--multi] [--json OUT]"""
 import argparse
 import json
 import os
@@ -53,18 +59,71 @@ def timed(call, kernel_ms, reps, warmup):
             "p90": round(float(np.percentile(ts, 90)), 4), "last_kernel_ms": round(kernel_ms(), 4)}
 
 
+MULTI_K = (1, 2, 4, 8, 16)
+
+
+def multi_rows(a, ctx, parent):
+    """The multi arm: K copies of the 276 x 48 region, each with its own arrays in HBM, as (a) K single device-resident
+    calls, (b) one host multi call, (c) one device-resident multi call; with a parent library, its (a) and (b) too."""
+    import torch
+    _, _, (reads, haps) = problems()[2]
+    n = reads.batch * haps.batch
+    for K in MULTI_K:
+        regions = [(reads, haps)] * K
+        dbs = [native.PdhmmDeviceBatch.upload_cross(reads, haps, DEV) for _ in range(K)]
+        outs = [torch.empty(n, dtype=torch.float64, device=DEV) for _ in range(K)]
+        torch.cuda.synchronize()
+        kernel_ms = [0.0]
+
+        def singles(c):
+            def call():
+                kernel_ms[0] = 0.0
+                for k in range(K):
+                    c.compute_cross_device(*dbs[k], out=outs[k])
+                    kernel_ms[0] += c.last_kernel_ms()
+            return call
+
+        row = {"problem": f"{K} x region {reads.batch} x {haps.batch}", "K": K}
+        if parent is not None:
+            row["parent_a_single_device_calls"] = timed(singles(parent), lambda: kernel_ms[0], a.reps, a.warmup)
+        row["a_single_device_calls"] = timed(singles(ctx), lambda: kernel_ms[0], a.reps, a.warmup)
+        want = [o.cpu().numpy().tobytes() for o in outs]
+        if parent is not None:
+            row["parent_b_host_multi"] = timed(lambda: parent.compute_cross_multi(regions), parent.last_kernel_ms, a.reps, a.warmup)
+        row["b_host_multi"] = timed(lambda: ctx.compute_cross_multi(regions), ctx.last_kernel_ms, a.reps, a.warmup)
+        for o in outs:
+            o.zero_()
+        row["c_multi_device"] = timed(lambda: ctx.compute_cross_multi_device(dbs, outs=outs), ctx.last_kernel_ms, a.reps, a.warmup)
+        row["c_bytes_equal_a"] = bool([o.cpu().numpy().tobytes() for o in outs] == want)
+        row["c_over_a_p50"] = round(row["c_multi_device"]["p50"] / row["a_single_device_calls"]["p50"], 4)
+        row["c_over_b_p50"] = round(row["c_multi_device"]["p50"] / row["b_host_multi"]["p50"], 4)
+        if parent is not None:
+            for arm in ("a_single_device_calls", "b_host_multi"):
+                p = row["parent_" + arm]
+                p50 = row[arm]["p50"]
+                row[arm + "_p50_vs_parent_band"] = "below" if p50 < p["p10"] else "above" if p50 > p["p90"] else "inside"
+        yield row
+        dbs = outs = None
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--parent-lib")
+    ap.add_argument("--multi", action="store_true", help="only the multi arm: K regions as single device calls, host multi, device multi")
     ap.add_argument("--json")
     a = ap.parse_args()
     import torch
     rows = []
     ctx = native.PdhmmContext(device=0, fma_mode=1)
     parent = native.PdhmmContext(device=0, fma_mode=1, lib_path=a.parent_lib) if a.parent_lib else None
-    for name, kind, payload in problems():
+    if a.multi:
+        for row in multi_rows(a, ctx, parent):
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+    for name, kind, payload in ([] if a.multi else problems()):
         row = {"problem": name}
         if kind == "paired":
             host = lambda c: (lambda: c.compute(payload))  # noqa: E731
