@@ -288,14 +288,17 @@ int gklhip_partition_reads(int32_t n_reads, const int64_t* read_off, int32_t n_p
   return GKLHIP_OK;
 }
 
-static int compute_device_impl(gklhip_ctx* c, const gklhip_batch* dev_batch, double* out_dev, void* hip_stream) {
-  if (!c) return fail(GKLHIP_ERR_INVALID_ARG, "context is NULL (initNative not called)");
-  if (c->remote) return fail(GKLHIP_ERR_UNSUPPORTED, "gklhip_compute_device: device-resident batches cannot go to the PairHMM server (client context)");
-  int rc = validate(dev_batch);
+// The argument checks of a device-resident batch (gklhip_compute_device; gklhip_compute_multi_device region by region).
+static int check_device_batch(const gklhip_batch* dev_batch, const double* out_dev) {
+  const int rc = validate(dev_batch);
   if (rc) return rc;
   if (!out_dev && (int64_t)dev_batch->n_reads * dev_batch->n_haps > 0)
     return fail(GKLHIP_ERR_INVALID_ARG, "output array is NULL");
-  std::lock_guard<std::mutex> lock(c->mu);
+  return GKLHIP_OK;
+}
+// One checked device-resident call on a context whose lock the caller holds.
+static int compute_device_locked(gklhip_ctx* c, const gklhip_batch* dev_batch, double* out_dev, void* hip_stream) {
+  int rc;
   HIP_TRY(hipSetDevice(c->dev[0]->device));
   int mode = c->cfg.finalize;
   if (mode != GKLHIP_FINALIZE_DEVICE_F64 && mode != GKLHIP_FINALIZE_DEVICE_REF32) mode = GKLHIP_FINALIZE_DEVICE_F64;
@@ -343,6 +346,14 @@ static int compute_device_impl(gklhip_ctx* c, const gklhip_batch* dev_batch, dou
     return rc;
   }
   return multi_compute_device(c, set, dev_batch, out_dev, mode, s);
+}
+static int compute_device_impl(gklhip_ctx* c, const gklhip_batch* dev_batch, double* out_dev, void* hip_stream) {
+  if (!c) return fail(GKLHIP_ERR_INVALID_ARG, "context is NULL (initNative not called)");
+  if (c->remote) return fail(GKLHIP_ERR_UNSUPPORTED, "gklhip_compute_device: device-resident batches cannot go to the PairHMM server (client context)");
+  const int rc = check_device_batch(dev_batch, out_dev);
+  if (rc) return rc;
+  std::lock_guard<std::mutex> lock(c->mu);
+  return compute_device_locked(c, dev_batch, out_dev, hip_stream);
 }
 
 // Fault injection (tests of the callers' error handling; nothing in the reference): "compute:N" or "compute:NxK" makes
@@ -478,6 +489,75 @@ static int compute_multi_impl(gklhip_ctx* c, int32_t n_regions, const gklhip_bat
       if (r.rc == GKLHIP_OK) c->multi_last[(size_t)r.index] = std::make_pair(r.lane, r.stats.n_pairs);
     c->after_multi = true;
   }
+  return first_rc == GKLHIP_OK ? GKLHIP_OK : fail(first_rc, "%s", first_err.c_str());
+}
+
+// The same for regions whose arrays and outputs lie in HBM (dev_compute_device_multi); synchronous.  See the header for
+// the contract.
+static int compute_multi_device_impl(gklhip_ctx* c, int32_t n_regions, const gklhip_batch* dev_regions, double* const* out_dev, int32_t* status_out,
+                                     void* hip_stream) {
+  if (c && c->remote) return fail(GKLHIP_ERR_UNSUPPORTED, "gklhip_compute_multi_device: device-resident regions cannot go to the PairHMM server (client context)");
+  if (!c) return fail(GKLHIP_ERR_INVALID_ARG, "context is NULL (initNative not called)");
+  if (n_regions <= 0) return fail(GKLHIP_ERR_INVALID_ARG, "no regions to process");
+  if (!dev_regions || !out_dev) return fail(GKLHIP_ERR_INVALID_ARG, "dev_regions / out_dev is NULL");
+  int first_rc = GKLHIP_OK, first_k = n_regions;   // the failing region with the lowest index
+  std::string first_err;
+  auto note = [&](int k, int rc) {   // (g_err holds region k's message)
+    if (status_out) status_out[k] = rc;
+    if (rc != GKLHIP_OK && k < first_k) { first_k = k; first_rc = rc; first_err = g_err; }
+  };
+  // the argument checks of gklhip_compute_device, region by region, before anything touches the device
+  std::vector<MultiRegion> R;
+  for (int32_t k = 0; k < n_regions; k++) {
+    const int rc = check_device_batch(&dev_regions[k], out_dev[k]);
+    note(k, rc);
+    if (rc != GKLHIP_OK || (int64_t)dev_regions[k].n_reads * dev_regions[k].n_haps == 0) continue;
+    MultiRegion r;
+    r.hb = &dev_regions[k]; r.out = out_dev[k]; r.index = k;
+    R.push_back(r);
+  }
+  std::lock_guard<std::mutex> lock(c->mu);
+  hipStream_t s = static_cast<hipStream_t>(hip_stream);  // NULL = HIP's default stream
+  gklhip_stats sum;
+  memset(&sum, 0, sizeof sum);
+  auto add_stats = [&](const gklhip_stats& st) {
+    sum.n_pairs += st.n_pairs; sum.cells += st.cells; sum.cells_fp64 += st.cells_fp64;
+    if (st.n_fallback < 0 || sum.n_fallback < 0) sum.n_fallback = -1; else sum.n_fallback += st.n_fallback;
+  };
+  // shared sets: one device, whose engine stages the regions that qualify on its lanes, every set behind what `s` holds
+  // now; several devices: every region through the single-call path
+  const bool sets = c->dev.size() == 1 && !R.empty();
+  if (sets) {
+    DevCtx* d = c->dev[0];
+    HIP_TRY(hipSetDevice(d->device));
+    if (!d->multi_in) HIP_TRY(hipEventCreateWithFlags(&d->multi_in, hipEventDisableTiming));
+    HIP_TRY(hipEventRecord(d->multi_in, s));
+    const int rc = dev_compute_device_multi(d, c->lanes, R, d->multi_in);
+    if (rc != GKLHIP_OK) return rc;
+  }
+  bool enqueued = false;
+  for (MultiRegion& r : R) {
+    if (!sets || r.alone) {
+      r.lane = -1;
+      r.rc = compute_device_locked(c, r.hb, r.out, hip_stream);
+      r.stats = c->stats;
+      enqueued = true;
+    } else {
+      g_err = r.err;
+    }
+    note(r.index, r.rc);
+    if (r.rc == GKLHIP_OK) add_stats(r.stats);
+  }
+  // synchronous: the region-by-region work has finished too when the call returns (the sets have: run_set waits)
+  if (enqueued) {
+    const hipError_t e = hipStreamSynchronize(s);
+    if (e != hipSuccess) { (void)hipGetLastError(); return fail(GKLHIP_ERR_HIP, "hipStreamSynchronize: %s (gklhip_compute_multi_device)", hipGetErrorString(e)); }
+  }
+  c->stats = sum;
+  c->multi_last.assign((size_t)n_regions, std::make_pair(-1, (int64_t)0));
+  for (const MultiRegion& r : R)
+    if (r.rc == GKLHIP_OK) c->multi_last[(size_t)r.index] = std::make_pair(r.lane, r.stats.n_pairs);
+  c->after_multi = true;
   return first_rc == GKLHIP_OK ? GKLHIP_OK : fail(first_rc, "%s", first_err.c_str());
 }
 
@@ -621,6 +701,7 @@ int gklhip_compute_device(gklhip_ctx* c, const gklhip_batch* dev_batch, double* 
 int gklhip_compute(gklhip_ctx* c, const gklhip_batch* hb, double* out_host) { return guarded([&] { return compute_impl(c, hb, out_host); }); }
 int gklhip_get_raw(gklhip_ctx* ctx, float* raw32, double* raw64, uint8_t* used64) { return guarded([&] { return get_raw_impl(ctx, raw32, raw64, used64); }); }
 int gklhip_compute_multi(gklhip_ctx* c, int32_t n_regions, const gklhip_batch* regions, double* const* out_host, int32_t* status_out) { return guarded([&] { return compute_multi_impl(c, n_regions, regions, out_host, status_out); }); }
+int gklhip_compute_multi_device(gklhip_ctx* c, int32_t n_regions, const gklhip_batch* dev_regions, double* const* out_dev, int32_t* status_out, void* hip_stream) { return guarded([&] { return compute_multi_device_impl(c, n_regions, dev_regions, out_dev, status_out, hip_stream); }); }
 int gklhip_get_raw_region(gklhip_ctx* ctx, int32_t region, float* raw32, double* raw64, uint8_t* used64) { return guarded([&] { return get_raw_region_impl(ctx, region, raw32, raw64, used64); }); }
 int gklhip_get_step_times(gklhip_ctx* ctx, int32_t steps_back, float* ms_main, float* ms_fallback, float* ms_total) { return guarded([&] { return get_step_times_impl(ctx, steps_back, ms_main, ms_fallback, ms_total); }); }
 int gklhip_rccl_selftest(int32_t device) { return guarded([&] { return rccl_selftest_impl(device); }); }

@@ -267,6 +267,54 @@ __global__ __launch_bounds__(kFlagBlock) void finalize64_multi_kernel(MultiArgs 
   reinterpret_cast<uint64_t*>(c->q.out)[p] = packed_word(c->d.raw[p]);
 }
 
+// The way out of a set for gklhip_compute_multi_device: behind the set's last launch, every region's packed words --
+// stored by the kernels above into the region's own output array in HBM, 8 bytes per pair -- become the doubles of the
+// device finalisation `mode` (1: GKLHIP_FINALIZE_DEVICE_F64, 2: GKLHIP_FINALIZE_DEVICE_REF32), in place.  A thread per
+// pair; region k owns multi_flag_blocks(n_pairs_k) blocks.  The same thread reads and writes the same 8 bytes, and nothing
+// else touches them after the set's last forward launch.  The three expressions are restated from pair_store_fp32 /
+// finalize32_kernel (an fp32-tagged word) and finalize64_kernel (any other word: the fp64 sum's bits); the constants are
+// the region's own (c->q).
+// Fallbacks: a wavefront adds the number of its fp64 words to the region's counter with one atomic (ballot + popcount),
+// then counts itself in; the wavefront that arrives last -- ceil(n_pairs / 64) arrive, the others of the region's last
+// block leave before -- stores the total to fallbacks[k], memory the host reads after it has waited for the set.  Counter
+// and arrivals are slots 14 and 15 of the region's counters, which prep_block clears and no other kernel uses.
+// Resources (gfx950, the compiler's resource-usage remarks): 22 VGPRs, 0 AGPRs, 26 SGPRs, no scratch, no LDS, 8 waves
+// per SIMD.
+constexpr int kFinalizeWordsSum = 14, kFinalizeWordsArrived = 15;
+__global__ __launch_bounds__(kFlagBlock) void finalize_words_multi_kernel(MultiArgs m, int mode, int32_t* fallbacks) {
+  const int r = multi_find(m, (int)blockIdx.x);
+  const SmallCall* c = m.call[r];
+  const int n_pairs = c->n_pairs;
+  const int p = multi_local(m.begin, r, (int)blockIdx.x) * kFlagBlock + (int)threadIdx.x;
+  if (p - (int)(threadIdx.x & 63) >= n_pairs) return;   // (the whole wavefront: it is not one of those that arrive)
+  bool fp64 = false;
+  if (p < n_pairs) {
+    uint64_t* out = global_ptr(reinterpret_cast<uint64_t*>(c->q.out));
+    const uint64_t w = out[p];
+    double res;
+    if ((w & kPackedF32Tag) == kPackedF32Tag) {
+      const float v = __uint_as_float((uint32_t)w);
+      if (mode == GKLHIP_FINALIZE_DEVICE_REF32) res = (double)((float)log10((double)v) - c->q.log10_init_f);
+      else                                      res = log10((double)v) - c->q.log10_init32_as_f64;
+    } else {
+      fp64 = true;
+      res = log10(__longlong_as_double((long long)w)) - c->q.log10_init_d;
+    }
+    reinterpret_cast<double*>(out)[p] = res;
+  }
+  const uint64_t flagged = __ballot(fp64);
+  if ((threadIdx.x & 63) == 0) {
+    int32_t* cnt = global_ptr(c->q.count);
+    if (flagged) atomicAdd(cnt + kFinalizeWordsSum, (int32_t)__popcll(flagged));
+    __threadfence();   // the sum before the arrival
+    const int32_t before = atomicAdd(cnt + kFinalizeWordsArrived, 1);
+    if (before == (n_pairs + 63) / 64 - 1) {
+      __threadfence();
+      fallbacks[r] = __hip_atomic_load(cnt + kFinalizeWordsSum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  }
+}
+
 constexpr int kModePacked = kModePackedWords;  // FinalizeArgs::mode: `out` receives packed raw sums (kPackedF32Tag, pairhmm_fwd_kernel.h)
 
 struct FinalizeArgs {

@@ -104,4 +104,8 @@ struct DevCtx {
   std::vector<PlanLane> long_lanes;
   std::vector<FwdJob> long_jobs;
   DevBuf carry;
+  // gklhip_compute_multi_device (an engine, not its lanes): the event that orders a set behind the caller's stream, and the
+  // fallback counts of a set's regions as finalize_words_multi_kernel leaves them (kMultiMax words of pinned memory)
+  hipEvent_t multi_in = nullptr;
+  PinBuf multi_fallbacks;
 };

@@ -37,6 +37,8 @@ void dev_done(DevCtx* c) {
   c->stage_slot[0].release();
   c->stage_slot[1].release();
   c->res_pin.release();
+  c->multi_fallbacks.release();
+  if (c->multi_in) (void)hipEventDestroy(c->multi_in);
   if (c->policy_done) (void)hipEventDestroy(c->policy_done);
   if (c->early_copy_done) (void)hipEventDestroy(c->early_copy_done);
   if (c->call_done) (void)hipEventDestroy(c->call_done);

@@ -60,7 +60,7 @@ struct PlanLayout {
       batch, batch_stride, stream, stream_flat, has_n, desc, total;
 };
 PlanLayout layout_for(const Plan& p, int n_reads, int n_haps, size_t n_long_lanes, size_t n_long_jobs, size_t inline_read_bytes,
-                      size_t inline_hap_bytes) {
+                      size_t inline_hap_bytes, bool resident_multi = false) {
   PlanLayout l;
   size_t o = 0;
   l.place_chunk = o; o = align_up(o + (size_t)n_reads * 4);
@@ -89,8 +89,9 @@ PlanLayout layout_for(const Plan& p, int n_reads, int n_haps, size_t n_long_lane
   l.stream = o; if (inline_read_bytes) o = align_up(o + (size_t)p.n_stream * 4);
   l.stream_flat = o; if (inline_read_bytes) o = align_up(o + (size_t)p.n_stream_flat * 4);
   l.has_n = o; if (inline_read_bytes) o = align_up(o + (size_t)n_haps);
-  // ... and the call's descriptor for the combined launches of several small calls (SmallCombiner)
-  l.desc = o; if (inline_read_bytes) o = align_up(o + sizeof(SmallCall));
+  // ... and the call's descriptor for the combined launches of several small calls (SmallCombiner); a region of the
+  // device-resident multi call (resident_multi) has one too, behind a block without inputs and host-built streams
+  l.desc = o; if (inline_read_bytes || resident_multi) o = align_up(o + sizeof(SmallCall));
   l.total = o;
   return l;
 }
@@ -353,6 +354,7 @@ struct CallPlan {
   size_t rl, hl;                 // read / haplotype bases
   int finalize_mode, fma, rpl_main, carry_len;
   bool inline_host, use_double;  // inline_host: the batch's byte arrays are HOST arrays that travel inside the plan block
+  bool resident_multi;           // the byte arrays lie in HBM, no larger than kSmallBatchBytes, and the caller is gklhip_compute_multi_device
   int n_long_main, n_long64;     // reads too long for a chunk of the main pass / of the packed fp64 pass
   PlanLayout L;
   bool pull;                     // the prep kernel pulls the block from pinned memory (plan_pulled)
@@ -369,27 +371,29 @@ struct CallPlan {
 // Which host-buffer calls are deferred -- planned and staged, then launched by the small-call combiner, alone or in one
 // set of launches with others (concurrent callers' calls, the regions of one gklhip_compute_multi).  What a host call
 // knows before it is planned (whether to offer deferral at all): inputs inline, not switched off (GKL_HIP_COMBINE=0) ...
-bool deferral_offered(bool inline_host) { return g_env.combine && inline_host; }
+// -- or, `resident_multi`, a region of gklhip_compute_multi_device: its arrays in HBM stand where "inputs inline" stands
+// (the same size limit; dev_compute_multi checks it).  No other caller passes it.
+bool deferral_offered(bool inline_host, bool resident_multi = false) { return g_env.combine && (inline_host || resident_multi); }
 // ... and of a planned call that was offered it (plan_call, nowhere else): plan block pulled, per-pair call, no long
 // read, host-exact packed finalisation, no event recording, at most kTwoStepFrom pairs.  A double-precision context's
 // call (kSmallDouble) under the same conditions: its per-pair kernel holds reads of up to 383 bases, or 511 with the
 // context's small_read_limit (pair_double), and its size limit has a name of its own (kSmallDoublePairs).
 bool small_call_defers(const DevCtx* c, const CallPlan& P) {
-  return deferral_offered(P.inline_host) && P.pull && c->cfg.record_events == 0 && (P.per_pair || P.pair_double) && c->plan.long_reads.empty() &&
+  return deferral_offered(P.inline_host, P.resident_multi) && P.pull && c->cfg.record_events == 0 && (P.per_pair || P.pair_double) && c->plan.long_reads.empty() &&
          P.finalize_mode == kModePacked && c->plan.n_chunks > 0 && P.n_pairs <= (P.pair_double ? kSmallDoublePairs : kTwoStepFrom);
 }
 // A mid-size region of a gklhip_compute_multi call shares a set with others of its kind (dev_compute_host_multi) when
 // everything above holds except the size: kTwoStepFrom < pairs <= kDirectPairs (per_pair says so), its policy in two
 // launches (not fused).  Asked of a plan that small_call_defers turned down; a SINGLE call asks through mid_call_combines only.
 bool mid_call_shares(const DevCtx* c, const CallPlan& P) {
-  return deferral_offered(P.inline_host) && P.pull && c->cfg.record_events == 0 && P.per_pair && !P.fused && c->plan.long_reads.empty() &&
+  return deferral_offered(P.inline_host, P.resident_multi) && P.pull && c->cfg.record_events == 0 && P.per_pair && !P.fused && c->plan.long_reads.empty() &&
          P.finalize_mode == kModePacked && c->plan.n_chunks > 0 && P.n_pairs > kTwoStepFrom && P.n_pairs <= kDirectPairs;
 }
 // ... and a mid-size region of a double-precision context (kSmallDoubleStream): the same of the all-fp64 pass.  No read
 // too long for a chunk of the packed fp64 pass (639 bases at kRplF64Jobs rows per lane: the limit is the chunk, not the
 // per-pair kernel's 383), a single-device context (a multi-device one keeps the general pass, as for kSmallDouble).
 bool double_mid_shares(const DevCtx* c, const CallPlan& P) {
-  return deferral_offered(P.inline_host) && P.pull && c->cfg.record_events == 0 && P.use_double && !c->multi_device && c->plan.long_reads.empty() &&
+  return deferral_offered(P.inline_host, P.resident_multi) && P.pull && c->cfg.record_events == 0 && P.use_double && !c->multi_device && c->plan.long_reads.empty() &&
          P.finalize_mode == kModePacked && c->plan.n_chunks > 0 && P.n_pairs > kTwoStepFrom && P.n_pairs <= kDirectPairs;
 }
 // A SINGLE call's mid-size region enters the combiner -- staged as a multi call stages one, launched in a set with the
@@ -403,9 +407,11 @@ bool mid_call_combines(const DevCtx* c, const CallPlan& P) {
 // where the context's small_read_limit says so AND the call is one the small-call path is offered at all -- a host call
 // with its inputs inline, combining not switched off, a single-device context without event recording.  Everything else
 // (device-resident calls, multi-device contexts, record_events, GKL_HIP_COMBINE=0) keeps the general pass for such reads.
+// The regions of gklhip_compute_multi_device (resident_multi) are offered the small-call path but not the fourth tier:
+// their limit is 383 bases whatever the context's small_read_limit says.
 static_assert(kRplPair8 == kRplF32 && kRplPair8 == kRplF64Wide, "the fourth tier: one wavefront at 8 rows per lane in both precisions");
-int small_read_len_max(const DevCtx* c, bool inline_host) {
-  const bool fourth_tier = c->small_read_limit == pair_tier_len_max(kRplPair8) && deferral_offered(inline_host) && !c->multi_device && c->cfg.record_events == 0;
+int small_read_len_max(const DevCtx* c, bool inline_host, bool resident_multi = false) {
+  const bool fourth_tier = !resident_multi && c->small_read_limit == pair_tier_len_max(kRplPair8) && deferral_offered(inline_host) && !c->multi_device && c->cfg.record_events == 0;
   return pair_tier_len_max(fourth_tier ? kRplPair8 : kRplF64);
 }
 // `load` of pick_f32_rpl: 1 for a call that is not offered deferral.  (About half of the calls inside the library are on
@@ -417,7 +423,7 @@ int call_load(bool deferral) {
 
 // Host only: no HIP call, no stream.  Fills c->plan, c->long_lanes, c->long_jobs and the statistics a plan decides.
 // `db` holds host offsets; the byte arrays are not read.
-void plan_call(DevCtx* c, const gklhip_batch* db, int finalize_mode, bool inline_host, bool deferral, int load, CallPlan* out) {
+void plan_call(DevCtx* c, const gklhip_batch* db, int finalize_mode, bool inline_host, bool deferral, int load, CallPlan* out, bool resident_multi = false) {
   CallPlan& P = *out;
   const int n_reads = P.n_reads = db->n_reads, n_haps = P.n_haps = db->n_haps;
   P.n_pairs = (int64_t)n_reads * n_haps;
@@ -429,6 +435,7 @@ void plan_call(DevCtx* c, const gklhip_batch* db, int finalize_mode, bool inline
   if (P.n_pairs == 0) return;
   P.finalize_mode = finalize_mode;
   P.inline_host = inline_host;
+  P.resident_multi = resident_multi;
   P.use_double = c->cfg.use_double != 0;
   P.fma = c->cfg.fma_mode != 0;
   P.t0 = std::chrono::steady_clock::now();
@@ -457,11 +464,11 @@ void plan_call(DevCtx* c, const gklhip_batch* db, int finalize_mode, bool inline
   }
   P.carry_len = (carry_len + 63) / 64 * 64;
   P.rl = (size_t)db->read_off[n_reads]; P.hl = (size_t)db->hap_off[n_haps];
-  P.L = layout_for(plan, n_reads, n_haps, long_lanes.size(), long_jobs.size(), inline_host ? P.rl : 0, inline_host ? P.hl : 0);
+  P.L = layout_for(plan, n_reads, n_haps, long_lanes.size(), long_jobs.size(), inline_host ? P.rl : 0, inline_host ? P.hl : 0, resident_multi);
   P.pull = plan_pulled(P.L.total);
   // policy + fp64 recomputation of one pair per wavefront (the kernel holds at most 64 x kRplF64 - 1 rows, or 64 x
   // kRplPair8 - 1 where the context's small_read_limit admits the fourth tier: small_read_len_max)
-  const int pair_len_max = small_read_len_max(c, inline_host);
+  const int pair_len_max = small_read_len_max(c, inline_host, resident_multi);
   P.per_pair = !P.use_double && P.n_pairs <= kDirectPairs && P.n_long64 == 0 && plan.max_read_len <= pair_len_max;
   // ... the tiny ones (one GATK active region) with the fp32 recurrence in the same wavefront and launch as the policy
   const int64_t fused_max = g_env.fused_max >= 0 ? g_env.fused_max : (int64_t)kTwoStepFrom;
@@ -651,7 +658,10 @@ PrepArgs prep_args(const DevCtx* c, const CallPlan& P, const StagedCall& S) {
   pa.hap_group = reinterpret_cast<const int32_t*>(pb + L.hap_group);
   pa.stream = S.stream_grouped;
   // the flat stream (no gaps between groups): the fp64 recomputation's jobs are arbitrary runs of it
-  pa.hap_pos_flat = P.use_double ? nullptr : reinterpret_cast<const int32_t*>(pb + L.hap_pos_flat);
+  // (a double-precision context's general pass has none; its per-pair kernel does, and a region of
+  //  gklhip_compute_multi_device that takes it has its streams built here, not on the host)
+  const bool flat = !P.use_double || (P.resident_multi && P.pair_double);
+  pa.hap_pos_flat = flat ? reinterpret_cast<const int32_t*>(pb + L.hap_pos_flat) : nullptr;
   pa.stream_flat = S.stream_flat;
   pa.hap_has_n = S.hap_has_n;
   pa.n_haps = P.inline_host ? 0 : P.n_haps;   // (host-built streams)

@@ -35,6 +35,13 @@ int finalize_threads(const DevCtx* c, int share) {
 // fwd_stream_multi_kernel, pair_policy_multi_kernel: a block finds its call through block offsets in the kernel
 // arguments).  A call that finds a free slot and nobody waiting goes out on its own stream exactly as before.
 constexpr int kFlightSlots = 4;
+// A set of gklhip_compute_multi_device, whose regions' arrays and outputs lie in HBM: what its launches wait for, and its
+// way out (finalize_words_multi_kernel behind the last launch).  NULL everywhere else.
+struct ResidentSet {
+  hipEvent_t after;     // recorded on the caller's stream: the set's stream waits for it before prep_multi_kernel
+  int mode;             // GKLHIP_FINALIZE_DEVICE_F64 or GKLHIP_FINALIZE_DEVICE_REF32
+  int32_t* fallbacks;   // [kMultiMax], as the device sees them: each region's number of fp64 words
+};
 struct SmallCombiner {
   struct Ticket {
     const SmallLaunch* sl = nullptr;
@@ -124,7 +131,7 @@ struct SmallCombiner {
   // One set of launches for calls[0 .. n) (every call of a set is of one kind: a leader only takes calls like its own, a
   // multi call cuts its sets by kind).  The kernel forms are the launchers' business (pairhmm_device_pass.h).  On stream `s`;
   // `done` (may be NULL) is recorded behind the last launch.
-  int launch_multi(const SmallLaunch* const* calls, int n, int fma, hipStream_t s, hipEvent_t done) {
+  int launch_multi(const SmallLaunch* const* calls, int n, int fma, hipStream_t s, hipEvent_t done, const ResidentSet* resident = nullptr) {
     // a launch's table: each call's descriptor (prep reads the pinned one) and where its `blocks` blocks begin
     auto set_of = [&](const SmallCall* SmallLaunch::*desc, int32_t SmallCall::*blocks) {
       MultiArgs m{};
@@ -138,6 +145,7 @@ struct SmallCombiner {
     int rows = kPairTiers[0];   // of the set's widest call
     for (int i = 0; i < n; i++) rows = std::max(rows, calls[i]->call.rows);
     const MultiArgs mp = set_of(&SmallLaunch::desc_pinned, &SmallCall::prep_grid);
+    if (resident) HIP_TRY(hipStreamWaitEvent(s, resident->after, 0));
     hipLaunchKernelGGL(prep_multi_kernel, set_grid(mp), dim3(kPrepBlock), 0, s, mp);
     int rc = GKLHIP_OK;
     switch (calls[0]->call.kind) {
@@ -163,6 +171,13 @@ struct SmallCombiner {
         rc = launch_pair_set(PairFamily::kPolicy, set_of(dev, &SmallCall::n_pairs), rows, fma, s);
     }
     if (rc) return rc;
+    if (resident) {   // the regions' packed words, in their own output arrays, become doubles there: a thread per pair
+      MultiArgs mf = set_of(dev, &SmallCall::n_pairs);
+      int32_t blocks[kMultiMax];
+      for (int i = 0; i < n; i++) blocks[i] = multi_flag_blocks(calls[i]->call.n_pairs);
+      multi_begin(blocks, n, mf.begin);
+      hipLaunchKernelGGL(finalize_words_multi_kernel, set_grid(mf), dim3(kFlagBlock), 0, s, mf, resident->mode, resident->fallbacks);
+    }
     HIP_TRY(hipGetLastError());
     if (done) HIP_TRY(hipEventRecord(done, s));
     return GKLHIP_OK;
@@ -176,7 +191,10 @@ struct SmallCombiner {
   // own stream like any lone call -- on the slot's stream it made the four flight streams at a lone caller's first call, which
   // a one-caller process should never hold (make_streams), and 100 x 10 callers that came later ran a quarter slower
   // (docs/NOTES.md 75).
-  int fly(std::unique_lock<std::mutex>& l, const SmallLaunch* const* calls, int n, hipStream_t own_stream, Ticket* const* others, int64_t t_lead) {
+  // A `resident` set (gklhip_compute_multi_device) of one region leaves through launch_multi as well: its way out is the
+  // set's.
+  int fly(std::unique_lock<std::mutex>& l, const SmallLaunch* const* calls, int n, hipStream_t own_stream, Ticket* const* others, int64_t t_lead,
+          const ResidentSet* resident = nullptr) {
     int si = 0;
     while (slot[si].busy) si++;
     Slot& sl = slot[si];
@@ -193,8 +211,8 @@ struct SmallCombiner {
     if (!own && !sl.stream) rc = fail(GKLHIP_ERR_HIP, "no stream for combined small calls");
     l.unlock();
     if (rc == GKLHIP_OK)
-      rc = !own ? launch_multi(calls, n, calls[0]->call.fma, sl.stream, sl.ev)
-           : mid ? launch_multi(calls, 1, calls[0]->call.fma, own_stream, nullptr) : launch_single(calls[0]->call, own_stream, alone);
+      rc = !own ? launch_multi(calls, n, calls[0]->call.fma, sl.stream, sl.ev, resident)
+           : mid || resident ? launch_multi(calls, 1, calls[0]->call.fma, own_stream, nullptr, resident) : launch_single(calls[0]->call, own_stream, alone);
     const std::string err = rc == GKLHIP_OK ? std::string() : g_err;
     const int64_t t_launched = now_ns();
     // a launch that failed part-way may have left kernels on the stream that still read the calls' staging blocks and
@@ -234,14 +252,14 @@ struct SmallCombiner {
   // mode), to completion: the set waits for a flight slot like any leader and leaves through the same launches, but it is
   // the caller's own from end to end -- it never enters the queue, so no other leader sees its regions, it takes nobody
   // else's tickets, and it never waits for company.  One region alone goes out on `own_stream` as a lone call does.
-  int run_set(const SmallLaunch* const* calls, int n, hipStream_t own_stream) {
+  int run_set(const SmallLaunch* const* calls, int n, hipStream_t own_stream, const ResidentSet* resident = nullptr) {
     const int64_t t_in = now_ns();
     std::unique_lock<std::mutex> l(mu);
     n_calls += n;
     cv.wait(l, [&] { return flights < max_flights; });
     const int64_t t_lead = now_ns();
     ns_queued += (t_lead - t_in) * n;
-    return fly(l, calls, n, own_stream, nullptr, t_lead);
+    return fly(l, calls, n, own_stream, nullptr, t_lead, resident);
   }
 
   // Runs one staged call to completion (its packed words are in the caller's pinned result buffer on return).
@@ -455,12 +473,28 @@ struct MultiRegion {
 // qualify (the cut needs that of the whole list), once more when the region's set is staged.
 // A failure is the region's own (`rc`, `err`), a failed set's the failure of every region in it; the return value is for
 // what stops the whole call before any region is touched.
-int dev_compute_host_multi(DevCtx* c, std::vector<DevCtx*>& lanes, std::vector<MultiRegion>& R) {
+//
+// gklhip_compute_multi_device is the same call with the regions' arrays and outputs in HBM (`resident`: the event on the
+// caller's stream that every set waits for).  It differs in three places: a region is planned as resident_multi (arrays in
+// HBM no larger than kSmallBatchBytes stand where "inputs inline" stands, and the context's device finalisation does not
+// turn it away); its packed words go into its own output array; and the set ends with finalize_words_multi_kernel, which
+// also leaves the region's fallback count -- no host log10, no res_pin.
+int dev_compute_multi(DevCtx* c, std::vector<DevCtx*>& lanes, std::vector<MultiRegion>& R, const hipEvent_t* resident) {
   HIP_TRY(hipSetDevice(c->device));
   const HostCallInFlight in_flight;
   const int threads = finalize_threads(c, in_flight.share);
   const bool on_device = finalizes_on_device(c->cfg.finalize);
   SmallCombiner* k = small_combiner(c->device);
+  ResidentSet rset{};
+  if (resident) {
+    int rc;
+    if ((rc = c->multi_fallbacks.reserve(kMultiMax * sizeof(int32_t)))) return rc;
+    void* p = nullptr;
+    HIP_TRY(hipHostGetDevicePointer(&p, c->multi_fallbacks.p, 0));
+    rset.after = *resident;
+    rset.mode = c->cfg.finalize == GKLHIP_FINALIZE_DEVICE_REF32 ? GKLHIP_FINALIZE_DEVICE_REF32 : GKLHIP_FINALIZE_DEVICE_F64;
+    rset.fallbacks = static_cast<int32_t*>(p);
+  }
   const int n = (int)R.size();
   const bool stage_first = n <= kMultiMax;
   std::vector<SmallLaunch> staged((size_t)kMultiMax);   // by lane
@@ -472,7 +506,8 @@ int dev_compute_host_multi(DevCtx* c, std::vector<DevCtx*>& lanes, std::vector<M
   auto plan = [&](int i, int li, CallPlan* plan_out, uint8_t* kind_out) -> int {
     MultiRegion& r = R[(size_t)i];
     const gklhip_batch* hb = r.hb;
-    if (on_device || !deferral_offered(inputs_inline(hb))) { r.alone = true; return kNone; }
+    // (inputs_inline: the size limit, of host arrays and of arrays in HBM alike)
+    if (resident ? !deferral_offered(false, inputs_inline(hb)) : (on_device || !deferral_offered(inputs_inline(hb)))) { r.alone = true; return kNone; }
     while ((int)lanes.size() <= li) {   // lanes are made on first use
       DevCtx* ln = nullptr;
       const int rc = lane_init(c, &ln);
@@ -481,7 +516,7 @@ int dev_compute_host_multi(DevCtx* c, std::vector<DevCtx*>& lanes, std::vector<M
     }
     DevCtx* ln = lanes[(size_t)li];
     CallPlan& P = *plan_out;
-    plan_call(ln, hb, kModePacked, true, true, call_load(true), &P);
+    plan_call(ln, hb, kModePacked, !resident, true, call_load(true), &P, resident != nullptr);
     const bool mid = !P.defers && (mid_call_shares(ln, P) || double_mid_shares(ln, P));
     if (!P.defers && !mid) { r.alone = true; return kNone; }
     P.defers = true;   // (a mid-size region too is staged for the combiner: see stage_call)
@@ -497,8 +532,9 @@ int dev_compute_host_multi(DevCtx* c, std::vector<DevCtx*>& lanes, std::vector<M
     void* pin_out = nullptr;
     if (owner[(size_t)li] >= 0) R[(size_t)owner[(size_t)li]].lane = -1;   // an earlier set's region: its raw sums go now
     owner[(size_t)li] = -1;
-    rc = ln->res_pin.reserve((size_t)hb->n_reads * (size_t)hb->n_haps * 8);
-    if (rc == GKLHIP_OK && hipHostGetDevicePointer(&pin_out, ln->res_pin.p, 0) != hipSuccess) { (void)hipGetLastError(); rc = fail(GKLHIP_ERR_HIP, "hipHostGetDevicePointer failed"); }
+    if (resident) pin_out = r.out;   // (the packed words go where the doubles will be)
+    else rc = ln->res_pin.reserve((size_t)hb->n_reads * (size_t)hb->n_haps * 8);
+    if (!resident && rc == GKLHIP_OK && hipHostGetDevicePointer(&pin_out, ln->res_pin.p, 0) != hipSuccess) { (void)hipGetLastError(); rc = fail(GKLHIP_ERR_HIP, "hipHostGetDevicePointer failed"); }
     if (rc != GKLHIP_OK) { fail_region(r, rc); return false; }
     StagedCall S;   // (the regions of a multi call are staged on lanes that have no stream of their own)
     if ((rc = stage_call(ln, hb, P, static_cast<double*>(pin_out), c->stream, &S))) { fail_region(r, rc); return false; }
@@ -572,18 +608,22 @@ int dev_compute_host_multi(DevCtx* c, std::vector<DevCtx*>& lanes, std::vector<M
       }
       if (m == 0) continue;
       if (pass == 1 && m == 1) { run_alone(members[0]); continue; }   // (its company failed to stage: one mid-size region is no set)
-      const int rc = k->run_set(calls, m, c->stream);
+      if (resident) std::fill_n(c->multi_fallbacks.as<int32_t>(), kMultiMax, -1);
+      const int rc = k->run_set(calls, m, c->stream, resident ? &rset : nullptr);
       for (int j = 0; j < m; j++) {
         MultiRegion& r = R[(size_t)members[j]];
         DevCtx* ln = lanes[(size_t)r.lane];
         if (rc != GKLHIP_OK) { fail_region(r, rc); owner[(size_t)r.lane] = -1; r.lane = -1; continue; }
         const HostFinalizer fin;
-        ln->stats.n_fallback = fin.all(&c->workers, ln->res_pin.as<uint64_t>(), r.out, ln->stats.n_pairs, threads, one_pass_min());
+        if (resident) ln->stats.n_fallback = c->multi_fallbacks.as<int32_t>()[j];
+        else ln->stats.n_fallback = fin.all(&c->workers, ln->res_pin.as<uint64_t>(), r.out, ln->stats.n_pairs, threads, one_pass_min());
         r.stats = ln->stats;
       }
     }
   }
   return GKLHIP_OK;
 }
+int dev_compute_host_multi(DevCtx* c, std::vector<DevCtx*>& lanes, std::vector<MultiRegion>& R) { return dev_compute_multi(c, lanes, R, nullptr); }
+int dev_compute_device_multi(DevCtx* c, std::vector<DevCtx*>& lanes, std::vector<MultiRegion>& R, hipEvent_t after) { return dev_compute_multi(c, lanes, R, &after); }
 
 }  // namespace

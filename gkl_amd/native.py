@@ -136,6 +136,9 @@ def load_library(path: Optional[str] = None):
     lib.gklhip_get_raw.restype = C.c_int
     lib.gklhip_compute_multi.argtypes = [C.c_void_p, C.c_int32, C.POINTER(CBatch), C.POINTER(C.c_void_p), C.POINTER(C.c_int32)]
     lib.gklhip_compute_multi.restype = C.c_int
+    if hasattr(lib, "gklhip_compute_multi_device"):   # (absent from an older build loaded by path for an A/B)
+        lib.gklhip_compute_multi_device.argtypes = [C.c_void_p, C.c_int32, C.POINTER(CBatch), C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_void_p]
+        lib.gklhip_compute_multi_device.restype = C.c_int
     lib.gklhip_get_raw_region.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.gklhip_get_raw_region.restype = C.c_int
     lib.gklhip_get_table_f32.argtypes = [C.c_int, C.c_void_p, C.c_int64]
@@ -452,6 +455,42 @@ class PairHmmContext:
         if st != OK:
             _raise(self.lib, st)
         return out
+
+    def compute_multi_device(self, dbatches, outs=None, stream=None) -> list:
+        """compute_multi for regions resident in HBM (gklhip_compute_multi_device; synchronous).  dbatches is a list of
+        DeviceBatch; returns the list of their torch float64 tensors, each byte for byte what compute_device() writes
+        for it alone.  outs, if given, is a list of float64 CUDA tensors of n_reads * n_haps elements on the context's
+        device (an entry may be None: the region then fails as one without an output array does); stream defaults to the
+        current torch stream.  When regions fail, the others are still computed: PairHmmMultiError carries their tensors
+        (None for a failed region) and every region's status and exception."""
+        import torch
+        n = len(dbatches)
+        if outs is None:
+            outs = [torch.empty(d.host.n_pairs, dtype=torch.float64, device=d.tensors[0].device) for d in dbatches]
+        outs = list(outs)
+        if len(outs) != n:
+            raise IllegalArgumentException("one output tensor per region")
+        for d, o in zip(dbatches, outs):
+            if o is not None and (o.dtype != torch.float64 or not o.is_cuda or o.numel() < d.host.n_pairs or not o.is_contiguous()):
+                raise IllegalArgumentException("likelihood tensor must be a contiguous float64 CUDA tensor of n_reads*n_haps")
+        if stream is None:
+            dev = next((o.device for o in outs if o is not None), None)
+            stream = torch.cuda.current_stream(dev)
+        cbs = (CBatch * max(n, 1))()
+        for k, d in enumerate(dbatches):
+            cbs[k] = d.c_batch()
+        out_ptrs = (C.c_void_p * max(n, 1))(*[None if o is None else o.data_ptr() for o in outs])
+        status = (C.c_int32 * max(n, 1))()
+        st = self.lib.gklhip_compute_multi_device(self.handle, n, cbs, out_ptrs, status, stream.cuda_stream)
+        if st == OK:
+            return outs
+        if n <= 0 or all(status[k] == OK for k in range(n)):
+            _raise(self.lib, st)   # the call itself was refused
+        msg = (self.lib.gklhip_last_error() or b"").decode()
+        first = next(k for k in range(n) if status[k] != OK)
+        errors = [None if status[k] == OK else _exception(self.lib, status[k], msg if k == first else f"region {k} failed with status {status[k]}")
+                  for k in range(n)]
+        raise PairHmmMultiError([o if status[k] == OK else None for k, o in enumerate(outs)], [int(status[k]) for k in range(n)], errors, st)
 
     def step_times(self, steps_back: int = 0):
         """record_events=2 contexts: (ms_main, ms_fallback, ms_total_device) of the call `steps_back` calls ago."""

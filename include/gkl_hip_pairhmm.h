@@ -207,6 +207,35 @@ void gklhip_host_free(void* p);
 int gklhip_compute_device(gklhip_ctx* ctx, const gklhip_batch* dev_batch, double* out_dev,
                           void* hip_stream);
 
+/* gklhip_compute_multi for regions that are resident in HBM: dev_regions[k] is exactly a `dev_batch` of
+ * gklhip_compute_device (offsets on the host, the six byte arrays in HBM on the context's device, at any alignment),
+ * `out_dev` a HOST array of n_regions HBM pointers -- region k gets n_reads * n_haps doubles --, status_out [n_regions]
+ * or NULL.  No byte of the regions' arrays is copied or read by the host.
+ * Results: out_dev[k] is, byte for byte, what gklhip_compute_device(ctx, &dev_regions[k], out_dev[k], ...) writes on the
+ * same context -- whichever regions ride along, in whatever order, in both fma modes, in both device finalisation modes
+ * (cfg.finalize 1 or 2; anything else means GKLHIP_FINALIZE_DEVICE_F64, as in the single call) and on use_double contexts.
+ * Which regions share a set: the rule of gklhip_compute_multi with "arrays in HBM" standing where "inputs inline" stands
+ * -- the six arrays of at most 1 MB; small regions (at most 2048 pairs) cut into sets by kind, mid-size regions (2049 to
+ * 65 536 pairs; reads of up to 639 bases on a use_double context) among themselves, one alone is no set; the same lanes,
+ * flight slots and caps.  The read-length limit of the small-call path is 383 bases in this call whatever
+ * gklhip_set_small_read_limit says: the 511-base tier is not offered here.  Every other region, every region of a
+ * multi-device context, of a process with GKL_HIP_COMBINE=0 and of a context with record_events != 0 runs through the path
+ * of gklhip_compute_device on `hip_stream`, in input order.
+ * Ordering: the call is SYNCHRONOUS, and there is no asynchronous variant.  Every set is ordered behind everything already
+ * enqueued on `hip_stream` (a set's own stream waits for an event recorded there), and the call returns after all its
+ * work has finished, the region-by-region work included.
+ * Errors: the argument checks of gklhip_compute_device run per region before anything touches the device (a NULL
+ * out_dev[k] is a NULL output array); a region that fails them is left out, its out_dev[k] stays untouched, and the rest
+ * run.  Return value and gklhip_last_error are the first failing region's.  A HIP failure of a shared set fails every
+ * region of that set after its stream has drained.  A client context returns GKLHIP_ERR_UNSUPPORTED before anything else.
+ * Afterwards: gklhip_small_call_counts counts as after gklhip_compute_multi (a set of n regions: n calls, n combined calls
+ * when n > 1, 1 set; a region that ran alone: nothing), gklhip_get_stats holds the sums over the regions of n_pairs,
+ * n_fallback (-1 when a region ran alone on a context that is not use_double: its count is not known without reading
+ * it back), cells and cells_fp64, gklhip_get_raw_region reads one region, gklhip_get_raw refuses, and
+ * gklhip_release_idle gives the lanes back. */
+int gklhip_compute_multi_device(gklhip_ctx* ctx, int32_t n_regions, const gklhip_batch* dev_regions, double* const* out_dev,
+                                int32_t* status_out, void* hip_stream);
+
 /* Introspection (tests, bench). */
 int gklhip_get_stats(gklhip_ctx* ctx, gklhip_stats* out);
 
@@ -307,7 +336,7 @@ int gklhip_fault_inject(const char* spec);
  * processes meet in one process's small-call combiner.  A client process makes no HIP call: batches travel through a
  * shared-memory arena (memfd) the server maps.  gklhip_init with GKL_HIP_SERVER=PATH in the environment is
  * gklhip_connect(PATH, cfg, out_ctx).  On a remote context gklhip_compute, gklhip_compute_multi (region by region), gklhip_get_stats, gklhip_release_idle (no-op)
- * and gklhip_done work; gklhip_compute_device, gklhip_get_raw, gklhip_get_raw_region, gklhip_get_step_times, gklhip_set_small_read_limit, gklhip_set_mid_combine and gklhip_measure_issue_ceiling
+ * and gklhip_done work; gklhip_compute_device, gklhip_compute_multi_device, gklhip_get_raw, gklhip_get_raw_region, gklhip_get_step_times, gklhip_set_small_read_limit, gklhip_set_mid_combine and gklhip_measure_issue_ceiling
  * return GKLHIP_ERR_UNSUPPORTED, and so does gklhip_fault_inject in a process with GKL_HIP_SERVER set.  A server that
  * has gone away fails the call with GKLHIP_ERR_HIP and a message that names the socket. */
 #define GKLHIP_SERVER_PROTOCOL 1
