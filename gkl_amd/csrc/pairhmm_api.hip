@@ -40,6 +40,7 @@
 #include "pairhmm_ctx.h"
 #include "pairhmm_device_pass.h"
 #include "pairhmm_ctx_lifecycle.h"
+#include "pairhmm_multi_call.h"
 #include "pairhmm_host_call.h"
 #include "pairhmm_multi_device.h"
 
@@ -288,8 +289,8 @@ int gklhip_partition_reads(int32_t n_reads, const int64_t* read_off, int32_t n_p
   return GKLHIP_OK;
 }
 
-// The argument checks of a device-resident batch (gklhip_compute_device; gklhip_compute_multi_device region by region).
-static int check_device_batch(const gklhip_batch* dev_batch, const double* out_dev) {
+// The argument checks of a batch that is not gklhip_compute's own (gklhip_compute_device; the multi calls region by region).
+static int check_batch(const gklhip_batch* dev_batch, const double* out_dev) {
   const int rc = validate(dev_batch);
   if (rc) return rc;
   if (!out_dev && (int64_t)dev_batch->n_reads * dev_batch->n_haps > 0)
@@ -318,9 +319,7 @@ static int compute_device_locked(gklhip_ctx* c, const gklhip_batch* dev_batch, d
       std::vector<DevCtx*> made;
       for (DevCtx* d : c->dev) {
         DevCtx* twin = nullptr;
-        if (dev_init(d->cfg, d->device, ndev, &twin) != GKLHIP_OK) break;   // e.g. out of memory: stay with one set
-        twin->small_read_limit = d->small_read_limit;
-        twin->mid_combine = d->mid_combine;
+        if (twin_init(d, ndev, &twin) != GKLHIP_OK) break;   // e.g. out of memory: stay with one set
         made.push_back(twin);
       }
       bool ok = made.size() == c->dev.size();
@@ -340,7 +339,7 @@ static int compute_device_locked(gklhip_ctx* c, const gklhip_batch* dev_batch, d
   if (devs.size() == 1 || (int64_t)dev_batch->n_reads * dev_batch->n_haps == 0) {
     c->bounds.assign(devs.size() + 1, dev_batch->n_reads);
     c->bounds[0] = 0;
-    rc = run_device(devs[0], dev_batch, out_dev, mode, s, false);
+    rc = run_device(devs[0], dev_batch, out_dev, mode, s, Arrays::kDevice);
     c->stats = devs[0]->stats;
     c->last = &devs;
     return rc;
@@ -350,7 +349,7 @@ static int compute_device_locked(gklhip_ctx* c, const gklhip_batch* dev_batch, d
 static int compute_device_impl(gklhip_ctx* c, const gklhip_batch* dev_batch, double* out_dev, void* hip_stream) {
   if (!c) return fail(GKLHIP_ERR_INVALID_ARG, "context is NULL (initNative not called)");
   if (c->remote) return fail(GKLHIP_ERR_UNSUPPORTED, "gklhip_compute_device: device-resident batches cannot go to the PairHMM server (client context)");
-  const int rc = check_device_batch(dev_batch, out_dev);
+  const int rc = check_batch(dev_batch, out_dev);
   if (rc) return rc;
   std::lock_guard<std::mutex> lock(c->mu);
   return compute_device_locked(c, dev_batch, out_dev, hip_stream);
@@ -399,9 +398,7 @@ static int compute_locked(gklhip_ctx* c, const gklhip_batch* hb, double* out_hos
       DevCtx* twin = nullptr;
       int ndev = 0;
       HIP_TRY(hipGetDeviceCount(&ndev));
-      if ((rc = dev_init(c->dev[0]->cfg, c->dev[0]->device, ndev, &twin))) { c->host_shards = (int)c->host_dev.size(); break; }  // e.g. out of memory: stay whole
-      twin->small_read_limit = c->dev[0]->small_read_limit;
-      twin->mid_combine = c->dev[0]->mid_combine;
+      if ((rc = twin_init(c->dev[0], ndev, &twin))) { c->host_shards = (int)c->host_dev.size(); break; }  // e.g. out of memory: stay whole
       c->twins.push_back(twin);
       c->host_dev.push_back(twin);
     }
@@ -433,54 +430,58 @@ static int compute_impl(gklhip_ctx* c, const gklhip_batch* hb, double* out_host)
   return compute_locked(c, hb, out_host);
 }
 
-// Several region calls, the ones the single call would defer in shared sets of launches (dev_compute_host_multi); see the
-// header for the contract.
-static int compute_multi_impl(gklhip_ctx* c, int32_t n_regions, const gklhip_batch* regions, double* const* out_host, int32_t* status_out) {
-  if (!c) return fail(GKLHIP_ERR_INVALID_ARG, "context is NULL (initNative not called)");
+// Several region calls, the ones that qualify in shared sets of launches (dev_compute_multi); see the header for the
+// contracts of gklhip_compute_multi and gklhip_compute_multi_device.  `single(r)`: one region through the single-call path.
+// `device_stream`: NULL for host regions; else the regions' arrays and outputs lie in HBM, the sets wait for what that
+// stream holds now, and the call is synchronous: the region-by-region work has finished too when it returns.
+static int compute_multi_common(gklhip_ctx* c, int32_t n_regions, const gklhip_batch* regions, double* const* out, int32_t* status_out, const char* what_is_null,
+                                const hipStream_t* device_stream, const std::function<int(const MultiRegion&)>& single) {
   if (n_regions <= 0) return fail(GKLHIP_ERR_INVALID_ARG, "no regions to process");
-  if (!regions || !out_host) return fail(GKLHIP_ERR_INVALID_ARG, "regions / out_host is NULL");
+  if (!regions || !out) return fail(GKLHIP_ERR_INVALID_ARG, "%s", what_is_null);
   int first_rc = GKLHIP_OK, first_k = n_regions;   // the failing region with the lowest index
   std::string first_err;
   auto note = [&](int k, int rc) {   // (g_err holds region k's message)
     if (status_out) status_out[k] = rc;
     if (rc != GKLHIP_OK && k < first_k) { first_k = k; first_rc = rc; first_err = g_err; }
   };
-  // the argument checks of gklhip_compute, region by region, before anything touches the device
+  // the argument checks of the single call, region by region, before anything touches the device
   std::vector<MultiRegion> R;
   for (int32_t k = 0; k < n_regions; k++) {
-    int rc = validate(&regions[k]);
-    const int64_t n_pairs = rc ? 0 : (int64_t)regions[k].n_reads * regions[k].n_haps;
-    if (rc == GKLHIP_OK && n_pairs > 0 && !out_host[k]) rc = fail(GKLHIP_ERR_INVALID_ARG, "output array is NULL");
+    const int rc = check_batch(&regions[k], out[k]);
     note(k, rc);
-    if (rc != GKLHIP_OK || n_pairs == 0) continue;
+    if (rc != GKLHIP_OK || (int64_t)regions[k].n_reads * regions[k].n_haps == 0) continue;
     MultiRegion r;
-    r.hb = &regions[k]; r.out = out_host[k]; r.index = k;
+    r.hb = &regions[k]; r.out = out[k]; r.index = k;
     R.push_back(r);
   }
   std::lock_guard<std::mutex> lock(c->mu);
   gklhip_stats sum;
   memset(&sum, 0, sizeof sum);
-  auto add_stats = [&](const gklhip_stats& s) {
-    sum.n_pairs += s.n_pairs; sum.cells += s.cells; sum.cells_fp64 += s.cells_fp64;
-    if (s.n_fallback < 0 || sum.n_fallback < 0) sum.n_fallback = -1; else sum.n_fallback += s.n_fallback;
-  };
   // shared sets: one device, whose engine stages the regions that qualify on its lanes; a client context, several
-  // devices: every region through the single-call path
-  const bool sets = !c->remote && c->dev.size() == 1;
+  // devices: every region through the single-call path (and a device call without a region left has no set to wait for)
+  const bool sets = !c->remote && c->dev.size() == 1 && !(device_stream && R.empty());
   if (sets) {
-    const int rc = dev_compute_host_multi(c->dev[0], c->lanes, R);
+    const int rc = dev_compute_multi(c->dev[0], c->lanes, R, device_stream);
     if (rc != GKLHIP_OK) return rc;
   }
+  bool enqueued = false;
   for (MultiRegion& r : R) {
     if (!sets || r.alone) {
       r.lane = -1;
-      r.rc = compute_locked(c, r.hb, r.out);
+      r.rc = single(r);
       r.stats = c->stats;
+      enqueued = true;
     } else {
       g_err = r.err;
     }
     note(r.index, r.rc);
-    if (r.rc == GKLHIP_OK) add_stats(r.stats);
+    if (r.rc != GKLHIP_OK) continue;
+    sum.n_pairs += r.stats.n_pairs; sum.cells += r.stats.cells; sum.cells_fp64 += r.stats.cells_fp64;
+    if (r.stats.n_fallback < 0 || sum.n_fallback < 0) sum.n_fallback = -1; else sum.n_fallback += r.stats.n_fallback;
+  }
+  if (device_stream && enqueued) {   // (the sets have finished: run_set waits)
+    const hipError_t e = hipStreamSynchronize(*device_stream);
+    if (e != hipSuccess) { (void)hipGetLastError(); return fail(GKLHIP_ERR_HIP, "hipStreamSynchronize: %s (gklhip_compute_multi_device)", hipGetErrorString(e)); }
   }
   c->stats = sum;
   if (!c->remote) {
@@ -491,74 +492,18 @@ static int compute_multi_impl(gklhip_ctx* c, int32_t n_regions, const gklhip_bat
   }
   return first_rc == GKLHIP_OK ? GKLHIP_OK : fail(first_rc, "%s", first_err.c_str());
 }
-
-// The same for regions whose arrays and outputs lie in HBM (dev_compute_device_multi); synchronous.  See the header for
-// the contract.
+static int compute_multi_impl(gklhip_ctx* c, int32_t n_regions, const gklhip_batch* regions, double* const* out_host, int32_t* status_out) {
+  if (!c) return fail(GKLHIP_ERR_INVALID_ARG, "context is NULL (initNative not called)");
+  return compute_multi_common(c, n_regions, regions, out_host, status_out, "regions / out_host is NULL", nullptr,
+                              [c](const MultiRegion& r) { return compute_locked(c, r.hb, r.out); });
+}
 static int compute_multi_device_impl(gklhip_ctx* c, int32_t n_regions, const gklhip_batch* dev_regions, double* const* out_dev, int32_t* status_out,
                                      void* hip_stream) {
   if (c && c->remote) return fail(GKLHIP_ERR_UNSUPPORTED, "gklhip_compute_multi_device: device-resident regions cannot go to the PairHMM server (client context)");
   if (!c) return fail(GKLHIP_ERR_INVALID_ARG, "context is NULL (initNative not called)");
-  if (n_regions <= 0) return fail(GKLHIP_ERR_INVALID_ARG, "no regions to process");
-  if (!dev_regions || !out_dev) return fail(GKLHIP_ERR_INVALID_ARG, "dev_regions / out_dev is NULL");
-  int first_rc = GKLHIP_OK, first_k = n_regions;   // the failing region with the lowest index
-  std::string first_err;
-  auto note = [&](int k, int rc) {   // (g_err holds region k's message)
-    if (status_out) status_out[k] = rc;
-    if (rc != GKLHIP_OK && k < first_k) { first_k = k; first_rc = rc; first_err = g_err; }
-  };
-  // the argument checks of gklhip_compute_device, region by region, before anything touches the device
-  std::vector<MultiRegion> R;
-  for (int32_t k = 0; k < n_regions; k++) {
-    const int rc = check_device_batch(&dev_regions[k], out_dev[k]);
-    note(k, rc);
-    if (rc != GKLHIP_OK || (int64_t)dev_regions[k].n_reads * dev_regions[k].n_haps == 0) continue;
-    MultiRegion r;
-    r.hb = &dev_regions[k]; r.out = out_dev[k]; r.index = k;
-    R.push_back(r);
-  }
-  std::lock_guard<std::mutex> lock(c->mu);
-  hipStream_t s = static_cast<hipStream_t>(hip_stream);  // NULL = HIP's default stream
-  gklhip_stats sum;
-  memset(&sum, 0, sizeof sum);
-  auto add_stats = [&](const gklhip_stats& st) {
-    sum.n_pairs += st.n_pairs; sum.cells += st.cells; sum.cells_fp64 += st.cells_fp64;
-    if (st.n_fallback < 0 || sum.n_fallback < 0) sum.n_fallback = -1; else sum.n_fallback += st.n_fallback;
-  };
-  // shared sets: one device, whose engine stages the regions that qualify on its lanes, every set behind what `s` holds
-  // now; several devices: every region through the single-call path
-  const bool sets = c->dev.size() == 1 && !R.empty();
-  if (sets) {
-    DevCtx* d = c->dev[0];
-    HIP_TRY(hipSetDevice(d->device));
-    if (!d->multi_in) HIP_TRY(hipEventCreateWithFlags(&d->multi_in, hipEventDisableTiming));
-    HIP_TRY(hipEventRecord(d->multi_in, s));
-    const int rc = dev_compute_device_multi(d, c->lanes, R, d->multi_in);
-    if (rc != GKLHIP_OK) return rc;
-  }
-  bool enqueued = false;
-  for (MultiRegion& r : R) {
-    if (!sets || r.alone) {
-      r.lane = -1;
-      r.rc = compute_device_locked(c, r.hb, r.out, hip_stream);
-      r.stats = c->stats;
-      enqueued = true;
-    } else {
-      g_err = r.err;
-    }
-    note(r.index, r.rc);
-    if (r.rc == GKLHIP_OK) add_stats(r.stats);
-  }
-  // synchronous: the region-by-region work has finished too when the call returns (the sets have: run_set waits)
-  if (enqueued) {
-    const hipError_t e = hipStreamSynchronize(s);
-    if (e != hipSuccess) { (void)hipGetLastError(); return fail(GKLHIP_ERR_HIP, "hipStreamSynchronize: %s (gklhip_compute_multi_device)", hipGetErrorString(e)); }
-  }
-  c->stats = sum;
-  c->multi_last.assign((size_t)n_regions, std::make_pair(-1, (int64_t)0));
-  for (const MultiRegion& r : R)
-    if (r.rc == GKLHIP_OK) c->multi_last[(size_t)r.index] = std::make_pair(r.lane, r.stats.n_pairs);
-  c->after_multi = true;
-  return first_rc == GKLHIP_OK ? GKLHIP_OK : fail(first_rc, "%s", first_err.c_str());
+  const hipStream_t s = static_cast<hipStream_t>(hip_stream);  // NULL = HIP's default stream
+  return compute_multi_common(c, n_regions, dev_regions, out_dev, status_out, "dev_regions / out_dev is NULL", &s,
+                              [c, hip_stream](const MultiRegion& r) { return compute_device_locked(c, r.hb, r.out, hip_stream); });
 }
 
 // A client process (GKL_HIP_SERVER set; decided once per process) makes no HIP call: its "page-locked" buffers are plain

@@ -180,6 +180,18 @@ int dev_init(const gklhip_config& cfg, int dev, int ndev, DevCtx** out) {
   return GKLHIP_OK;
 }
 
+// A second engine beside `parent` on its device (the twin engines of big host calls, the second engine set of two-stream
+// device-resident callers), and the context's switches that it and every staging lane follow.
+void inherit_switches(DevCtx* twin, const DevCtx* parent) {
+  twin->small_read_limit = parent->small_read_limit;
+  twin->mid_combine = parent->mid_combine;
+}
+int twin_init(const DevCtx* parent, int n_devices, DevCtx** out) {
+  const int rc = dev_init(parent->cfg, parent->device, n_devices, out);
+  if (rc == GKLHIP_OK) inherit_switches(*out, parent);
+  return rc;
+}
+
 // A staging lane of `parent` (gklhip_compute_multi: a set of n regions needs n staged calls alive at once).  A lane is a
 // DevCtx used for its per-call staging state only -- plan slots, pinned result words, raw sums and flags, the prep
 // kernel's outputs -- over the PARENT's device tables; it has no stream and no event ring of its own (every stream is a
@@ -198,8 +210,7 @@ int lane_init(DevCtx* parent, DevCtx** out) {
   c->n_xcds = parent->n_xcds;
   c->asm_general = parent->asm_general;
   c->speculate_fp64 = parent->speculate_fp64;
-  c->small_read_limit = parent->small_read_limit;
-  c->mid_combine = parent->mid_combine;
+  inherit_switches(c, parent);
   c->lds_oob_zero = parent->lds_oob_zero;
   c->dt32 = parent->dt32;   // (the parent's tab32 / tab64 own the memory)
   c->dt64 = parent->dt64;

@@ -59,9 +59,15 @@ struct PlanLayout {
   size_t place_chunk, place_lane, chunk_used, groups, hap_len, hap_pos, hap_pos_flat, hap_orig, hap_sidx, hap_group, hap_src, y0_32, y0_64, read_off, long_lanes, long_jobs, long_count,
       batch, batch_stride, stream, stream_flat, has_n, desc, total;
 };
-PlanLayout layout_for(const Plan& p, int n_reads, int n_haps, size_t n_long_lanes, size_t n_long_jobs, size_t inline_read_bytes,
-                      size_t inline_hap_bytes, bool resident_multi = false) {
+// Where a call's six byte arrays live -- what decides the block's layout and whether the small-call path is offered.
+enum class Arrays {
+  kHostInline,   // HOST arrays that travel inside the plan block (a host call no larger than kSmallBatchBytes)
+  kDevice,       // on the device: a device-resident call, or a host call whose arrays were copied there
+  kRegionInHbm,  // in HBM, no larger than kSmallBatchBytes, as a region of gklhip_compute_multi_device
+};
+PlanLayout layout_for(const Plan& p, int n_reads, int n_haps, size_t n_long_lanes, size_t n_long_jobs, size_t read_bytes, size_t hap_bytes, Arrays where) {
   PlanLayout l;
+  const size_t inline_read_bytes = where == Arrays::kHostInline ? read_bytes : 0, inline_hap_bytes = where == Arrays::kHostInline ? hap_bytes : 0;
   size_t o = 0;
   l.place_chunk = o; o = align_up(o + (size_t)n_reads * 4);
   l.place_lane = o; o = align_up(o + (size_t)n_reads);
@@ -90,8 +96,8 @@ PlanLayout layout_for(const Plan& p, int n_reads, int n_haps, size_t n_long_lane
   l.stream_flat = o; if (inline_read_bytes) o = align_up(o + (size_t)p.n_stream_flat * 4);
   l.has_n = o; if (inline_read_bytes) o = align_up(o + (size_t)n_haps);
   // ... and the call's descriptor for the combined launches of several small calls (SmallCombiner); a region of the
-  // device-resident multi call (resident_multi) has one too, behind a block without inputs and host-built streams
-  l.desc = o; if (inline_read_bytes || resident_multi) o = align_up(o + sizeof(SmallCall));
+  // device-resident multi call (kRegionInHbm) has one too, behind a block without inputs and host-built streams
+  l.desc = o; if (inline_read_bytes || where == Arrays::kRegionInHbm) o = align_up(o + sizeof(SmallCall));
   l.total = o;
   return l;
 }
@@ -353,8 +359,9 @@ struct CallPlan {
   int64_t n_pairs;               // 0: an empty call -- nothing else is set, and nothing is staged or launched
   size_t rl, hl;                 // read / haplotype bases
   int finalize_mode, fma, rpl_main, carry_len;
-  bool inline_host, use_double;  // inline_host: the batch's byte arrays are HOST arrays that travel inside the plan block
-  bool resident_multi;           // the byte arrays lie in HBM, no larger than kSmallBatchBytes, and the caller is gklhip_compute_multi_device
+  Arrays where;                  // where the batch's byte arrays live
+  bool inline_host() const { return where == Arrays::kHostInline; }
+  bool use_double;
   int n_long_main, n_long64;     // reads too long for a chunk of the main pass / of the packed fp64 pass
   PlanLayout L;
   bool pull;                     // the prep kernel pulls the block from pinned memory (plan_pulled)
@@ -371,31 +378,29 @@ struct CallPlan {
 // Which host-buffer calls are deferred -- planned and staged, then launched by the small-call combiner, alone or in one
 // set of launches with others (concurrent callers' calls, the regions of one gklhip_compute_multi).  What a host call
 // knows before it is planned (whether to offer deferral at all): inputs inline, not switched off (GKL_HIP_COMBINE=0) ...
-// -- or, `resident_multi`, a region of gklhip_compute_multi_device: its arrays in HBM stand where "inputs inline" stands
-// (the same size limit; dev_compute_multi checks it).  No other caller passes it.
-bool deferral_offered(bool inline_host, bool resident_multi = false) { return g_env.combine && (inline_host || resident_multi); }
-// ... and of a planned call that was offered it (plan_call, nowhere else): plan block pulled, per-pair call, no long
-// read, host-exact packed finalisation, no event recording, at most kTwoStepFrom pairs.  A double-precision context's
-// call (kSmallDouble) under the same conditions: its per-pair kernel holds reads of up to 383 bases, or 511 with the
-// context's small_read_limit (pair_double), and its size limit has a name of its own (kSmallDoublePairs).
+// -- or a region of gklhip_compute_multi_device: its arrays in HBM stand where "inputs inline" stands (the same size
+// limit: MultiCallOps::plan says kRegionInHbm only within it).
+bool deferral_offered(Arrays where) { return g_env.combine && where != Arrays::kDevice; }
+// ... and of a planned call that was offered it, what the three rules below have in common: plan block pulled, no event
+// recording, no long read, host-exact packed finalisation, something to compute.
+bool launches_shareable(const DevCtx* c, const CallPlan& P) {
+  return deferral_offered(P.where) && P.pull && c->cfg.record_events == 0 && c->plan.long_reads.empty() && P.finalize_mode == kModePacked && c->plan.n_chunks > 0;
+}
+bool mid_size(const CallPlan& P) { return P.n_pairs > kTwoStepFrom && P.n_pairs <= kDirectPairs; }
+// A small call (plan_call asks, nowhere else): a per-pair call of at most kTwoStepFrom pairs.  A double-precision
+// context's call (kSmallDouble) likewise: its per-pair kernel holds reads of up to 383 bases, or 511 with the context's
+// small_read_limit (pair_double), and its size limit has a name of its own (kSmallDoublePairs).
 bool small_call_defers(const DevCtx* c, const CallPlan& P) {
-  return deferral_offered(P.inline_host, P.resident_multi) && P.pull && c->cfg.record_events == 0 && (P.per_pair || P.pair_double) && c->plan.long_reads.empty() &&
-         P.finalize_mode == kModePacked && c->plan.n_chunks > 0 && P.n_pairs <= (P.pair_double ? kSmallDoublePairs : kTwoStepFrom);
+  return launches_shareable(c, P) && (P.per_pair || P.pair_double) && P.n_pairs <= (P.pair_double ? kSmallDoublePairs : kTwoStepFrom);
 }
-// A mid-size region of a gklhip_compute_multi call shares a set with others of its kind (dev_compute_host_multi) when
-// everything above holds except the size: kTwoStepFrom < pairs <= kDirectPairs (per_pair says so), its policy in two
-// launches (not fused).  Asked of a plan that small_call_defers turned down; a SINGLE call asks through mid_call_combines only.
-bool mid_call_shares(const DevCtx* c, const CallPlan& P) {
-  return deferral_offered(P.inline_host, P.resident_multi) && P.pull && c->cfg.record_events == 0 && P.per_pair && !P.fused && c->plan.long_reads.empty() &&
-         P.finalize_mode == kModePacked && c->plan.n_chunks > 0 && P.n_pairs > kTwoStepFrom && P.n_pairs <= kDirectPairs;
-}
+// A mid-size region of a gklhip_compute_multi call shares a set with others of its kind (multi_call_drive): its policy in
+// two launches (per-pair, not fused).  Asked of a plan that small_call_defers turned down; a SINGLE call asks through
+// mid_call_combines only.
+bool mid_call_shares(const DevCtx* c, const CallPlan& P) { return launches_shareable(c, P) && P.per_pair && !P.fused && mid_size(P); }
 // ... and a mid-size region of a double-precision context (kSmallDoubleStream): the same of the all-fp64 pass.  No read
 // too long for a chunk of the packed fp64 pass (639 bases at kRplF64Jobs rows per lane: the limit is the chunk, not the
 // per-pair kernel's 383), a single-device context (a multi-device one keeps the general pass, as for kSmallDouble).
-bool double_mid_shares(const DevCtx* c, const CallPlan& P) {
-  return deferral_offered(P.inline_host, P.resident_multi) && P.pull && c->cfg.record_events == 0 && P.use_double && !c->multi_device && c->plan.long_reads.empty() &&
-         P.finalize_mode == kModePacked && c->plan.n_chunks > 0 && P.n_pairs > kTwoStepFrom && P.n_pairs <= kDirectPairs;
-}
+bool double_mid_shares(const DevCtx* c, const CallPlan& P) { return launches_shareable(c, P) && P.use_double && !c->multi_device && mid_size(P); }
 // A SINGLE call's mid-size region enters the combiner -- staged as a multi call stages one, launched in a set with the
 // like regions of concurrent callers or as a set of one -- where the context's switch says so (gklhip_set_mid_combine /
 // GKL_HIP_COMBINE_MID; off by default) and one of the two rules above holds.  Asked by dev_compute_host_impl of a plan that
@@ -407,11 +412,11 @@ bool mid_call_combines(const DevCtx* c, const CallPlan& P) {
 // where the context's small_read_limit says so AND the call is one the small-call path is offered at all -- a host call
 // with its inputs inline, combining not switched off, a single-device context without event recording.  Everything else
 // (device-resident calls, multi-device contexts, record_events, GKL_HIP_COMBINE=0) keeps the general pass for such reads.
-// The regions of gklhip_compute_multi_device (resident_multi) are offered the small-call path but not the fourth tier:
+// The regions of gklhip_compute_multi_device (kRegionInHbm) are offered the small-call path but not the fourth tier:
 // their limit is 383 bases whatever the context's small_read_limit says.
 static_assert(kRplPair8 == kRplF32 && kRplPair8 == kRplF64Wide, "the fourth tier: one wavefront at 8 rows per lane in both precisions");
-int small_read_len_max(const DevCtx* c, bool inline_host, bool resident_multi = false) {
-  const bool fourth_tier = !resident_multi && c->small_read_limit == pair_tier_len_max(kRplPair8) && deferral_offered(inline_host) && !c->multi_device && c->cfg.record_events == 0;
+int small_read_len_max(const DevCtx* c, Arrays where) {
+  const bool fourth_tier = where == Arrays::kHostInline && c->small_read_limit == pair_tier_len_max(kRplPair8) && deferral_offered(where) && !c->multi_device && c->cfg.record_events == 0;
   return pair_tier_len_max(fourth_tier ? kRplPair8 : kRplF64);
 }
 // `load` of pick_f32_rpl: 1 for a call that is not offered deferral.  (About half of the calls inside the library are on
@@ -423,7 +428,7 @@ int call_load(bool deferral) {
 
 // Host only: no HIP call, no stream.  Fills c->plan, c->long_lanes, c->long_jobs and the statistics a plan decides.
 // `db` holds host offsets; the byte arrays are not read.
-void plan_call(DevCtx* c, const gklhip_batch* db, int finalize_mode, bool inline_host, bool deferral, int load, CallPlan* out, bool resident_multi = false) {
+void plan_call(DevCtx* c, const gklhip_batch* db, int finalize_mode, Arrays where, bool deferral, int load, CallPlan* out) {
   CallPlan& P = *out;
   const int n_reads = P.n_reads = db->n_reads, n_haps = P.n_haps = db->n_haps;
   P.n_pairs = (int64_t)n_reads * n_haps;
@@ -434,8 +439,7 @@ void plan_call(DevCtx* c, const gklhip_batch* db, int finalize_mode, bool inline
   c->have_last = false;
   if (P.n_pairs == 0) return;
   P.finalize_mode = finalize_mode;
-  P.inline_host = inline_host;
-  P.resident_multi = resident_multi;
+  P.where = where;
   P.use_double = c->cfg.use_double != 0;
   P.fma = c->cfg.fma_mode != 0;
   P.t0 = std::chrono::steady_clock::now();
@@ -464,11 +468,11 @@ void plan_call(DevCtx* c, const gklhip_batch* db, int finalize_mode, bool inline
   }
   P.carry_len = (carry_len + 63) / 64 * 64;
   P.rl = (size_t)db->read_off[n_reads]; P.hl = (size_t)db->hap_off[n_haps];
-  P.L = layout_for(plan, n_reads, n_haps, long_lanes.size(), long_jobs.size(), inline_host ? P.rl : 0, inline_host ? P.hl : 0, resident_multi);
+  P.L = layout_for(plan, n_reads, n_haps, long_lanes.size(), long_jobs.size(), P.rl, P.hl, where);
   P.pull = plan_pulled(P.L.total);
   // policy + fp64 recomputation of one pair per wavefront (the kernel holds at most 64 x kRplF64 - 1 rows, or 64 x
   // kRplPair8 - 1 where the context's small_read_limit admits the fourth tier: small_read_len_max)
-  const int pair_len_max = small_read_len_max(c, inline_host, resident_multi);
+  const int pair_len_max = small_read_len_max(c, where);
   P.per_pair = !P.use_double && P.n_pairs <= kDirectPairs && P.n_long64 == 0 && plan.max_read_len <= pair_len_max;
   // ... the tiny ones (one GATK active region) with the fp32 recurrence in the same wavefront and launch as the policy
   const int64_t fused_max = g_env.fused_max >= 0 ? g_env.fused_max : (int64_t)kTwoStepFrom;
@@ -561,7 +565,7 @@ void fill_plan_block(unsigned char* hs, const CallPlan& P, const Plan& plan, con
     int32_t lc[4] = {(int32_t)long_jobs.size(), P.n_long_main, P.n_long64, 0};
     memcpy(hs + L.long_count, lc, sizeof lc);
   }
-  if (P.inline_host) {
+  if (P.inline_host()) {
     unsigned char* dst = hs + L.batch;
     copy_six_arrays(*db, L.batch_stride, [dst](size_t at, const uint8_t* src, size_t n) { memcpy(dst + at, src, n); return 0; });
     build_host_streams(hs, L, plan, db->hap_bases, n_haps);
@@ -582,7 +586,7 @@ struct StagedCall {
   uint8_t *hap_has_n, *xcarry;  // xcarry: carry rows of the super-stripe kernel (reserve_carry)
 };
 
-// `db` holds host offsets and DEVICE byte arrays -- or, with P.inline_host, HOST byte arrays that travel inside the plan
+// `db` holds host offsets and DEVICE byte arrays -- or, with P.inline_host(), HOST byte arrays that travel inside the plan
 // block (small host-buffer calls: one copy for plan and inputs).  Flips c->plan_slot.
 int stage_call(DevCtx* c, const gklhip_batch* db, const CallPlan& P, double* out_dev, hipStream_t s, StagedCall* out) {
   const PlanLayout& L = P.L;
@@ -634,14 +638,14 @@ int stage_call(DevCtx* c, const gklhip_batch* db, const CallPlan& P, double* out
 
   S.s = s; S.out = out_dev; S.slot = slot; S.hs = hs; S.dp = dp; S.xcarry = nullptr;
   // the six byte arrays as the device reads them: inside the block, or where the caller put them
-  const gklhip_batch dbi = P.inline_host ? batch_at(*db, dp + L.batch, L.batch_stride) : *db;
+  const gklhip_batch dbi = P.inline_host() ? batch_at(*db, dp + L.batch, L.batch_stride) : *db;
   S.b = DevBatch{dbi.read_bases, dbi.read_quals, dbi.ins_gop, dbi.del_gop, dbi.gcp, reinterpret_cast<const int64_t*>(dp + L.read_off), P.n_reads, P.n_haps};
   // (pulling: the prep kernel reads the HOST copy of the block)
-  S.hap_bases = (P.pull && P.inline_host) ? batch_at(*db, S.hs_dev + L.batch, L.batch_stride).hap_bases : dbi.hap_bases;
+  S.hap_bases = (P.pull && P.inline_host()) ? batch_at(*db, S.hs_dev + L.batch, L.batch_stride).hap_bases : dbi.hap_bases;
   // (host-built streams arrive with the block; the prep kernel then only pulls and clears)
-  S.stream_grouped = P.inline_host ? reinterpret_cast<uint32_t*>(dp + L.stream) : c->stream_buf.as<uint32_t>();
-  S.stream_flat = P.inline_host ? reinterpret_cast<uint32_t*>(dp + L.stream_flat) : c->stream_buf.as<uint32_t>() + plan.n_stream;
-  S.hap_has_n = P.inline_host ? dp + L.has_n : c->hap_flags.as<uint8_t>();
+  S.stream_grouped = P.inline_host() ? reinterpret_cast<uint32_t*>(dp + L.stream) : c->stream_buf.as<uint32_t>();
+  S.stream_flat = P.inline_host() ? reinterpret_cast<uint32_t*>(dp + L.stream_flat) : c->stream_buf.as<uint32_t>() + plan.n_stream;
+  S.hap_has_n = P.inline_host() ? dp + L.has_n : c->hap_flags.as<uint8_t>();
   return GKLHIP_OK;
 }
 
@@ -660,11 +664,11 @@ PrepArgs prep_args(const DevCtx* c, const CallPlan& P, const StagedCall& S) {
   // the flat stream (no gaps between groups): the fp64 recomputation's jobs are arbitrary runs of it
   // (a double-precision context's general pass has none; its per-pair kernel does, and a region of
   //  gklhip_compute_multi_device that takes it has its streams built here, not on the host)
-  const bool flat = !P.use_double || (P.resident_multi && P.pair_double);
+  const bool flat = !P.use_double || (P.where == Arrays::kRegionInHbm && P.pair_double);
   pa.hap_pos_flat = flat ? reinterpret_cast<const int32_t*>(pb + L.hap_pos_flat) : nullptr;
   pa.stream_flat = S.stream_flat;
   pa.hap_has_n = S.hap_has_n;
-  pa.n_haps = P.inline_host ? 0 : P.n_haps;   // (host-built streams)
+  pa.n_haps = P.inline_host() ? 0 : P.n_haps;   // (host-built streams)
   pa.clear_a = c->counters.as<int32_t>(); pa.n_a = 32;
   pa.clear_b = c->read_fail.as<int32_t>(); pa.n_b = P.use_double ? 0 : P.n_reads;
   pa.clear_c = c->fail_hist.as<int32_t>(); pa.n_c = P.n_hist;
@@ -1027,9 +1031,9 @@ int launch_call(DevCtx* c, const gklhip_batch* db, const CallPlan& P, double* ou
 }
 // The whole pass of a call that is never deferred (device-resident and multi-device callers, host calls with device
 // finalisation) on stream `s`: `db` as for stage_call.
-int run_device(DevCtx* c, const gklhip_batch* db, double* out_dev, int finalize_mode, hipStream_t s, bool inline_host) {
+int run_device(DevCtx* c, const gklhip_batch* db, double* out_dev, int finalize_mode, hipStream_t s, Arrays where) {
   CallPlan P;
-  plan_call(c, db, finalize_mode, inline_host, false, call_load(false), &P);
+  plan_call(c, db, finalize_mode, where, false, call_load(false), &P);
   return launch_call(c, db, P, out_dev, s);
 }
 

@@ -1,5 +1,5 @@
 // The host-buffer call of one device (dev_compute_host: H2D, device pass, reference-exact host log10), the small-call combiner that launches
-// the GATK-sized calls of several threads together, and the multi-region call that hands it whole sets (dev_compute_host_multi).
+// the GATK-sized calls of several threads together, and the multi-region call that hands it whole sets (dev_compute_multi).
 // Part of the ONE translation unit gkl_amd/csrc/pairhmm_api.hip, which includes it in the order it needs; not a stand-alone header.
 #pragma once
 
@@ -346,9 +346,9 @@ int dev_compute_host_impl(DevCtx* c, const gklhip_batch* hb, double* out_host) {
   HIP_TRY(hipSetDevice(c->device));
   hipStream_t s = c->stream;
   int rc;
-  const bool inline_inputs = inputs_inline(hb);
+  const Arrays where = inputs_inline(hb) ? Arrays::kHostInline : Arrays::kDevice;
   gklhip_batch db = *hb;
-  if (!inline_inputs) {
+  if (where == Arrays::kDevice) {
     // H2D of the six byte arrays (one allocation, 256-byte aligned sub-buffers)
     if ((rc = c->batch_dev.reserve(six_arrays_bytes(hb)))) return rc;
     unsigned char* d = c->batch_dev.as<unsigned char>();
@@ -369,7 +369,7 @@ int dev_compute_host_impl(DevCtx* c, const gklhip_batch* hb, double* out_host) {
     pin_out = static_cast<double*>(p);
   }
   if (finalizes_on_device(mode)) {
-    if ((rc = run_device(c, &db, pin_out, mode, s, inline_inputs))) return rc;
+    if ((rc = run_device(c, &db, pin_out, mode, s, where))) return rc;
     HIP_TRY(hipStreamSynchronize(s));
     memcpy(out_host, c->res_pin.p, (size_t)n_pairs * 8);
     return GKLHIP_OK;
@@ -382,12 +382,12 @@ int dev_compute_host_impl(DevCtx* c, const gklhip_batch* hb, double* out_host) {
   const int threads = finalize_threads(c, in_flight.share);
   HostFinalizer fin;
   // (a context with an asynchronous device-resident call still in flight keeps the stream-ordered path)
-  const bool may_defer = deferral_offered(inline_inputs) && (!c->have_call_done || hipEventQuery(c->call_done) == hipSuccess);
+  const bool may_defer = deferral_offered(where) && (!c->have_call_done || hipEventQuery(c->call_done) == hipSuccess);
   (void)hipGetLastError();  // (hipErrorNotReady of the query)
   const int64_t t_call = SmallCombiner::now_ns();
   CallPlan P;
-  plan_call(c, &db, kModePacked, inline_inputs, may_defer, call_load(may_defer), &P);
-  // a mid-size region of a context with the mid-size switch on: staged as dev_compute_host_multi stages one, and into the
+  plan_call(c, &db, kModePacked, where, may_defer, call_load(may_defer), &P);
+  // a mid-size region of a context with the mid-size switch on: staged as a multi call stages one (MultiCallOps::stage), and into the
   // combiner with the like regions of whoever else is calling right now
   const bool mid = !P.defers && may_defer && mid_call_combines(c, P);
   if (mid) P.defers = true;
@@ -451,7 +451,7 @@ int dev_compute_host(DevCtx* c, const gklhip_batch* hb, double* out_host) {
   return rc;
 }
 
-// ---- several region calls in one set of launches (gklhip_compute_multi) ----
+// ---- several region calls in one set of launches (gklhip_compute_multi, gklhip_compute_multi_device) ----
 // A region of a multi call: checked by the caller (validate, at least one pair, an output array).
 struct MultiRegion {
   const gklhip_batch* hb = nullptr;
@@ -464,166 +464,97 @@ struct MultiRegion {
   gklhip_stats stats;
 };
 
-// The regions that the single-call path would defer are staged on the context's lanes -- plan_call, stage_call and
-// describe_small_call, exactly as a single call stages itself --, cut into sets (multi_cut_sets) and leave set by set through
-// the combiner's launches; each region's packed words are then finalised on the host as a single call's are.  Mid-size
-// regions (mid_call_shares; a double-precision context's: double_mid_shares) are staged the same way and cut among themselves (multi_cut_mid_sets): two or more of them
-// share sets of their own, one alone is no set.  Every other region comes back marked `alone`.
-// Up to kMultiMax regions are staged first and cut afterwards; a longer list is planned twice: once to learn which regions
-// qualify (the cut needs that of the whole list), once more when the region's set is staged.
-// A failure is the region's own (`rc`, `err`), a failed set's the failure of every region in it; the return value is for
-// what stops the whole call before any region is touched.
-//
-// gklhip_compute_multi_device is the same call with the regions' arrays and outputs in HBM (`resident`: the event on the
-// caller's stream that every set waits for).  It differs in three places: a region is planned as resident_multi (arrays in
-// HBM no larger than kSmallBatchBytes stand where "inputs inline" stands, and the context's device finalisation does not
-// turn it away); its packed words go into its own output array; and the set ends with finalize_words_multi_kernel, which
-// also leaves the region's fallback count -- no host log10, no res_pin.
-int dev_compute_multi(DevCtx* c, std::vector<DevCtx*>& lanes, std::vector<MultiRegion>& R, const hipEvent_t* resident) {
-  HIP_TRY(hipSetDevice(c->device));
-  const HostCallInFlight in_flight;
-  const int threads = finalize_threads(c, in_flight.share);
-  const bool on_device = finalizes_on_device(c->cfg.finalize);
-  SmallCombiner* k = small_combiner(c->device);
-  ResidentSet rset{};
-  if (resident) {
-    int rc;
-    if ((rc = c->multi_fallbacks.reserve(kMultiMax * sizeof(int32_t)))) return rc;
-    void* p = nullptr;
-    HIP_TRY(hipHostGetDevicePointer(&p, c->multi_fallbacks.p, 0));
-    rset.after = *resident;
-    rset.mode = c->cfg.finalize == GKLHIP_FINALIZE_DEVICE_REF32 ? GKLHIP_FINALIZE_DEVICE_REF32 : GKLHIP_FINALIZE_DEVICE_F64;
-    rset.fallbacks = static_cast<int32_t*>(p);
-  }
-  const int n = (int)R.size();
-  const bool stage_first = n <= kMultiMax;
-  std::vector<SmallLaunch> staged((size_t)kMultiMax);   // by lane
-  std::vector<int> owner((size_t)kMultiMax, -1);        // by lane: the region whose raw sums it holds
-  auto fail_region = [](MultiRegion& r, int rc) { r.rc = rc; r.err = g_err; };
-  enum { kNone, kSmall, kMid };
-  // Plans region i on lane `li`.  kNone: no set for this region (it does not qualify: r.alone; it failed: r.rc).
-  // *kind_out: the kind of a small region that qualifies (multi_cut_sets cuts by it).
-  auto plan = [&](int i, int li, CallPlan* plan_out, uint8_t* kind_out) -> int {
-    MultiRegion& r = R[(size_t)i];
-    const gklhip_batch* hb = r.hb;
+// The device side of multi_call_drive (pairhmm_multi_call.h, which decides everything): a region is planned, staged and
+// described on a lane of the context exactly as a single call stages itself (plan_call, stage_call, describe_small_call),
+// a set leaves through the combiner's launches (run_set), and each region's packed words are finalised on the host as a
+// single call's are.  The regions that qualify are the ones the single call would defer, and the mid-size ones
+// (mid_call_shares; a double-precision context's: double_mid_shares).
+// `resident` (gklhip_compute_multi_device: the regions' arrays and outputs lie in HBM) differs in three places: a region's
+// arrays are kRegionInHbm (within kSmallBatchBytes they stand where "inputs inline" stands, and the context's device
+// finalisation does not turn the region away); its packed words go into its own output array; and the set waits for the
+// caller's stream and ends with finalize_words_multi_kernel, which also leaves the region's fallback count -- no host
+// log10, no res_pin.
+struct MultiCallOps {
+  DevCtx* c;
+  std::vector<DevCtx*>& lanes;
+  std::vector<MultiRegion>& R;
+  const ResidentSet* resident;
+  int threads;                      // of the host finalisation
+  std::vector<SmallLaunch> staged;  // by lane
+  CallPlan last, held;
+  bool last_mid = false, held_mid = false;
+
+  MultiPlanned plan(int i, int li) {
+    const gklhip_batch* hb = R[(size_t)i].hb;
     // (inputs_inline: the size limit, of host arrays and of arrays in HBM alike)
-    if (resident ? !deferral_offered(false, inputs_inline(hb)) : (on_device || !deferral_offered(inputs_inline(hb)))) { r.alone = true; return kNone; }
+    const Arrays where = !inputs_inline(hb) ? Arrays::kDevice : resident ? Arrays::kRegionInHbm : Arrays::kHostInline;
+    if (!deferral_offered(where) || (!resident && finalizes_on_device(c->cfg.finalize))) return {GKLHIP_OK, kMultiNone, 0, false};
     while ((int)lanes.size() <= li) {   // lanes are made on first use
       DevCtx* ln = nullptr;
-      const int rc = lane_init(c, &ln);
-      if (rc != GKLHIP_OK) { fail_region(r, rc); return kNone; }
+      if (const int rc = lane_init(c, &ln)) return {rc, kMultiNone, 0, false};
       lanes.push_back(ln);
     }
     DevCtx* ln = lanes[(size_t)li];
-    CallPlan& P = *plan_out;
-    plan_call(ln, hb, kModePacked, !resident, true, call_load(true), &P, resident != nullptr);
-    const bool mid = !P.defers && (mid_call_shares(ln, P) || double_mid_shares(ln, P));
-    if (!P.defers && !mid) { r.alone = true; return kNone; }
-    P.defers = true;   // (a mid-size region too is staged for the combiner: see stage_call)
-    *kind_out = (uint8_t)small_call_kind(P);
-    return mid ? kMid : kSmall;
-  };
-  // ... and stages it there, from that plan (nothing else was planned on the lane in between).  false: it failed (r.rc).
-  auto put = [&](int i, int li, const CallPlan& P, bool mid) -> bool {
+    plan_call(ln, hb, kModePacked, where, true, call_load(true), &last);
+    last_mid = !last.defers && (mid_call_shares(ln, last) || double_mid_shares(ln, last));
+    if (!last.defers && !last_mid) return {GKLHIP_OK, kMultiNone, 0, false};
+    last.defers = true;   // (a mid-size region too is staged for the combiner: see stage_call)
+    return {GKLHIP_OK, last_mid ? kMultiMid : kMultiSmall, (uint8_t)small_call_kind(last), last.use_double};
+  }
+  void hold() { held = last; held_mid = last_mid; }
+  int stage(int i, int li, bool from_held) {
     MultiRegion& r = R[(size_t)i];
-    const gklhip_batch* hb = r.hb;
     DevCtx* ln = lanes[(size_t)li];
-    int rc = GKLHIP_OK;
-    void* pin_out = nullptr;
-    if (owner[(size_t)li] >= 0) R[(size_t)owner[(size_t)li]].lane = -1;   // an earlier set's region: its raw sums go now
-    owner[(size_t)li] = -1;
-    if (resident) pin_out = r.out;   // (the packed words go where the doubles will be)
-    else rc = ln->res_pin.reserve((size_t)hb->n_reads * (size_t)hb->n_haps * 8);
-    if (!resident && rc == GKLHIP_OK && hipHostGetDevicePointer(&pin_out, ln->res_pin.p, 0) != hipSuccess) { (void)hipGetLastError(); rc = fail(GKLHIP_ERR_HIP, "hipHostGetDevicePointer failed"); }
-    if (rc != GKLHIP_OK) { fail_region(r, rc); return false; }
+    const CallPlan& P = from_held ? held : last;
+    int rc;
+    void* pin_out = r.out;   // (resident: the packed words go where the doubles will be)
+    if (!resident) {
+      if ((rc = ln->res_pin.reserve((size_t)r.hb->n_reads * (size_t)r.hb->n_haps * 8))) return rc;
+      if (hipHostGetDevicePointer(&pin_out, ln->res_pin.p, 0) != hipSuccess) { (void)hipGetLastError(); return ::fail(GKLHIP_ERR_HIP, "hipHostGetDevicePointer failed"); }
+    }
     StagedCall S;   // (the regions of a multi call are staged on lanes that have no stream of their own)
-    if ((rc = stage_call(ln, hb, P, static_cast<double*>(pin_out), c->stream, &S))) { fail_region(r, rc); return false; }
-    if (mid && !P.use_double && (rc = ln->fail_order.reserve((size_t)P.n_pairs * 4))) { fail_region(r, rc); return false; }   // the list of its flagged pairs
+    if ((rc = stage_call(ln, r.hb, P, static_cast<double*>(pin_out), c->stream, &S))) return rc;
+    if ((from_held ? held_mid : last_mid) && !P.use_double && (rc = ln->fail_order.reserve((size_t)P.n_pairs * 4))) return rc;   // the list of its flagged pairs
     describe_small_call(ln, P, S, &staged[(size_t)li]);
-    owner[(size_t)li] = i; r.lane = li;
-    return true;
-  };
-  auto stage = [&](int i, int li, bool plan_only, uint8_t* kind_out) -> int {
-    CallPlan P;
-    const int what = plan(i, li, &P, kind_out);
-    if (what == kNone || plan_only) return what;
-    return put(i, li, P, what == kMid) ? what : kNone;
-  };
-  // A region that was staged and then finds no set: through the single-call path after all.
-  auto run_alone = [&](int i) {
+    return GKLHIP_OK;
+  }
+  int run(const int* members, int m) {
+    const SmallLaunch* calls[kMultiMax];
+    for (int j = 0; j < m; j++) calls[j] = &staged[(size_t)R[(size_t)members[j]].lane];
+    if (resident) std::fill_n(c->multi_fallbacks.as<int32_t>(), kMultiMax, -1);
+    return small_combiner(c->device)->run_set(calls, m, c->stream, resident);
+  }
+  void take(int i, int j) {
     MultiRegion& r = R[(size_t)i];
-    if (r.lane >= 0) owner[(size_t)r.lane] = -1;
-    r.lane = -1; r.alone = true;
-  };
-  std::vector<uint8_t> qualifies((size_t)n), mid((size_t)n), kind((size_t)n);
-  // A double-precision context's first mid-size region is held back, planned, until a second one shows up: one alone is no
-  // set, and a call with ONE such region costs what it did before these regions shared (its plan here, then the single-call
-  // path) -- staged and dropped it measured 0.01 - 0.03 ms more (400 x 40: 0.39 -> 0.41 ms).  Its lane keeps the plan.
-  int held = -1;
-  CallPlan held_plan;
-  bool any_mid = false;
-  for (int i = 0; i < n; i++) {
-    int what;
-    if (!stage_first) {
-      what = stage(i, 0, true, &kind[(size_t)i]);
-    } else {
-      CallPlan P;
-      what = plan(i, i, &P, &kind[(size_t)i]);
-      if (what == kMid && P.use_double && !any_mid) {
-        held = i; held_plan = P;
-      } else if (what != kNone) {
-        if (what == kMid && held >= 0) {
-          if (!put(held, held, held_plan, true)) mid[(size_t)held] = 0;
-          held = -1;
-        }
-        if (!put(i, i, P, what == kMid)) what = kNone;
-      }
-      any_mid = any_mid || what == kMid;
-    }
-    qualifies[(size_t)i] = what == kSmall ? 1 : 0;
-    mid[(size_t)i] = what == kMid ? 1 : 0;
+    DevCtx* ln = lanes[(size_t)r.lane];
+    if (resident) ln->stats.n_fallback = c->multi_fallbacks.as<int32_t>()[j];
+    else ln->stats.n_fallback = HostFinalizer().all(&c->workers, ln->res_pin.as<uint64_t>(), r.out, ln->stats.n_pairs, threads, one_pass_min());
+    r.stats = ln->stats;
   }
-  std::vector<int32_t> set_of((size_t)n), mid_set_of((size_t)n);
-  const int n_small_sets = multi_cut_sets(qualifies.data(), kind.data(), n, set_of.data());
-  const int n_mid_sets = multi_cut_mid_sets(mid.data(), n, mid_set_of.data());
-  for (int i = 0; i < n; i++)
-    if (mid[(size_t)i] && mid_set_of[(size_t)i] < 0) run_alone(i);
-  // the small regions' sets, then the mid-size regions' (a set is of one kind)
-  for (int pass = 0; pass < 2; pass++) {
-    const std::vector<int32_t>& of = pass == 0 ? set_of : mid_set_of;
-    const int n_sets = pass == 0 ? n_small_sets : n_mid_sets;
-    const int want = pass == 0 ? kSmall : kMid;
-    for (int s = 0, i = 0; s < n_sets; s++) {
-      const SmallLaunch* calls[kMultiMax];
-      int members[kMultiMax], m = 0;
-      for (; i < n && of[(size_t)i] <= s; i++) {
-        if (of[(size_t)i] != s) continue;
-        if (!stage_first) {
-          const int what = stage(i, m, false, &kind[(size_t)i]);
-          if (what == kNone) continue;                          // (planned under another load, it no longer qualifies: alone after all)
-          if (what != want) { run_alone(i); continue; }
-        }
-        calls[m] = &staged[(size_t)R[(size_t)i].lane];
-        members[m++] = i;
-      }
-      if (m == 0) continue;
-      if (pass == 1 && m == 1) { run_alone(members[0]); continue; }   // (its company failed to stage: one mid-size region is no set)
-      if (resident) std::fill_n(c->multi_fallbacks.as<int32_t>(), kMultiMax, -1);
-      const int rc = k->run_set(calls, m, c->stream, resident ? &rset : nullptr);
-      for (int j = 0; j < m; j++) {
-        MultiRegion& r = R[(size_t)members[j]];
-        DevCtx* ln = lanes[(size_t)r.lane];
-        if (rc != GKLHIP_OK) { fail_region(r, rc); owner[(size_t)r.lane] = -1; r.lane = -1; continue; }
-        const HostFinalizer fin;
-        if (resident) ln->stats.n_fallback = c->multi_fallbacks.as<int32_t>()[j];
-        else ln->stats.n_fallback = fin.all(&c->workers, ln->res_pin.as<uint64_t>(), r.out, ln->stats.n_pairs, threads, one_pass_min());
-        r.stats = ln->stats;
-      }
-    }
+  void fail(int i, int rc) { R[(size_t)i].rc = rc; R[(size_t)i].err = g_err; }
+};
+
+// The return value is for what stops the whole call before any region is touched; a failure later is a region's own (`rc`,
+// `err`).  `resident_stream`: NULL for host regions; else the caller's stream, which every set waits for (an event on it).
+int dev_compute_multi(DevCtx* c, std::vector<DevCtx*>& lanes, std::vector<MultiRegion>& R, const hipStream_t* resident_stream) {
+  HIP_TRY(hipSetDevice(c->device));
+  const HostCallInFlight in_flight;
+  ResidentSet rset{};
+  if (resident_stream) {
+    if (!c->multi_in) HIP_TRY(hipEventCreateWithFlags(&c->multi_in, hipEventDisableTiming));
+    HIP_TRY(hipEventRecord(c->multi_in, *resident_stream));
+    if (const int rc = c->multi_fallbacks.reserve(kMultiMax * sizeof(int32_t))) return rc;
+    void* p = nullptr;
+    HIP_TRY(hipHostGetDevicePointer(&p, c->multi_fallbacks.p, 0));
+    rset.after = c->multi_in;
+    rset.mode = c->cfg.finalize == GKLHIP_FINALIZE_DEVICE_REF32 ? GKLHIP_FINALIZE_DEVICE_REF32 : GKLHIP_FINALIZE_DEVICE_F64;
+    rset.fallbacks = static_cast<int32_t*>(p);
   }
+  MultiCallOps ops{c, lanes, R, resident_stream ? &rset : nullptr, finalize_threads(c, in_flight.share), std::vector<SmallLaunch>((size_t)kMultiMax), {}, {}};
+  int32_t owner[kMultiMax];   // by lane: the region whose raw sums it holds
+  std::fill_n(owner, kMultiMax, -1);
+  multi_call_drive(R.data(), (int)R.size(), owner, ops);
   return GKLHIP_OK;
 }
-int dev_compute_host_multi(DevCtx* c, std::vector<DevCtx*>& lanes, std::vector<MultiRegion>& R) { return dev_compute_multi(c, lanes, R, nullptr); }
-int dev_compute_device_multi(DevCtx* c, std::vector<DevCtx*>& lanes, std::vector<MultiRegion>& R, hipEvent_t after) { return dev_compute_multi(c, lanes, R, &after); }
 
 }  // namespace

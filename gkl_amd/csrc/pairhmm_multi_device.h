@@ -315,7 +315,7 @@ int multi_compute_device(gklhip_ctx* c, int set, const gklhip_batch* db, double*
   int rc = for_each_shard(c, n, [=](int d) -> int {
     DevCtx* dc = (*dp)[(size_t)d];
     const gklhip_batch v = shard_view(c, db, d);
-    if (d == 0) return run_device(dc, &v, out_dev, mode, s, false);
+    if (d == 0) return run_device(dc, &v, out_dev, mode, s, Arrays::kDevice);
     HIP_TRY(hipSetDevice(dc->device));
     hipStream_t sd = dc->stream;
     const size_t stride = align_up((size_t)v.read_off[v.n_reads]);
@@ -327,7 +327,7 @@ int multi_compute_device(gklhip_ctx* c, int set, const gklhip_batch* db, double*
     const int from = root->device, to = dc->device;
     if ((r = copy_six_arrays(v, stride, [=](size_t at, const uint8_t* src, size_t bytes) -> int { HIP_TRY(hipMemcpyPeerAsync(dst + at, to, src, from, bytes, sd)); return GKLHIP_OK; }))) return r;
     const gklhip_batch lv = batch_at(v, dst, stride);
-    if ((r = run_device(dc, &lv, dc->out_dev.as<double>(), mode, sd, false))) return r;
+    if ((r = run_device(dc, &lv, dc->out_dev.as<double>(), mode, sd, Arrays::kDevice))) return r;
     if (!use_rccl) {
       HIP_TRY(hipMemcpyPeerAsync(out_dev + (int64_t)c->bounds[(size_t)d] * n_haps, root->device, dc->out_dev.p, dc->device,
                                  (size_t)v.n_reads * n_haps * 8, sd));

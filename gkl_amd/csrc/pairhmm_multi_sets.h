@@ -6,8 +6,9 @@
 // local block (block - begin[k]) exactly as its single-call kernel would.  begin[] is a prefix sum of n + 1 values, so a
 // block finds its call by a binary search over it -- uniform over the wavefront, once per block.
 //
-// Plain C++ (tests/native/pairhmm_multi_sets_check.cpp and pairhmm_mid_combine_check.cpp compile it for the host alone,
-// under the sanitizers).
+// The rules only: what a multi call does with them -- lanes, order, failures -- is pairhmm_multi_call.h, which includes
+// this file.  Plain C++ (tests/native/pairhmm_multi_sets_check.cpp, pairhmm_multi_mid_check.cpp, pairhmm_mid_combine_check.cpp
+// and pairhmm_multi_call_check.cpp compile it for the host alone, under the sanitizers).
 #pragma once
 #include <stdint.h>
 
@@ -22,7 +23,7 @@ namespace gklhip {
 constexpr int kMultiMax = 64;     // calls per set of launches (what MultiArgs holds: a set of gklhip_compute_multi)
 constexpr int kCombineMax = 16;   // ... of which a leader of concurrent callers takes at most this many (SmallCombiner::run)
 
-// The set-cutting rule of gklhip_compute_multi.  The regions that qualify for a shared set (the single call would defer
+// The set-cutting rule of gklhip_compute_multi (multi_call_drive applies it).  The regions that qualify for a shared set (the single call would defer
 // them: small_call_defers) form runs in input order: a run ends where the next qualifying region is of another kind
 // (`kind`: any values -- the fused per-pair kernel, the one-launch policy, the all-fp64 per-pair kernel of a
 // double-precision context); regions that do not qualify run alone and do not interrupt a run.  A run of m regions

@@ -152,6 +152,51 @@ def test_unfused_kernels(pool, fma):
     pool.check(ctx, fma, names, got, singles)
 
 
+# A list longer than one set's lanes, so it is planned twice (once to classify, once when a region's set is staged), with every
+# class in it: 66 small regions (QUALIFYING in turn), three mid-size ones from tests/test_pairhmm_multi_mid.py's pool at 5, 30
+# and 60, and `long`, which does not qualify, at 17.  The counters, from the cutting rule (pairhmm_multi_sets.h):
+#   * a context has ONE kind of small fp32 region (fused with rows_per_lane 0, unfused with 4), so the 66 small ones are one
+#     run -- the mid-size regions and `long` do not interrupt it -- that multi_cut_sets cuts into ceil(66 / 64) = 2 sets of
+#     33 + 33: 66 calls, 66 combined, 2 sets of launches;
+#   * multi_cut_mid_sets puts the three mid-size regions into one set: 3 calls, 3 combined, 1 set;
+#   * `long` takes the single call's general pass, which counts nothing;
+# (calls, combined, sets) = (69, 69, 3), in both kinds of context.
+MIXED_MID = {5: "m2049", 30: "m2304", 60: "m_nofb"}
+
+
+def mixed_list_of_70():
+    names, k = [], 0
+    for at in range(70):
+        if at in MIXED_MID or at == 17:
+            names.append(MIXED_MID.get(at, "long"))
+        else:
+            names.append(QUALIFYING[k % len(QUALIFYING)])
+            k += 1
+    assert len(names) == 70 and k == 66
+    return names
+
+
+@pytest.mark.parametrize("rows_per_lane", [0, 4])
+def test_a_mixed_list_longer_than_a_set(pool, rows_per_lane):
+    from gkl_amd import native
+    from tests.test_pairhmm_multi_mid import build_pool as build_mid_pool
+    mid = build_mid_pool()
+    ctx = pool.context(1, rows_per_lane=rows_per_lane)
+    names = mixed_list_of_70()
+    batch = {n: mid[n] if n in mid else pool.batch[n] for n in set(names)}
+    singles = {n: ctx.compute(b) for n, b in batch.items()}
+    native.small_call_counts(0, reset=True)
+    got = ctx.compute_multi([batch[n] for n in names])
+    counts = native.small_call_counts(0)
+    print("rows_per_lane", rows_per_lane, "counts", counts)
+    assert counts == (69, 69, 3)
+    assert ctx.stats()["n_pairs"] == sum(batch[n].n_pairs for n in names)
+    for k, (n, out) in enumerate(zip(names, got)):
+        assert out.tobytes() == singles[n].tobytes(), (k, n, "single call")
+        if n not in mid:
+            assert np.array_equal(bits(out), bits(pool.want[1][n][0])), (k, n, "oracle")
+
+
 def test_regions_that_do_not_qualify_run_alone_inside_the_call(pool):
     from gkl_amd import native
     ctx = pool.context(1)

@@ -18,7 +18,7 @@ from tests.test_gpu_parity import REL_TOL
 from tests.test_pairhmm_double_mid import build_pool as build_double_mid_pool
 from tests.test_pairhmm_double_small import QUALIFYING as DOUBLE_QUALIFYING
 from tests.test_pairhmm_double_small import build_pool as build_double_pool
-from tests.test_pairhmm_multi import QUALIFYING, bits, build_pool
+from tests.test_pairhmm_multi import QUALIFYING, bits, build_pool, mixed_list_of_70
 from tests.test_pairhmm_multi_mid import QUALIFYING as MID_QUALIFYING
 from tests.test_pairhmm_multi_mid import build_pool as build_mid_pool
 
@@ -225,6 +225,19 @@ def test_double_precision_contexts(pool, fma):
         assert u.all(), n
         assert np.array_equal(bits(r64), bits(want[2])), n
         assert np.array_equal(bits(outs[k].cpu().numpy()), bits(np.frombuffer(pool.single(ctx, n), np.float64)))
+
+
+@pytest.mark.parametrize("rows_per_lane", [0, 4])
+def test_a_mixed_list_longer_than_a_set(pool, rows_per_lane):
+    """tests/test_pairhmm_multi.py's list of 70 regions -- planned twice, 66 small regions in two sets of 33, three mid-size
+    ones in a set of their own, `long` alone: (69, 69, 3) as derived there -- with the regions in HBM."""
+    ctx = pool.context(fma_mode=1, rows_per_lane=rows_per_lane)
+    names = mixed_list_of_70()
+    outs, counts = pool.run(ctx, names)
+    print("rows_per_lane", rows_per_lane, "counts", counts)
+    assert counts == (69, 69, 3)
+    assert ctx.stats()["n_pairs"] == sum(pool.batch[n].n_pairs for n in names)
+    pool.check(ctx, names, outs)
 
 
 def test_regions_that_do_not_qualify_run_alone_inside_the_call(pool):
