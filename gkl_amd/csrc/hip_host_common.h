@@ -1,5 +1,5 @@
-// What the host side of every HIP translation unit here shares (pairhmm_api.hip through pairhmm_ctx.h, pdhmm_api.hip,
-// sw_api.hip): the error plumbing behind each library's *_last_error and the grow-and-trim device / pinned buffers of a
+// What the host side of every HIP translation unit here shares (pairhmm_api.hip through pairhmm_ctx.h, pdhmm_api.hip
+// ahead of pdhmm_ctx.h and the launch paths it includes, sw_api.hip): the error plumbing behind each library's *_last_error and the grow-and-trim device / pinned buffers of a
 // context.  Everything sits in an anonymous namespace: each library keeps its own thread_local message.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -11,6 +11,18 @@
 
 namespace gklhip {
 
+// What the kernels (pdhmm_kernel.h includes this header) and the host's planner (pdhmm_call_plan.h) both read: one
+// definition, so a -DGKL_PD_RPL=... variant build reaches both.
+// PD flag bits of hap_pdbases (reference MathUtils.h:66-75)
+constexpr int kPdSnp = 1, kPdDelStart = 2, kPdDelEnd = 4, kPdA = 8, kPdC = 16, kPdG = 32, kPdT = 64;
+// The most column classes of a table haplotype (pdhmm_kernel.h: "Table entries").
+constexpr int kPdTabClasses = 6;
+// Rows per lane (pdhmm_kernel.h: "Rows per lane" has the measurements behind the 6).
+#ifndef GKL_PD_RPL
+#define GKL_PD_RPL 6
+#endif
+constexpr int kPdRpl = GKL_PD_RPL;
+
 inline size_t pd_up(size_t x) { return (x + 255) / 256 * 256; }
 constexpr size_t kPdLaneRowBytes = 64 * sizeof(PlanLane);   // one job's lane row: 64 lanes of {item, block}
 

@@ -28,11 +28,10 @@
 #include "pairhmm_fwd_kernel.h"  // recv_above, read_lane, kLanes
 #include "pdhmm_multi_plan.h"   // PdRegion: the multi-region launches
 #include "pdhmm_gather_plan.h"  // PdGatherDesc, PdRegionResults: the device-resident multi-region call
+#include "pdhmm_job_layout.h"   // kPdSnp and the other PD flag bits, kPdTabClasses, kPdRpl (GKL_PD_RPL): shared with the host's planner
 
 namespace gklhip {
 
-// PD flag bits of hap_pdbases (reference MathUtils.h:66-75)
-constexpr int kPdSnp = 1, kPdDelStart = 2, kPdDelEnd = 4, kPdA = 8, kPdC = 16, kPdG = 32, kPdT = 64;
 // stream entry: [7:0] haplotype base, [14:8] PD flag bits, [17:16] state on entry to the column,
 // [19:18] the same for the reference's SCALAR engine on rows >= 2 (its state variable survives from one row to the
 // next, pdhmm-serial.cc:306: those rows start in the state the previous row ended in), bit 30 = idle (no column).
@@ -55,7 +54,6 @@ constexpr uint32_t kPdIdle = 1u << 30, kPdOdd = 1u << 31, kPdMatchBits = 0xfffff
 // workgroup's LDS allocation returns 0 (ISA manuals since GCN3; tools/ubench_lds_oob.hip checks it on this chip), so a
 // lane on an idle entry that takes the step anyway computes with prior 0 -- which leaves a lane that has not started
 // in its initial state and adds +0 to the sum of one that is done (the whole-job asm program has no idle test).
-constexpr int kPdTabClasses = 6;
 constexpr uint32_t kPdTabDelEnd = 1u << 18, kPdTabOffsetMask = 0x7fffu, kPdTabSpecial = 1u << 31;
 constexpr uint32_t kPdTabIdleOffset = 0x6000u, kPdTabIdle = kPdIdle | kPdTabIdleOffset;
 __device__ __forceinline__ uint32_t pd_onehot_acgt(uint32_t b) {
@@ -66,11 +64,7 @@ __device__ __forceinline__ uint32_t pd_onehot_acgt(uint32_t b) {
 // wavefronts per SIMD) 11.2 ms, 3 rows 7.5, 4 rows 6.7, **5 rows 6.0** (256 VGPRs, 13 spilled outside the two
 // in-place step loops), 6 rows 6.5 (72-138 spilled), 8 rows 25 (523 spilled) with every step function in ONE kernel;
 // the kernel that carries only the two in-place loops (kHot, see pdhmm_fwd_kernel): 5 rows 6.0, **6 rows 5.5** (234
-// VGPRs, no spill), 7 rows 5.5 (5 spilled), 8 rows 5.5 (54 spilled).
-#ifndef GKL_PD_RPL
-#define GKL_PD_RPL 6
-#endif
-constexpr int kPdRpl = GKL_PD_RPL;
+// VGPRs, no spill), 7 rows 5.5 (5 spilled), 8 rows 5.5 (54 spilled).  (kPdRpl = GKL_PD_RPL: pdhmm_job_layout.h)
 #ifndef GKL_PD_TAB_UNROLL
 #define GKL_PD_TAB_UNROLL 1
 #endif

@@ -12,7 +12,7 @@
 namespace gklhip_pd_remote {
 
 struct Client;
-// One call, already checked (pd_validate / pd_cross_problem of pdhmm_api.hip).  Paired layout: n_read_items == n_hap_items == the batch.
+// One call, already checked (pd_validate / pd_cross_problem / pd_paired_problem of pdhmm_api.hip; sent by its pd_run_remote).  Paired layout: n_read_items == n_hap_items == the batch.
 struct Call {
   int32_t layout, n_read_items, n_hap_items, max_hap_len, max_read_len, flags;
   int64_t ref_batch_pairs, n_pairs;

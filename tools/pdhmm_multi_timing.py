@@ -77,7 +77,8 @@ def main():
         same = all(m.tobytes() == s.tobytes() for m, s in zip(outs_m, outs_s))
         row = {"K": K, "one_launch_set": bool(shared), "same_bytes": bool(same)}
         for name in ("multi", "singles"):
-            row[name] = {"host_ms_p50": round(float(np.median(t[name])), 4), "host_ms_p90": round(float(np.percentile(t[name], 90)), 4),
+            row[name] = {"host_ms_p50": round(float(np.median(t[name])), 4), "host_ms_p10": round(float(np.percentile(t[name], 10)), 4),
+                         "host_ms_p90": round(float(np.percentile(t[name], 90)), 4),
                          "kernel_ms_p50": round(float(np.median(k[name])), 4),
                          "tcups_host": round(K * cells / (float(np.median(t[name])) * 1e-3) / 1e12, 4)}
         row["host_speedup"] = round(row["singles"]["host_ms_p50"] / row["multi"]["host_ms_p50"], 3)
