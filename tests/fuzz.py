@@ -8,7 +8,7 @@ Every round draws new shapes (read / haplotype counts and lengths from 1 up to t
 N / lower case / arbitrary bytes, qualities 0..255, related and unrelated reads, both arithmetics, every rows-per-lane
 variant, single- and multi-shard contexts) and compares bit for bit: PairHMM raw fp32 / fp64 sums, fallback flags and
 host-finalised doubles; PDHMM doubles (vector arithmetic, paired and cross entry points); Smith-Waterman CIGAR bytes
-and offsets.  Prints one line per mismatch (with the seed that reproduces it) and a summary; exit code 1 on any."""
+and offsets (random ACGT, and random members of the edge families of tests/sw_cases.py under its parameter sets).  Prints one line per mismatch (with the seed that reproduces it) and a summary; exit code 1 on any."""
 import argparse
 import os
 import sys
@@ -37,6 +37,7 @@ def main():
     from oracle.oracle import Oracle
     from oracle.pdhmm import PdhmmOracle
     from oracle.sw import SwOracle
+    from tests import sw_cases
     from tests.test_pdhmm import cross_product, expand_cross, random_pd_batch
 
     oracle, pdo, swo = Oracle(), PdhmmOracle(), SwOracle()
@@ -131,6 +132,12 @@ def main():
                 alt = bytes(np.frombuffer(b"ACGT", np.uint8)[rng.randint(0, 4, n_alt)])
             params = [(200, -150, -260, -11), (25, -50, -110, -6), (3, -1, -4, -3), (10, -15, -30, -5)][int(rng.randint(0, 4))]
             strategy = [9, 10, 11, 12][int(rng.randint(0, 4))]
+            sw_kind = int(rng.randint(0, 4))
+            if sw_kind == 1:    # the same sequences under a parameter set that ties: zero penalties, extension dearer than opening...
+                params = sw_cases.EXTRA_PARAMS[int(rng.randint(0, len(sw_cases.EXTRA_PARAMS)))]
+            elif sw_kind >= 2:  # a random member of an edge family: low complexity, long gaps, stripe seams, the score floor, all bytes
+                ref, alt, params, strategy = sw_cases.draw(rng)
+                n_ref = len(ref)
             try:
                 g = sw.align(ref, alt, params, strategy)
                 e = swo.align(ref, alt, params, strategy)[1:]

@@ -72,7 +72,8 @@ def test_pdhmm_shapes(ctxs, n, rl, hl, seed, flag_rate):
 
 @settings(max_examples=300, **COMMON)
 @given(rl=length, al=length, seed=st.integers(0, 2**31 - 1), strategy=st.sampled_from([9, 10, 11, 12]),
-       params=st.sampled_from([(200, -150, -260, -11), (3, -1, -4, -3), (1, -1, -1, -1), (5, -4, 0, 0), (10, -5, -10, -10)]),
+       params=st.sampled_from([(200, -150, -260, -11), (3, -1, -4, -3), (1, -1, -1, -1), (5, -4, 0, 0), (10, -5, -10, -10),
+                               (1, 0, 0, 0), (0, 0, 0, 0), (2, -1, -1, -3), (1, 1, -1, -1), (65536, -65536, -3, -1)]),
        related=st.booleans())
 def test_smith_waterman_shapes(ctxs, rl, al, seed, strategy, params, related):
     from tests.test_sw import mutate
