@@ -23,3 +23,7 @@ class OutOfMemoryError(MemoryError):
 
 class RuntimeException(RuntimeError):
     pass
+
+
+class ArrayIndexOutOfBoundsException(IndexError):
+    pass

@@ -1124,3 +1124,195 @@ class SwContext:
             self.close()
         except Exception:
             pass
+
+
+# ---------------------------------------------------------------- batch inflate (include/inflate/gkl_hip_inflate.h)
+INFLATE_LIB_PATH = os.path.join(LIB_DIR, "libgklhip_inflate.so")
+INFLATE_OK, INFLATE_INVALID_BLOCK, INFLATE_INVALID_SYMBOL, INFLATE_INVALID_LOOKBACK, INFLATE_END_INPUT, INFLATE_OUT_OVERFLOW = range(6)
+_inflate_lib = None
+
+
+def load_inflate_library(path: Optional[str] = None):
+    global _inflate_lib
+    if _inflate_lib is not None and path is None:
+        return _inflate_lib
+    p = path or INFLATE_LIB_PATH
+    try:
+        import torch  # noqa: F401  (HIP runtime load order, see load_library)
+    except ImportError:
+        pass
+    if not os.path.exists(p):
+        raise RuntimeException(f"{p} is not built (hipcc --offload-arch=gfx950); there is no CPU fallback")
+    lib = C.CDLL(p)
+    lib.gklhip_inflate_init.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
+    lib.gklhip_inflate_init.restype = C.c_int
+    lib.gklhip_inflate_done.argtypes = [C.c_void_p]
+    lib.gklhip_inflate_done.restype = C.c_int
+    lib.gklhip_inflate_batch.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 8
+    lib.gklhip_inflate_batch.restype = C.c_int
+    lib.gklhip_inflate_batch_device.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 9
+    lib.gklhip_inflate_batch_device.restype = C.c_int
+    lib.gklhip_bgzf_scan.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
+    lib.gklhip_bgzf_scan.restype = C.c_int
+    lib.gklhip_bgzf_inflate.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
+    lib.gklhip_bgzf_inflate.restype = C.c_int
+    lib.gklhip_inflate_last_kernel_ms.argtypes = [C.c_void_p]
+    lib.gklhip_inflate_last_kernel_ms.restype = C.c_float
+    lib.gklhip_inflate_last_error.restype = C.c_char_p
+    if path is None:
+        _inflate_lib = lib
+    return lib
+
+
+class BgzfError(IllegalArgumentException):
+    """A BGZF file image that gklhip_bgzf_scan / gklhip_bgzf_inflate refuse; bad_member is the first member at fault."""
+
+    def __init__(self, msg, bad_member):
+        super().__init__(msg)
+        self.bad_member = bad_member
+
+
+def bgzf_scan(data, max_members: Optional[int] = None):
+    """gklhip_bgzf_scan (host only, no device needed): (payload_off int64[n], payload_len int32[n], crc32 uint32[n],
+    isize uint32[n], bytes_used) of the BGZF members of a file image; BgzfError at a malformed member."""
+    lib = load_inflate_library()
+    buf = np.frombuffer(bytes(data) or b"\0", dtype=np.uint8)
+    length = len(data)
+    n, used = C.c_int32(0), C.c_int64(0)
+    if max_members is None:
+        st = lib.gklhip_bgzf_scan(buf.ctypes.data, length, 0, None, None, None, None, C.byref(n), C.byref(used))
+        if st != OK:
+            raise BgzfError((lib.gklhip_inflate_last_error() or b"").decode(), n.value)
+        max_members = n.value
+    m = max(int(max_members), 1)
+    off, plen = np.zeros(m, np.int64), np.zeros(m, np.int32)
+    crc, isize = np.zeros(m, np.uint32), np.zeros(m, np.uint32)
+    st = lib.gklhip_bgzf_scan(buf.ctypes.data, length, int(max_members), off.ctypes.data, plen.ctypes.data, crc.ctypes.data,
+                              isize.ctypes.data, C.byref(n), C.byref(used))
+    if st != OK:
+        raise BgzfError((lib.gklhip_inflate_last_error() or b"").decode(), n.value)
+    k = n.value
+    return off[:k], plen[:k], crc[:k], isize[:k], used.value
+
+
+class InflateContext:
+    """One gklhip_inflate context: batches of independent raw-deflate streams, one wavefront per stream."""
+
+    def __init__(self, device: int = -1):
+        self.lib = load_inflate_library()
+        h = C.c_void_p()
+        st = self.lib.gklhip_inflate_init(device, C.byref(h))
+        if st != OK:
+            self._raise(st)
+        self.handle = h
+
+    def _raise(self, status):
+        msg = (self.lib.gklhip_inflate_last_error() or b"").decode()
+        if status == ERR_INVALID_ARG:
+            raise IllegalArgumentException(msg)
+        if status == ERR_OOM:
+            raise OutOfMemoryError(msg)
+        raise RuntimeException(msg)
+
+    def inflate_batch_raw(self, src: np.ndarray, src_off: np.ndarray, dst: np.ndarray, dst_off: np.ndarray, want_crc: bool = True):
+        """gklhip_inflate_batch on flat arrays: src / dst uint8, src_off / dst_off int64[n + 1]; dst is written in place
+        (only the bytes the streams produce).  Returns (out_len int32[n], consumed int32[n], crc32 uint32[n] or None,
+        status int32[n])."""
+        n = len(src_off) - 1
+        if n < 0 or len(dst_off) != n + 1:
+            raise IllegalArgumentException("n + 1 offsets each")
+        src_off, dst_off = np.ascontiguousarray(src_off, np.int64), np.ascontiguousarray(dst_off, np.int64)
+        if src.dtype != np.uint8 or dst.dtype != np.uint8 or not src.flags.c_contiguous or not dst.flags.c_contiguous:
+            raise IllegalArgumentException("src and dst must be contiguous uint8 arrays")
+        if n and (src_off[-1] > src.size or dst_off[-1] > dst.size):
+            raise IllegalArgumentException("offsets exceed the arrays")
+        m = max(n, 1)
+        out_len, consumed, status = np.zeros(m, np.int32), np.zeros(m, np.int32), np.zeros(m, np.int32)
+        crc = np.zeros(m, np.uint32) if want_crc else None
+        st = self.lib.gklhip_inflate_batch(self.handle, n, src.ctypes.data, src_off.ctypes.data, dst.ctypes.data, dst_off.ctypes.data,
+                                           out_len.ctypes.data, consumed.ctypes.data, crc.ctypes.data if want_crc else None,
+                                           status.ctypes.data)
+        if st != OK:
+            self._raise(st)
+        return out_len[:n], consumed[:n], (crc[:n] if want_crc else None), status[:n]
+
+    def inflate_batch(self, streams, capacities):
+        """Lists in, lists out: (outputs, crcs, statuses, consumed).  outputs[k] is the valid prefix (all of the output
+        when statuses[k] == INFLATE_OK), crcs[k] its CRC-32."""
+        streams = [bytes(s) for s in streams]
+        n = len(streams)
+        if len(capacities) != n:
+            raise IllegalArgumentException("one capacity per stream")
+        so, do = np.zeros(n + 1, np.int64), np.zeros(n + 1, np.int64)
+        np.cumsum([len(s) for s in streams], out=so[1:])
+        np.cumsum([int(c) for c in capacities], out=do[1:])
+        src = np.frombuffer(b"".join(streams) or b"\0", dtype=np.uint8)
+        dst = np.zeros(max(int(do[-1]), 1), np.uint8)
+        out_len, consumed, crc, status = self.inflate_batch_raw(src, so, dst, do)
+        outs = [dst[do[k]:do[k] + out_len[k]].tobytes() for k in range(n)]
+        return outs, [int(c) for c in crc], [int(s) for s in status], [int(c) for c in consumed]
+
+    def inflate_batch_device(self, src, src_off, dst, dst_off, want_crc: bool = True, stream=None):
+        """gklhip_inflate_batch_device (synchronous): src and dst are contiguous torch uint8 CUDA tensors on the
+        context's device, src_off / dst_off int64[n + 1] on the host; dst is written in place.  Returns torch tensors
+        (out_len int32, consumed int32, crc32 as int32 bit patterns or None, status int32) on that device."""
+        import torch
+        n = len(src_off) - 1
+        if n < 0 or len(dst_off) != n + 1:
+            raise IllegalArgumentException("n + 1 offsets each")
+        for t in (src, dst):
+            if t.dtype != torch.uint8 or not t.is_cuda or not t.is_contiguous():
+                raise IllegalArgumentException("src and dst must be contiguous uint8 CUDA tensors")
+        src_off, dst_off = np.ascontiguousarray(src_off, np.int64), np.ascontiguousarray(dst_off, np.int64)
+        if n and (src_off[-1] > src.numel() or dst_off[-1] > dst.numel()):
+            raise IllegalArgumentException("offsets exceed the tensors")
+        m = max(n, 1)
+        out_len, consumed, status = (torch.zeros(m, dtype=torch.int32, device=dst.device) for _ in range(3))
+        crc = torch.zeros(m, dtype=torch.int32, device=dst.device) if want_crc else None
+        if stream is None:
+            stream = torch.cuda.current_stream(dst.device)
+        st = self.lib.gklhip_inflate_batch_device(self.handle, n, src.data_ptr(), src_off.ctypes.data, dst.data_ptr(),
+                                                  dst_off.ctypes.data, out_len.data_ptr(), consumed.data_ptr(),
+                                                  crc.data_ptr() if want_crc else None, status.data_ptr(), stream.cuda_stream)
+        if st != OK:
+            self._raise(st)
+        return out_len[:n], consumed[:n], (crc[:n] if want_crc else None), status[:n]
+
+    bgzf_scan = staticmethod(bgzf_scan)
+
+    def bgzf_inflate(self, data, out_cap: Optional[int] = None) -> bytes:
+        """gklhip_bgzf_inflate: the concatenated output of every member of a BGZF file image, each member's CRC32 and
+        ISIZE checked; BgzfError (bad_member set) otherwise."""
+        data = bytes(data)
+        if out_cap is None:
+            out_cap = int(bgzf_scan(data)[3].astype(np.int64).sum())
+        buf = np.frombuffer(data or b"\0", dtype=np.uint8)
+        out = np.zeros(max(int(out_cap), 1), np.uint8)
+        n, bad = C.c_int64(0), C.c_int32(-1)
+        st = self.lib.gklhip_bgzf_inflate(self.handle, buf.ctypes.data, len(data), out.ctypes.data, int(out_cap), C.byref(n), C.byref(bad))
+        if st != OK:
+            if bad.value >= 0:
+                raise BgzfError((self.lib.gklhip_inflate_last_error() or b"").decode(), bad.value)
+            self._raise(st)
+        return out[:n.value].tobytes()
+
+    def last_kernel_ms(self) -> float:
+        return float(self.lib.gklhip_inflate_last_kernel_ms(self.handle))
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self.lib.gklhip_inflate_done(self.handle)
+            self.handle = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
