@@ -1316,3 +1316,185 @@ class InflateContext:
             self.close()
         except Exception:
             pass
+
+
+# ---------------------------------------------------------------- batch deflate (include/deflate/gkl_hip_deflate.h)
+DEFLATE_LIB_PATH = os.path.join(LIB_DIR, "libgklhip_deflate.so")
+DEFLATE_OK, DEFLATE_OUT_OVERFLOW = range(2)
+DEFLATE_DEFAULT_STRATEGY, DEFLATE_HUFFMAN_ONLY = range(2)
+DEFLATE_STORED, DEFLATE_FIXED, DEFLATE_DYNAMIC = 1, 2, 4
+_deflate_lib = None
+
+
+def load_deflate_library(path: Optional[str] = None):
+    global _deflate_lib
+    if _deflate_lib is not None and path is None:
+        return _deflate_lib
+    p = path or DEFLATE_LIB_PATH
+    try:
+        import torch  # noqa: F401  (HIP runtime load order, see load_library)
+    except ImportError:
+        pass
+    if not os.path.exists(p):
+        raise RuntimeException(f"{p} is not built (hipcc --offload-arch=gfx950); there is no CPU fallback")
+    lib = C.CDLL(p)
+    lib.gklhip_deflate_init.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
+    lib.gklhip_deflate_init.restype = C.c_int
+    lib.gklhip_deflate_done.argtypes = [C.c_void_p]
+    lib.gklhip_deflate_done.restype = C.c_int
+    lib.gklhip_deflate_bound.argtypes = [C.c_int64]
+    lib.gklhip_deflate_bound.restype = C.c_int64
+    lib.gklhip_deflate_set_strategy.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
+    lib.gklhip_deflate_set_strategy.restype = C.c_int
+    lib.gklhip_deflate_batch.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 4 + [C.c_int32] + [C.c_void_p] * 3
+    lib.gklhip_deflate_batch.restype = C.c_int
+    lib.gklhip_deflate_batch_device.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 4 + [C.c_int32] + [C.c_void_p] * 4
+    lib.gklhip_deflate_batch_device.restype = C.c_int
+    lib.gklhip_bgzf_bound.argtypes = [C.c_int64, C.c_int32]
+    lib.gklhip_bgzf_bound.restype = C.c_int64
+    lib.gklhip_bgzf_deflate.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64,
+                                        C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
+    lib.gklhip_bgzf_deflate.restype = C.c_int
+    lib.gklhip_deflate_last_kernel_ms.argtypes = [C.c_void_p]
+    lib.gklhip_deflate_last_kernel_ms.restype = C.c_float
+    lib.gklhip_deflate_last_error.restype = C.c_char_p
+    if path is None:
+        _deflate_lib = lib
+    return lib
+
+
+def deflate_bound(length: int) -> int:
+    """gklhip_deflate_bound (host arithmetic, no device needed): the stored size of `length` input bytes."""
+    return int(load_deflate_library().gklhip_deflate_bound(int(length)))
+
+
+def bgzf_bound(length: int, block_size: int = 0) -> int:
+    """gklhip_bgzf_bound (host arithmetic): an output capacity that bgzf_deflate never exceeds; -1 for a bad block size."""
+    return int(load_deflate_library().gklhip_bgzf_bound(int(length), int(block_size)))
+
+
+class DeflateContext:
+    """One gklhip_deflate context: batches of independent inputs, one wavefront per raw-deflate stream."""
+
+    def __init__(self, device: int = -1):
+        self.lib = load_deflate_library()
+        h = C.c_void_p()
+        st = self.lib.gklhip_deflate_init(device, C.byref(h))
+        if st != OK:
+            self._raise(st)
+        self.handle = h
+
+    def _raise(self, status):
+        msg = (self.lib.gklhip_deflate_last_error() or b"").decode()
+        if status == ERR_INVALID_ARG:
+            raise IllegalArgumentException(msg)
+        if status == ERR_OOM:
+            raise OutOfMemoryError(msg)
+        raise RuntimeException(msg)
+
+    def set_strategy(self, strategy: int = DEFLATE_DEFAULT_STRATEGY, block_types: int = 0) -> None:
+        """strategy 0 default, 1 Huffman only; block_types a mask of DEFLATE_STORED / _FIXED / _DYNAMIC, 0 = all."""
+        st = self.lib.gklhip_deflate_set_strategy(self.handle, int(strategy), int(block_types))
+        if st != OK:
+            self._raise(st)
+
+    def deflate_batch_raw(self, src: np.ndarray, src_off: np.ndarray, dst: np.ndarray, dst_off: np.ndarray, level: int = 1,
+                          want_crc: bool = True):
+        """gklhip_deflate_batch on flat arrays: src / dst uint8, src_off / dst_off int64[n + 1]; dst is written in place
+        (only the bytes of the streams).  Returns (out_len int32[n], crc32 of the inputs uint32[n] or None,
+        status int32[n])."""
+        n = len(src_off) - 1
+        if n < 0 or len(dst_off) != n + 1:
+            raise IllegalArgumentException("n + 1 offsets each")
+        src_off, dst_off = np.ascontiguousarray(src_off, np.int64), np.ascontiguousarray(dst_off, np.int64)
+        if src.dtype != np.uint8 or dst.dtype != np.uint8 or not src.flags.c_contiguous or not dst.flags.c_contiguous:
+            raise IllegalArgumentException("src and dst must be contiguous uint8 arrays")
+        if n and (src_off[-1] > src.size or dst_off[-1] > dst.size):
+            raise IllegalArgumentException("offsets exceed the arrays")
+        m = max(n, 1)
+        out_len, status = np.zeros(m, np.int32), np.zeros(m, np.int32)
+        crc = np.zeros(m, np.uint32) if want_crc else None
+        st = self.lib.gklhip_deflate_batch(self.handle, n, src.ctypes.data, src_off.ctypes.data, dst.ctypes.data, dst_off.ctypes.data,
+                                           int(level), out_len.ctypes.data, crc.ctypes.data if want_crc else None, status.ctypes.data)
+        if st != OK:
+            self._raise(st)
+        return out_len[:n], (crc[:n] if want_crc else None), status[:n]
+
+    def deflate_batch(self, inputs, level: int = 1, capacities=None):
+        """Lists in, lists out: (streams, crcs of the inputs, statuses).  capacities default to deflate_bound of each
+        input, which never overflows while stored blocks are allowed; streams[k] is b"" on DEFLATE_OUT_OVERFLOW."""
+        inputs = [bytes(s) for s in inputs]
+        n = len(inputs)
+        if capacities is None:
+            capacities = [deflate_bound(len(s)) for s in inputs]
+        if len(capacities) != n:
+            raise IllegalArgumentException("one capacity per input")
+        so, do = np.zeros(n + 1, np.int64), np.zeros(n + 1, np.int64)
+        np.cumsum([len(s) for s in inputs], out=so[1:])
+        np.cumsum([int(c) for c in capacities], out=do[1:])
+        src = np.frombuffer(b"".join(inputs) or b"\0", dtype=np.uint8)
+        dst = np.zeros(max(int(do[-1]), 1), np.uint8)
+        out_len, crc, status = self.deflate_batch_raw(src, so, dst, do, level)
+        outs = [dst[do[k]:do[k] + out_len[k]].tobytes() for k in range(n)]
+        return outs, [int(c) for c in crc], [int(s) for s in status]
+
+    def deflate_batch_device(self, src, src_off, dst, dst_off, level: int = 1, want_crc: bool = True, stream=None):
+        """gklhip_deflate_batch_device (synchronous): src and dst are contiguous torch uint8 CUDA tensors on the
+        context's device, src_off / dst_off int64[n + 1] on the host; dst is written in place.  Returns torch tensors
+        (out_len int32, crc32 of the inputs as int32 bit patterns or None, status int32) on that device."""
+        import torch
+        n = len(src_off) - 1
+        if n < 0 or len(dst_off) != n + 1:
+            raise IllegalArgumentException("n + 1 offsets each")
+        for t in (src, dst):
+            if t.dtype != torch.uint8 or not t.is_cuda or not t.is_contiguous():
+                raise IllegalArgumentException("src and dst must be contiguous uint8 CUDA tensors")
+        src_off, dst_off = np.ascontiguousarray(src_off, np.int64), np.ascontiguousarray(dst_off, np.int64)
+        if n and (src_off[-1] > src.numel() or dst_off[-1] > dst.numel()):
+            raise IllegalArgumentException("offsets exceed the tensors")
+        m = max(n, 1)
+        out_len, status = (torch.zeros(m, dtype=torch.int32, device=dst.device) for _ in range(2))
+        crc = torch.zeros(m, dtype=torch.int32, device=dst.device) if want_crc else None
+        if stream is None:
+            stream = torch.cuda.current_stream(dst.device)
+        st = self.lib.gklhip_deflate_batch_device(self.handle, n, src.data_ptr(), src_off.ctypes.data, dst.data_ptr(),
+                                                  dst_off.ctypes.data, int(level), out_len.data_ptr(),
+                                                  crc.data_ptr() if want_crc else None, status.data_ptr(), stream.cuda_stream)
+        if st != OK:
+            self._raise(st)
+        return out_len[:n], (crc[:n] if want_crc else None), status[:n]
+
+    def bgzf_deflate(self, data, block_size: int = 0, level: int = 1, append_eof: bool = True):
+        """gklhip_bgzf_deflate: the BGZF image of data (members of block_size input bytes, 0 = 65280) and its member count."""
+        data = bytes(data)
+        cap = bgzf_bound(len(data), block_size)
+        if cap < 0:
+            raise IllegalArgumentException(f"block_size {block_size}: 1 .. 65498, 0 = 65280")
+        buf = np.frombuffer(data or b"\0", dtype=np.uint8)
+        out = np.zeros(max(cap, 1), np.uint8)
+        n, members = C.c_int64(0), C.c_int32(0)
+        st = self.lib.gklhip_bgzf_deflate(self.handle, buf.ctypes.data, len(data), int(block_size), int(level), 1 if append_eof else 0,
+                                          out.ctypes.data, cap, C.byref(n), C.byref(members))
+        if st != OK:
+            self._raise(st)
+        return out[:n.value].tobytes(), members.value
+
+    def last_kernel_ms(self) -> float:
+        return float(self.lib.gklhip_deflate_last_kernel_ms(self.handle))
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self.lib.gklhip_deflate_done(self.handle)
+            self.handle = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

@@ -8,7 +8,8 @@
  * (acceptance rules: zlib's inflate with windowBits = -15); every malformed input becomes a per-stream status.
  * The header has a directory of its own under include/: the headers directly in include/ are the set whose libraries
  * tests/test_cabi_cpu.py enumerates; tests/test_inflate_core_cpu.py checks this one's symbols.
- * Not here: the deflater, a libgkl_compression drop-in, JNI, the zlib and gzip wrappers other than BGZF members.
+ * The deflater is include/deflate/gkl_hip_deflate.h.
+ * Not here: a libgkl_compression drop-in, JNI, the zlib and gzip wrappers other than BGZF members.
  */
 #ifndef GKL_HIP_INFLATE_H
 #define GKL_HIP_INFLATE_H
