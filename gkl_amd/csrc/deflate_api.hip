@@ -82,8 +82,8 @@ int job_from_offsets(Job& job, int32_t n, const int64_t* src_off, const int64_t*
 }
 
 int check_level(int32_t level) {
-  if (level == 0 || level == 1) return GKLHIP_OK;
-  return fail(GKLHIP_ERR_UNSUPPORTED, "compression level %d is not built: 0 (stored) and 1 are", level);
+  if (level == 0 || level == 1 || (level >= 3 && level <= 8)) return GKLHIP_OK;
+  return fail(GKLHIP_ERR_UNSUPPORTED, "compression level %d is not built: 0 (stored), 1 and 3 to 8 are", level);
 }
 
 size_t meta_bytes(size_t n) { return 256 + up(n * sizeof(DeflateStream)) + up(n * 4); }
@@ -117,7 +117,9 @@ int launch(gklhip_deflate_ctx* c, hipStream_t s, const Job& job, int32_t level, 
   // persistent wavefronts: each pulls inputs until the counter runs out, each owns one slice of the token area
   const int n_waves = (int)std::min<size_t>(n, (size_t)c->n_waves);
   HIP_TRY(hipEventRecord(c->ev0, s));
-  hipLaunchKernelGGL(deflate_kernel, dim3(n_waves), dim3(64), 0, s, a);
+  // levels 0 and 1 launch the kernel they always had; the chain search of levels 3-8 is a kernel of its own
+  if (level >= 3) hipLaunchKernelGGL(deflate_kernel<gkldef::SEARCH_CHAINS>, dim3(n_waves), dim3(64), 0, s, a);
+  else hipLaunchKernelGGL(deflate_kernel<gkldef::SEARCH_TABLE>, dim3(n_waves), dim3(64), 0, s, a);
   HIP_TRY(hipEventRecord(c->ev1, s));
   HIP_TRY(hipGetLastError());
   return GKLHIP_OK;

@@ -1,4 +1,4 @@
-// RFC 1951 encoder, written once: match search, greedy selection, histograms, length-limited code construction, the
+// RFC 1951 encoder, written once: match search, greedy or lazy selection, histograms, length-limited code construction, the
 // block-type decision by exact bit count and the bit packing.  deflate_kernel.h instantiates it for a wavefront
 // (64 lanes), tests/native/deflate_core_check.cpp for one host thread and for four (under the sanitizers).  The execution
 // policy X says how a step is carried out, never what it decides:
@@ -18,6 +18,26 @@
 //
 // A stream is cut into blocks of kBlockLen input bytes; positions are block-relative and matches never reach before the
 // block, so a table entry is 16 bits (position + 1, 0 = empty).
+//
+// LEVELS 3-8 (tokenize_chains) search hash chains instead of the one-entry table, under the same contract.  The table
+// holds the head of each chain (the latest position of a 3-byte hash), a ring of kRingLen 16-bit links behind the tokens
+// in the lanes' own area holds prev[p & (kRingLen - 1)] = the previous position of p's hash (+ 1, 0 = none).  Unlike
+// level 1, a lookup at p sees EVERY lower position of the block, its own chunk's included: the links come out as if the
+// positions had been inserted one by one in ascending order.  Per chunk: the 64 hashes go to shared memory, every
+// position takes as its link the nearest lower position of its chunk with the same hash, or else the head as before
+// the chunk, and writes it to the ring; then the heads move ("the highest position wins") while every position walks
+// its own chain: at most depth(level) candidates, nearest first, the longest match kept (on a tie the nearest), the
+// walk over at nice(level) bytes, at the end of the input or at 258.  A walk checks, BEFORE it reads a candidate's link,
+// that the candidate lies below the one before it and within kMaxDist: a ring slot that a position kRingLen higher has
+// taken over may hold anything (of this block; a slot is never read before this block wrote it), and such a link ends
+// the walk or leads to a lower position that is compared like any other -- so the loop runs at most depth times.  A
+// 3-byte match farther than kFar3 is dropped.  Lazy selection (a match at p yields to a longer one at p + 1, p becomes
+// a literal) looks at the chunk's candidates only: the last position of a chunk does not look ahead.
+//     level   3    4    5    6    7    8
+//     depth   4    8   16   32   64  128
+//     nice   32   32   64  128  258  258
+//     lazy   no  yes  yes  yes  yes  yes
+// Huffman-only takes no search at any level, so its bytes are those of level 1.
 #pragma once
 #include <stdint.h>
 
@@ -34,9 +54,12 @@ enum Strategy : int32_t { STRATEGY_DEFAULT = 0, STRATEGY_HUFFMAN_ONLY = 1 };
 enum BlockType : int32_t { BT_STORED = 1, BT_FIXED = 2, BT_DYNAMIC = 4, BT_ALL = 7 };
 
 constexpr uint32_t kBlockLen = 65535;        // input bytes per deflate block: a stored block is always possible
-constexpr uint32_t kTokensPerWave = 65536;   // one token per input byte at the most, plus the end-of-block token
+constexpr uint32_t kTokenWords = 65536;      // one token per input byte at the most, plus the end-of-block token
+constexpr uint32_t kRingLen = 32768;         // levels 3-8: the 16-bit chain links of the last kMaxDist positions, 64 KB
+constexpr uint32_t kTokensPerWave = kTokenWords + kRingLen / 2;   // words of a wavefront's own area: tokens, then the ring (320 KB)
 constexpr int kHashBits = 13;                // 8192 slots, one entry each: 16 KB
 constexpr uint32_t kMinMatch = 4, kMaxMatch = 258, kMaxDist = 32768;
+constexpr uint32_t kFar3 = 4096;             // levels 3-8: a 3-byte match farther back than this is dropped (zlib's TOO_FAR)
 constexpr uint32_t kTokMatch = 0x80000000u;  // token: a literal byte, 256 = end of block, or kTokMatch | (len - 3) << 16 | (dist - 1)
 
 // the node arrays of one code construction (2 * 286 - 1 nodes at the most)
@@ -62,7 +85,7 @@ struct Scratch {
   uint16_t lcode[288], dcode[32], ccode[20];
   uint8_t llen[288], dlen[32], clen[20];
   uint16_t bl_count[16], next_code[16];
-  uint16_t mlen[64], mdist[64];      // the chunk's candidates
+  uint16_t mlen[64], mdist[64];      // the chunk's candidates (levels 3-8: before them the chunk's links and hashes)
   uint32_t staging[104];             // 7 carried bits + 64 x 48 bits
   uint16_t hdr[320];                 // the dynamic header's code-length symbols: symbol | extra << 8
   uint32_t n_hdr, n_used, hlit, hdist;
@@ -75,7 +98,28 @@ GKL_DEF_FN uint32_t bit_reverse(uint32_t v, int n) {
 }
 GKL_DEF_FN uint32_t load4(const uint8_t* p) { uint32_t v; __builtin_memcpy(&v, p, 4); return v; }
 GKL_DEF_FN uint32_t hash4(uint32_t v) { return (v * 2654435761u) >> (32 - kHashBits); }
+GKL_DEF_FN uint32_t hash3(uint32_t v) { return ((v & 0xFFFFFFu) * 2654435761u) >> (32 - kHashBits); }
 GKL_DEF_FN uint32_t floor_log2(uint32_t v) { return 31u - (uint32_t)__builtin_clz(v); }
+
+// levels 3-8: the candidates a walk may try, the length that ends it, lazy selection or greedy
+struct LevelParams { uint16_t depth, nice, lazy; };
+GKL_DEF_FN LevelParams level_params(int32_t level) {
+  constexpr LevelParams table[6] = {{4, 32, 0}, {8, 32, 1}, {16, 64, 1}, {32, 128, 1}, {64, 258, 1}, {128, 258, 1}};
+  return table[level < 3 ? 0 : level > 8 ? 5 : level - 3];
+}
+
+// the bytes in[c...] and in[p...] share, maxl at the most; c < p, p + maxl <= the end of the input.  (Level 1 keeps
+// the loop it was built with: through this function its kernel takes 118 VGPRs instead of 114.)
+GKL_DEF_FN uint32_t match_length(const uint8_t* in, uint32_t c, uint32_t p, uint32_t maxl) {
+  uint32_t l = 0;
+  while (l + 4 <= maxl) {   // four bytes a step
+    const uint32_t x = load4(in + c + l) ^ load4(in + p + l);
+    if (x) return l + ((uint32_t)__builtin_ctz(x) >> 3);
+    l += 4;
+  }
+  while (l < maxl && in[c + l] == in[p + l]) l++;
+  return l;
+}
 
 // length 3..258 -> symbol 257..285, extra bits
 GKL_DEF_FN void length_symbol(uint32_t len, uint32_t* sym, uint32_t* nextra, uint32_t* extra) {
@@ -197,7 +241,10 @@ GKL_DEF_FN void assign_codes(Scratch& S, const uint8_t* lens, uint32_t n, uint16
   X::sync();
 }
 
-template <class X>
+// kSearches: which match searches an instantiation carries, so that a kernel for level 1 holds no code of levels 3-8
+enum Searches : int { SEARCH_TABLE = 1, SEARCH_CHAINS = 2, SEARCH_BOTH = 3 };
+
+template <class X, int kSearches = SEARCH_BOTH>
 struct Deflater {
   Scratch& S;
   uint8_t* dst;
@@ -285,43 +332,129 @@ struct Deflater {
           const uint32_t p = b + i;
           if (p + 4 <= n) X::atomic_max16(&S.u.table[hash4(load4(in + p))], (uint16_t)(p + 1));
         }
-      // greedy selection in position order, the same in every lane
-      const uint32_t cnt = n - b < 64 ? n - b : 64;
-      const uint64_t valid = cnt == 64 ? ~0ull : (1ull << cnt) - 1ull;
-      const uint64_t cand = X::which64(S.mlen) & valid;
-      const uint32_t first = next > b ? next - b : 0;   // < 64 or the whole chunk is covered
-      uint64_t covered = first >= 64 ? ~0ull : (1ull << first) - 1ull;
-      uint64_t starts = 0;
-      uint64_t open = cand & ~covered;
-      while (open) {
-        const uint32_t i = (uint32_t)__builtin_ctzll(open);
-        const uint32_t e = i + S.mlen[i];
-        starts |= 1ull << i;
-        const uint64_t upto = e >= 64 ? ~0ull : (1ull << e) - 1ull;
-        covered |= upto & ~((2ull << i) - 1ull);
-        next = b + e;
-        open &= ~upto;
-      }
-      const uint64_t tokmask = valid & ~covered;   // literals and match starts
-      for (uint32_t i = lane; i < cnt; i += X::kLanes) {
-        if (!((tokmask >> i) & 1ull)) continue;
-        const uint32_t idx = ntok + (uint32_t)__builtin_popcountll(tokmask & ((1ull << i) - 1ull));
-        if ((starts >> i) & 1ull) {
-          const uint32_t len = S.mlen[i], d1 = S.mdist[i];
-          uint32_t ls, ds, nx, ex;
-          length_symbol(len, &ls, &nx, &ex);
-          dist_symbol(d1 + 1, &ds, &nx, &ex);
-          toks[idx] = kTokMatch | ((len - 3) << 16) | d1;
-          X::atomic_add(&S.lhist[ls], 1u);
-          X::atomic_add(&S.dhist[ds], 1u);
-        } else {
-          const uint32_t byte = in[b + i];
-          toks[idx] = byte;
-          X::atomic_add(&S.lhist[byte], 1u);
-        }
-      }
-      ntok += (uint32_t)__builtin_popcountll(tokmask);
+      select64(in, b, n, false, &next, &ntok);
       X::sync();   // mlen / mdist are free again, the inserts are in the table
+    }
+    if (lane == 0) { toks[ntok] = 256; S.lhist[256] += 1; }
+    X::sync();
+    return ntok + 1;
+  }
+
+  // Selection over the candidates of the chunk at b (mlen / mdist, visible already) in position order, the same in
+  // every lane, then the chunk's tokens and their counts.  Greedy: the first candidate that no match covers is taken.
+  // Lazy: such a candidate yields to a longer one at the next position of the same chunk and becomes a literal.
+  GKL_DEF_FN void select64(const uint8_t* in, uint32_t b, uint32_t n, bool lazy, uint32_t* next_io, uint32_t* ntok_io) {
+    const uint32_t lane = (uint32_t)X::lane();
+    uint32_t next = *next_io;
+    const uint32_t ntok = *ntok_io;
+    const uint32_t cnt = n - b < 64 ? n - b : 64;
+    const uint64_t valid = cnt == 64 ? ~0ull : (1ull << cnt) - 1ull;
+    const uint64_t cand = X::which64(S.mlen) & valid;
+    const uint32_t first = next > b ? next - b : 0;   // < 64 or the whole chunk is covered
+    uint64_t covered = first >= 64 ? ~0ull : (1ull << first) - 1ull;
+    uint64_t starts = 0;
+    uint64_t open = cand & ~covered;
+    while (open) {
+      const uint32_t i = (uint32_t)__builtin_ctzll(open);
+      if (lazy && ((open >> i) & 2ull) && S.mlen[i + 1] > S.mlen[i]) {   // bit i + 1 of open: i < 63
+        open &= ~(1ull << i);
+        continue;
+      }
+      const uint32_t e = i + S.mlen[i];
+      starts |= 1ull << i;
+      const uint64_t upto = e >= 64 ? ~0ull : (1ull << e) - 1ull;
+      covered |= upto & ~((2ull << i) - 1ull);
+      next = b + e;
+      open &= ~upto;
+    }
+    const uint64_t tokmask = valid & ~covered;   // literals and match starts
+    for (uint32_t i = lane; i < cnt; i += X::kLanes) {
+      if (!((tokmask >> i) & 1ull)) continue;
+      const uint32_t idx = ntok + (uint32_t)__builtin_popcountll(tokmask & ((1ull << i) - 1ull));
+      if ((starts >> i) & 1ull) {
+        const uint32_t len = S.mlen[i], d1 = S.mdist[i];
+        uint32_t ls, ds, nx, ex;
+        length_symbol(len, &ls, &nx, &ex);
+        dist_symbol(d1 + 1, &ds, &nx, &ex);
+        toks[idx] = kTokMatch | ((len - 3) << 16) | d1;
+        X::atomic_add(&S.lhist[ls], 1u);
+        X::atomic_add(&S.dhist[ds], 1u);
+      } else {
+        const uint32_t byte = in[b + i];
+        toks[idx] = byte;
+        X::atomic_add(&S.lhist[byte], 1u);
+      }
+    }
+    *next_io = next;
+    *ntok_io = ntok + (uint32_t)__builtin_popcountll(tokmask);
+  }
+
+  // Levels 3-8: hash chains, bounded walks, lazy or greedy selection (see the head of the file).  Tokens to toks[],
+  // counts to lhist / dhist, links to the ring behind the tokens.  Returns the token count.
+  GKL_DEF_FN uint32_t tokenize_chains(const uint8_t* in, uint32_t n, const LevelParams lp) {
+    const uint32_t lane = (uint32_t)X::lane();
+    uint16_t* ring = reinterpret_cast<uint16_t*>(toks + kTokenWords);   // these words hold links only, never tokens
+    for (uint32_t i = lane; i < (1u << kHashBits) / 2; i += X::kLanes) S.u.table_words[i] = 0;
+    for (uint32_t i = lane; i < 288; i += X::kLanes) S.lhist[i] = 0;
+    for (uint32_t i = lane; i < 32; i += X::kLanes) S.dhist[i] = 0;
+    X::sync();
+    constexpr uint32_t kNoHash = 0xFFFFu;   // a position with fewer than 3 bytes left: no hash, no link, no lookup
+    uint32_t ntok = 0, next = 0;
+    for (uint32_t b = 0; b < n; b += 64) {
+      // the chunk's hashes (mdist holds them until the candidates take it back)
+      for (uint32_t i = lane; i < 64; i += X::kLanes) {
+        const uint32_t p = b + i;
+        uint32_t h = kNoHash;
+        if (p + 4 <= n) h = hash3(load4(in + p));
+        else if (p + 3 == n) h = hash3((uint32_t)in[p] | ((uint32_t)in[p + 1] << 8) | ((uint32_t)in[p + 2] << 16));
+        S.mdist[i] = (uint16_t)h;
+      }
+      X::sync();
+      // links: the nearest lower position of the chunk with the same hash, else the head as before the chunk; mlen
+      // keeps a position's own link for its walk
+      for (uint32_t i = lane; i < 64; i += X::kLanes) {
+        const uint32_t p = b + i, h = S.mdist[i];
+        uint32_t c1 = 0;
+        if (h != kNoHash) {
+          uint32_t j = i;
+          while (j > 0 && S.mdist[j - 1] != h) j--;
+          c1 = j > 0 ? b + j : S.u.table[h];   // position b + j - 1, plus one
+          ring[p & (kRingLen - 1)] = (uint16_t)c1;
+        }
+        S.mlen[i] = (uint16_t)c1;
+      }
+      X::sync();
+      // heads: the highest position wins.  Walks: they read the ring, never the heads; mlen[i] and mdist[i] are read
+      // and written by position i's own lane from here to the next sync
+      for (uint32_t i = lane; i < 64; i += X::kLanes) {
+        const uint32_t p = b + i, h = S.mdist[i];
+        if (h != kNoHash) X::atomic_max16(&S.u.table[h], (uint16_t)(p + 1));
+        uint32_t c1 = S.mlen[i];
+        uint32_t best = 0, bdist = 0;
+        if (p >= next && p + 3 <= n) {
+          const uint32_t maxl = n - p < kMaxMatch ? n - p : kMaxMatch;
+          const uint32_t enough = maxl < lp.nice ? maxl : lp.nice;
+          uint32_t above = p;   // the candidate before this one: positions along a chain strictly decrease
+          for (uint32_t k = 0; k < lp.depth; k++) {
+            if (c1 == 0) break;
+            const uint32_t c = c1 - 1;
+            if (c >= above || p - c > kMaxDist) break;   // checked before c's link is read
+            if (best == 0 || in[c + best] == in[p + best]) {   // best < maxl: only a longer match replaces the best
+              const uint32_t l = match_length(in, c, p, maxl);
+              if (l > best) { best = l; bdist = p - c; }
+              if (l >= enough) break;
+            }
+            above = c;
+            c1 = ring[c & (kRingLen - 1)];
+          }
+          if (best < 3 || (best == 3 && bdist > kFar3)) { best = 0; bdist = 0; }
+        }
+        S.mlen[i] = (uint16_t)best;
+        S.mdist[i] = (uint16_t)(bdist - (bdist != 0));
+      }
+      X::sync();
+      select64(in, b, n, lp.lazy != 0, &next, &ntok);
+      X::sync();   // mlen / mdist are free again, the heads are in the table
     }
     if (lane == 0) { toks[ntok] = 256; S.lhist[256] += 1; }
     X::sync();
@@ -415,7 +548,8 @@ struct Deflater {
   }
 
   // One block.  Returns false when the stream no longer fits its capacity.
-  GKL_DEF_FN bool block(const uint8_t* in, uint32_t n, bool final, bool stored_only) {
+  GKL_DEF_FN bool block(const uint8_t* in, uint32_t n, bool final, int32_t level) {
+    const bool stored_only = level == 0;
     const uint64_t at = (uint64_t)outpos * 8 + carry;
     const uint32_t pad = (uint32_t)((8 - ((at + 3) & 7u)) & 7u);
     const uint64_t stored_bits = 3 + pad + 32 + 8ull * n;
@@ -423,7 +557,9 @@ struct Deflater {
     uint64_t dyn_bits = 0, fixed_bits = 0;
     uint32_t ntok = 0, hlit = 0, hdist = 0, hclen = 0;
     if (allow != BT_STORED) {
-      ntok = tokenize(in, n, strategy == STRATEGY_DEFAULT);
+      const bool search = strategy == STRATEGY_DEFAULT;
+      if ((kSearches & SEARCH_CHAINS) && search && level >= 3) ntok = tokenize_chains(in, n, level_params(level));
+      else ntok = tokenize(in, n, search && (kSearches & SEARCH_TABLE));
       const uint32_t hdr_bits = dynamic_codes(&hlit, &hdist, &hclen);
       dyn_bits = 3 + hdr_bits;
       fixed_bits = 3;
@@ -486,7 +622,7 @@ struct Deflater {
     uint32_t at = 0;
     do {
       const uint32_t n = len - at < kBlockLen ? len - at : kBlockLen;
-      if (!block(src + at, n, at + n == len, level == 0)) return ST_OUT_OVERFLOW;
+      if (!block(src + at, n, at + n == len, level)) return ST_OUT_OVERFLOW;
       at += n;
     } while (at < len);
     if (carry) {   // the capacity check of the last block counted this byte
@@ -506,12 +642,14 @@ constexpr int64_t deflate_bound(int64_t len) {
   return (len < 0 ? 0 : len) + 5 * blocks;
 }
 
-// One stream, 0 <= src_len, cap <= 2^31 - 1; level 0 (stored blocks only) or 1; types: a mask of BlockType, 0 = all.
-// toks: kTokensPerWave words that only these lanes use.  Every lane returns the same status and length.
-template <class X>
+// One stream, 0 <= src_len, cap <= 2^31 - 1; level 0 (stored blocks only), 1 or 3..8 (the callers refuse the others);
+// types: a mask of BlockType, 0 = all.  toks: kTokensPerWave words that only these lanes use; nothing is read from them
+// that this call has not written.  Every lane returns the same status and length.  kSearches: an instantiation without
+// SEARCH_CHAINS serves levels 0 and 1 only, one without SEARCH_TABLE levels 3..8 only.
+template <class X, int kSearches = SEARCH_BOTH>
 GKL_DEF_FN int deflate_stream(Scratch& S, const uint8_t* src, int32_t src_len, uint8_t* dst, int32_t cap, uint32_t* toks,
                               int32_t level, int32_t strategy, int32_t types, int32_t* out_len) {
-  Deflater<X> d(S, dst, (uint32_t)cap, toks, strategy, (types & BT_ALL) ? (types & BT_ALL) : BT_ALL);
+  Deflater<X, kSearches> d(S, dst, (uint32_t)cap, toks, strategy, (types & BT_ALL) ? (types & BT_ALL) : BT_ALL);
   return d.run(src, (uint32_t)src_len, level, out_len);
 }
 

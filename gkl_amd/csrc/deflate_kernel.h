@@ -5,9 +5,11 @@
 //
 // LDS: 20 160 B a wavefront (16 KB of it the match table, which the code construction, the CRC and the emission
 // reuse), so eight
-// workgroups fit a CU's 160 KB; the grid is kDeflateWavesPerCu per CU.  Tokens go to the wavefront's own 256 KB of
-// the context's token area in global memory and are read back by the same wavefront behind WaveExec::sync()
-// (__syncthreads() of a one-wavefront workgroup: see inflate_kernel.h on why that is visibility by the memory model).
+// workgroups fit a CU's 160 KB; the grid is kDeflateWavesPerCu per CU.  Tokens go to the wavefront's own 320 KB of
+// the context's token area in global memory (256 KB of tokens, then the 64 KB ring of chain links that levels 3-8 use)
+// and are read back by the same wavefront behind WaveExec::sync() (__syncthreads() of a one-wavefront workgroup: see
+// inflate_kernel.h on why that is visibility by the memory model).  At levels 3-8 lane i also walks the chain of
+// position i; the walk's bound is the level's depth, whatever the ring holds (deflate_core.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -78,6 +80,9 @@ struct DeflateWaveExec {
 // the pull loop; the wavefronts never wait for each other.
 constexpr int kDeflateWavesPerCu = 8;
 
+// Two instantiations: SEARCH_TABLE for levels 0 and 1, SEARCH_CHAINS for levels 3-8 (and for their Huffman-only
+// streams, which search nothing).  Neither carries the other's search, so level 1 pays nothing for the chains.
+template <int kSearches>
 __global__ __launch_bounds__(64) void deflate_kernel(DeflateArgs a) {
   __shared__ gkldef::Scratch S;
   const int lane = threadIdx.x;
@@ -94,7 +99,7 @@ __global__ __launch_bounds__(64) void deflate_kernel(DeflateArgs a) {
     uint32_t crc = 0;
     if (a.crc32) crc = gklinf::crc32_stream<DeflateWaveExec>(S.u.inf, in, (uint32_t)s.src_len);
     int32_t out_len = 0;
-    const int st = gkldef::deflate_stream<DeflateWaveExec>(S, in, s.src_len, a.dst + s.dst_off, s.cap, toks, a.level, a.strategy, a.types, &out_len);
+    const int st = gkldef::deflate_stream<DeflateWaveExec, kSearches>(S, in, s.src_len, a.dst + s.dst_off, s.cap, toks, a.level, a.strategy, a.types, &out_len);
     if (lane == 0) {
       a.status[si] = st;
       a.out_len[si] = out_len;

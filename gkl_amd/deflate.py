@@ -9,8 +9,10 @@ one whole raw-deflate stream, which is how htsjdk's BlockCompressedOutputStream 
 one deflate into a buffer that holds the whole BGZF block).  One stream per launch is the slow way to use a GPU
 (README, "Deflate"); the batch entry points of ``native.DeflateContext`` are the ones that pay.
 
-Built levels: 0 (stored blocks) and 1.  The reference sends levels 1 and 2 to ISA-L and the others to zlib; here every
-other level is refused at ``reset()``.  The stream is valid raw deflate, not the reference's byte sequence."""
+Built levels: 0 (stored blocks), 1 (one-entry hash table, greedy) and 3 to 8 (hash chains of depth 4 to 128, minimum
+match 3, lazy selection from level 4 on).  The reference sends levels 1 and 2 to ISA-L and the others to zlib; here
+levels 2, 9 and -1 (the default) are refused at ``reset()``.  The stream is valid raw deflate, not the reference's byte
+sequence."""
 from __future__ import annotations
 
 from typing import Optional
@@ -22,7 +24,7 @@ from .errors import ArrayIndexOutOfBoundsException, IllegalArgumentException, Nu
 
 DEFAULT_COMPRESSION = -1
 DEFAULT_STRATEGY = 0
-BUILT_LEVELS = (0, 1)
+BUILT_LEVELS = (0, 1, 3, 4, 5, 6, 7, 8)
 
 
 class IntelDeflater:
@@ -54,7 +56,7 @@ class IntelDeflater:
 
     def reset(self) -> None:
         if self.level not in BUILT_LEVELS or not self.nowrap:
-            raise RuntimeException(f"compression level {self.level} (nowrap={self.nowrap}) is not built: raw deflate at levels 0 and 1 is")
+            raise RuntimeException(f"compression level {self.level} (nowrap={self.nowrap}) is not built: raw deflate at levels 0, 1 and 3 to 8 is")
         if self._ctx is None and not self.load():
             raise RuntimeException("no gfx950 device: the deflater has no CPU path")
         self._input = None

@@ -1374,7 +1374,9 @@ def bgzf_bound(length: int, block_size: int = 0) -> int:
 
 
 class DeflateContext:
-    """One gklhip_deflate context: batches of independent inputs, one wavefront per raw-deflate stream."""
+    """One gklhip_deflate context: batches of independent inputs, one wavefront per raw-deflate stream.  `level` of
+    every call: 0 (stored blocks), 1 (the fast one) or 3 to 8 (hash chains, lazy matching from 4 on); 2, 9 and -1 raise
+    RuntimeException ("... is not built")."""
 
     def __init__(self, device: int = -1):
         self.lib = load_deflate_library()

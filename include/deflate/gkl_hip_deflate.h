@@ -8,7 +8,17 @@
  * that any inflater reads; it is NOT the byte sequence of zlib or ISA-L (no two deflaters agree on that).  The bytes of
  * a stream depend on its input, the level, the strategy and the block-type mask only.
  * The header has a directory of its own under include/ (see gkl_hip_inflate.h).
- * Not here: levels 2-9, a libgkl_compression drop-in, JNI, the zlib and gzip wrappers other than BGZF members.
+ *
+ * Levels: 0 = stored blocks only; 1 = a one-entry hash table of 4-byte keys, greedy selection (the fast one); 3 to 8 =
+ * hash chains of 3-byte keys searched to a depth, minimum match 3 (a 3-byte match farther back than 4096 is dropped),
+ * lazy selection from level 4 on, a walk over once a match of `nice` bytes is found:
+ *     level   3    4    5    6    7    8
+ *     depth   4    8   16   32   64  128
+ *     nice   32   32   64  128  258  258
+ *     lazy   no  yes  yes  yes  yes  yes
+ * The reference sends every level but 1 and 2 to zlib; 5 is htsjdk's default.  Huffman only gives the same bytes at
+ * every level from 1 to 8.  Levels 2, 9 and -1 (zlib's default) are left for a later change and are refused.
+ * Not here: levels 2, 9 and -1, a libgkl_compression drop-in, JNI, the zlib and gzip wrappers other than BGZF members.
  */
 #ifndef GKL_HIP_DEFLATE_H
 #define GKL_HIP_DEFLATE_H
@@ -30,7 +40,8 @@ enum {
 enum { GKLHIP_DEFLATE_DEFAULT_STRATEGY = 0, GKLHIP_DEFLATE_HUFFMAN_ONLY = 1 };
 enum { GKLHIP_DEFLATE_STORED = 1, GKLHIP_DEFLATE_FIXED = 2, GKLHIP_DEFLATE_DYNAMIC = 4 };
 
-/* init allocates the token area of the context once: 256 KB per resident wavefront (8 per compute unit). */
+/* init allocates the token area of the context once: 320 KB per resident wavefront (8 per compute unit) -- 256 KB of
+ * tokens and the 64 KB ring of chain links of levels 3 to 8 -- which is 640 MB on an MI355X's 256 compute units. */
 int gklhip_deflate_init(int device /* -1 = current */, gklhip_deflate_ctx** out_ctx);
 int gklhip_deflate_done(gklhip_deflate_ctx* ctx);
 
@@ -45,7 +56,7 @@ int gklhip_deflate_set_strategy(gklhip_deflate_ctx* ctx, int32_t strategy, int32
 
 /* n independent inputs.  Input k is src[src_off[k] .. src_off[k+1]); its stream goes to dst[dst_off[k] ..) with
  * capacity dst_off[k+1] - dst_off[k] (n + 1 non-decreasing offsets each; an input and a capacity are at most
- * 2^31 - 1 bytes).  level 0: stored blocks only; level 1: the encoder; other levels: GKLHIP_ERR_UNSUPPORTED.
+ * 2^31 - 1 bytes).  level 0, 1 or 3 to 8 (above); other levels: GKLHIP_ERR_UNSUPPORTED.
  * out_len[k] = bytes of the stream (0 on OUT_OVERFLOW).  crc32[k] = CRC-32 (zlib / BGZF polynomial) of INPUT k.
  * Nothing outside [dst_off[k], dst_off[k+1]) is written for stream k.  n == 0 succeeds and touches nothing. */
 int gklhip_deflate_batch(gklhip_deflate_ctx* ctx, int32_t n, const uint8_t* src, const int64_t* src_off, uint8_t* dst,
