@@ -939,7 +939,7 @@ struct PdJob {
           if (lane == 0) r[k] = v;
         }
       }
-      step<false>(cur);   // striped jobs (reads that need more than 64 lanes: 320 bases or more) keep the compute-and-select step
+      step<false>(cur);   // striped jobs (reads that need more than 64 lanes: 384 bases or more) keep the compute-and-select step
       cur = nxt;
       if (cout) {
         const int p = t - (kLanes - 1);

@@ -108,7 +108,7 @@ def main():
                 print(f"PDHMM MISMATCH seed={seed} fma={m} batch={pb.batch}", flush=True)
             if rnd % 3 == 0:
                 # the cross entry point (what computeLikelihoodsNative calls): few flags -> the LDS-table kernel, many
-                # or odd bases -> the predicate / byte-comparing kernels, reads of 320+ bases -> striped jobs
+                # or odd bases -> the predicate / byte-comparing kernels, reads of 384+ bases -> striped jobs
                 fr = float(rng.choice([0.0, 0.005, 0.02, 0.15]))
                 prd = random_pd_batch(rng, int(rng.randint(1, 90)), read_len=(1, int(rng.randint(2, 400))), hap_len=(1, 2))
                 phd = random_pd_batch(rng, int(rng.randint(1, 10)), read_len=(1, 2), hap_len=(1, int(rng.randint(2, 400))), flag_rate=fr,
